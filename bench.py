@@ -4,7 +4,14 @@
 Contract (driver):  python bench.py --gpus N --steps K --warmup W
   N>1 is launched as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
   (one rank per GPU, RCCL via backend "nccl"); rank 0 prints ONE JSON line.  Started WITHOUT a launcher
-  (`python bench.py --gpus N`, WORLD_SIZE unset) it re-executes itself under torch.distributed.run with N ranks.
+  (`python bench.py --gpus N`, WORLD_SIZE unset) it runs itself as a child under torch.distributed.run with N ranks.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs DIR is given,
+and prints the line.  Everything else it can measure or check -- CPU baselines, the bf16-storage, pipelined, index-cache,
+fb_projection, fb_projection_train and reference-kernel legs, the device fill rate and the store floors of the roofline, the
+device identity, the graph-vs-eager check, the other --conv-dtype of --mode train -- runs only with --full.
+--dump-outputs DIR: DIR/<name>.npy (float32 / float64, < 64 MB in all) of what the timed path computed in its last step; the
+  inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 --mode forward (default, the headline metric) | train (BASELINE configs[3]: forward_train + backward of the whole
   FB-OCC detector, 4 samples per GPU, gradients of ALL parameters averaged over ranks by bucketed RCCL all-reduces
@@ -99,15 +106,25 @@ def parse():
     ap.add_argument('--conv-dtype', choices=['f32', 'bf16'], default='bf16',
                     help='train mode: compute dtype of the 2-D stacks (image backbone / neck / depth net), channels-last on the vendor '
                          'library; default bf16 with fp32 master weights, gradients and every other block fp32 (stated in `dtype`)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run every extra leg, baseline and check beside the headline (off: set up, warm up, time the steps, '
+                         'print the line); the --no-* flags above then switch single legs off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         'a fixed seeded sample where the output is larger than 64 MB)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run --nproc-per-node N bench.py ...`
-    (one rank per GPU, rank -> GPU binding through LOCAL_RANK, rendezvous on 127.0.0.1)."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run --nproc-per-node N bench.py ...` as a child
+    process and exit with its status (one rank per GPU, rank -> GPU binding through LOCAL_RANK, rendezvous on 127.0.0.1)."""
     if args.gpus <= 1 or 'WORLD_SIZE' in os.environ:
         return
     import socket
+    import subprocess
     import torch
     have = torch.cuda.device_count()
     s = socket.socket()
@@ -116,7 +133,7 @@ def self_launch(args):
     s.close()
     cmd = launch_command(args, have, port)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def launch_command(args, have, port, argv=None):
@@ -728,6 +745,70 @@ def device_identity(dev):
     return out
 
 
+DUMP_SAMPLE = 1 << 21      # values kept of an output larger than this: 8 MB of float32 + 16 MB of float64 positions
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs files together
+
+
+def _sample_positions(numel, seed=0):
+    """Fixed, seeded flat positions (sorted, repeats possible) into an output of `numel` elements; None = keep all of them."""
+    import torch
+    if numel <= DUMP_SAMPLE:
+        return None
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, numel, (DUMP_SAMPLE,), generator=g).sort().values
+
+
+def _sampled(name, flat, pos):
+    """{name: all of `flat`} or {name_sample: its values at `pos`, name_sample_positions: `pos`}."""
+    if pos is None:
+        return {name: flat}
+    return {name + '_sample': flat[pos.to(flat.device)], name + '_sample_positions': pos.double()}
+
+
+def volume_outputs(out):
+    """What a caller of the forward step receives: the (B, C, Z, Y, X) BEV volume (3.3 GB at the default shapes) -- its values at
+    a fixed seeded sample of positions, and the float64 sum over Z, Y, X of every (sample, channel) of the whole volume."""
+    import torch
+    res = {'bev_volume_sum_bc': out.sum(dim=(2, 3, 4), dtype=torch.float64)}
+    flat = out.reshape(-1)
+    res.update(_sampled('bev_volume', flat, _sample_positions(flat.numel())))
+    return res
+
+
+def train_outputs(total, params):
+    """What the training step leaves: the loss, and every parameter after the optimizer step with the gradient the step applied
+    (all-reduced and clipped), flattened in parameter order -- both at one fixed seeded sample of positions, and float64 sums
+    per tensor."""
+    import torch
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    res = {'loss': total.detach().reshape(1),
+           'param_sum_per_tensor': torch.stack([p.detach().sum(dtype=torch.float64) for p in params]),
+           'grad_sum_per_tensor': torch.stack([g.detach().sum(dtype=torch.float64) for g in grads])}
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([g.detach().reshape(-1) for g in grads])
+    pos = _sample_positions(flat_p.numel())
+    res.update(_sampled('param', flat_p, pos))
+    res.update({k: v for k, v in _sampled('grad', flat_g, pos).items() if not k.endswith('_positions')})   # = param_sample_positions
+    return res
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy -- float64 stays float64, everything else becomes float32 (exact for the
+    16-bit storage types); at most DUMP_LIMIT bytes in all."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).numpy()
+    nbytes = sum(a.nbytes for a in host.values())
+    if nbytes > DUMP_LIMIT:
+        raise SystemExit(f'--dump-outputs: {nbytes} bytes, more than the {DUMP_LIMIT} allowed')
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def run_forward(args):
     import torch
     import torch.distributed as dist
@@ -838,7 +919,7 @@ def run_forward(args):
             idx = step()
     fence()
     dev_id = None
-    if rank == 0:                               # outside the timed region: queue a burst of steps and read the card's own busy counter under it
+    if args.full and rank == 0:                 # outside the timed region: queue a burst of steps and read the card's own busy counter under it
         for _ in range(20):
             step()
         dev_id = device_identity(dev)
@@ -850,10 +931,12 @@ def run_forward(args):
         fence()
         elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(elapsed, dev)
+    if args.dump_outputs and rank == 0:         # before anything else writes `out`
+        dump_outputs(args.dump_outputs, volume_outputs(out))
 
     # the graph-replayed step must produce what the eagerly launched step produces: one eager step into a second volume
     graph_equal = None
-    if graph is not None:
+    if args.full and graph is not None:
         ei, ef = prep()
         chk = torch.empty_like(out)
         pool(ei, ef, chk)
@@ -866,7 +949,7 @@ def run_forward(args):
     # The default line stays fp32 because that is what the reference's op computes and stores (bev_pool.py:16-22) and what
     # the bit-exact parity bar is defined on.
     alt = None
-    if world == 1 and args.storage == 'f32' and not args.no_alt_storage:
+    if args.full and world == 1 and args.storage == 'f32' and not args.no_alt_storage:
         v16 = LSSViewTransformerFunction3D(cfg.grid_config, cfg.input_size, cfg.downsample, out_dtype=torch.bfloat16).to(dev)
         tv16, fl16 = v16.tiling(cfg.n_cams)
         tws16 = v16._tile_ws(dev, B, tv16)
@@ -939,7 +1022,7 @@ def run_forward(args):
     # workspace and output volume.  The ranking kernels are short latency-bound launches (<= 256 workgroups) that leave
     # most of the chip idle; on a second stream they run under the HBM-bound pooling kernel of the previous batch.
     piped = None
-    if world == 1 and args.streams > 1:
+    if args.full and world == 1 and args.streams > 1:
         ns = args.streams
         ctxs = [(vt, tile_ws, out)]
         for _ in range(ns - 1):
@@ -1002,20 +1085,22 @@ def run_forward(args):
     pct = lambda q: step_ms[min(len(step_ms) - 1, int(q * len(step_ms)))] if step_ms else None  # noqa: E731
     # context for the roofline fraction (outside the timed region): what a plain device fill of the same output
     # buffer reaches on this box -- the practical write ceiling (report vs peak AND vs measured bandwidth)
-    fill_ms = []
-    for _ in range(7):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out.zero_()
-        b.record()
-        torch.cuda.synchronize(dev)
-        fill_ms.append(a.elapsed_time(b))
-    fill_gbs = out.numel() * esz / (sorted(fill_ms)[len(fill_ms) // 2] * 1e-3) / 1e9
+    fill_gbs = None
+    if args.full:
+        fill_ms = []
+        for _ in range(7):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            out.zero_()
+            b.record()
+            torch.cuda.synchronize(dev)
+            fill_ms.append(a.elapsed_time(b))
+        fill_gbs = out.numel() * esz / (sorted(fill_ms)[len(fill_ms) // 2] * 1e-3) / 1e9
     # the kernel's own STORE PATTERN as a floor: the same instantiation, grid, tile walk, XCD order and
     # `sc1 nt` stores with the gathers compiled out (mode 1: stores alone; mode 2: all but the depth / feature gathers),
     # timed per launch with HIP events like the real kernel; outside the timed region, results never used
     floors = {}
-    if args.storage == 'f32':
+    if args.full and args.storage == 'f32':
         feat_f = _capi.nchw_to_nhwc(ctx)
         scratch = torch.empty_like(out)
         # round 6: the real kernel and its three diagnostic instantiations are launched INTERLEAVED (K, 1, 2, 3, K, 1,
@@ -1065,7 +1150,7 @@ def run_forward(args):
     # `pre_compute` / `init_acceleration_v2`, view_transformer.py:500-519,607-611, disabled upstream): the six camera tensors are
     # compared on the device every step, the index build returns at once on a hit -- what a deployment with a fixed rig runs
     cached = None
-    if world == 1 and rank == 0 and args.storage == 'f32':
+    if args.full and world == 1 and rank == 0 and args.storage == 'f32':
         with torch.no_grad():
             vc = LSSViewTransformerFunction3D(cfg.grid_config, cfg.input_size, cfg.downsample, accelerate=True).to(dev)
             for _ in range(max(3, args.warmup)):
@@ -1088,7 +1173,7 @@ def run_forward(args):
 
     # Stated baseline beside `value`: the reference's own compiled kernel + its ATen index preparation on this GPU (never the target)
     ref_gpu = None
-    if world == 1 and rank == 0 and args.storage == 'f32' and not args.no_reference_gpu:
+    if args.full and world == 1 and rank == 0 and args.storage == 'f32' and not args.no_reference_gpu:
         try:
             ref_gpu = reference_same_gpu_leg(dev, cfg, B, cam, depth, ctx, vt, idx)
         except Exception as e:
@@ -1097,7 +1182,7 @@ def run_forward(args):
 
     # Extra leg (beside `value`, never as it): BASELINE configs[2] -- the backward-projection half of the path on this GPU
     fb = None
-    if world == 1 and rank == 0 and not args.no_fb_projection and cfg.name == 'BL2':
+    if args.full and world == 1 and rank == 0 and not args.no_fb_projection and cfg.name == 'BL2':
         del out
         try:
             fb = fb_projection_leg(dev, args.fb_steps, args.warmup, min(10.0, args.cpu_seconds), with_cpu=not args.no_cpu_baseline)
@@ -1106,7 +1191,7 @@ def run_forward(args):
 
     # Extra leg (beside `value`, never as it): the path's TRAINING step (forward + backward) at the same shapes -- VERDICT r5 item 1
     fbt = None
-    if world == 1 and rank == 0 and not args.no_fb_projection and not args.no_fb_train and cfg.name == 'BL2':
+    if args.full and world == 1 and rank == 0 and not args.no_fb_projection and not args.no_fb_train and cfg.name == 'BL2':
         try:
             import gc
             gc.collect()
@@ -1129,6 +1214,7 @@ def run_forward(args):
                        'every kernel launched one by one from the host'),
             'graph_step_equals_eager_step': graph_equal, 'launch_probe': launch_probe, 'graph_capture_error': graph_error,
             'timed_regions': 'cyclic garbage collector paused (collected before, re-enabled after); barrier + device synchronisation on both sides',
+            'full': args.full,
             'config': {'workload': f'FB-OCC forward projection, ' + ('BASELINE configs[1] ' if cfg.name == 'BL2' else '') +
                                    f'({cfg.name}): 6x{cfg.input_size[0]}x{cfg.input_size[1]} in, '
                                    f'feat {H}x{W}, D={D}, C={C}, grid {X}x{Y}x{Z}; index tensors rebuilt every step',
@@ -1139,7 +1225,7 @@ def run_forward(args):
                          'traffic_source': None if traffic is None else f'profiles/pmc_traffic.json[{key}] (rocprofv3 --pmc FETCH_SIZE / '
                                                                        'WRITE_SIZE passes of this command, recorded earlier -- not measured in this run)',
                          'algorithmic_bytes_per_launch': algo_bytes, 'kernel_ms': kern_ms,
-                         'device_fill_GBps': fill_gbs, 'frac_of_device_fill': achieved / fill_gbs if fill_gbs > 0 else None,
+                         'device_fill_GBps': fill_gbs, 'frac_of_device_fill': achieved / fill_gbs if fill_gbs else None,
                          'store_floor_ms': floors.get('store_floor_ms'), 'no_gather_ms': floors.get('no_gather_ms'),
                          'no_store_ms': floors.get('no_store_ms'),
                          'kernel_interleaved_ms': floors.get('kernel_interleaved_ms'),
@@ -1163,7 +1249,7 @@ def run_forward(args):
                 res['reference_same_gpu']['value_over_reference_s2'] = res['value'] / ref_gpu['samples_per_s']
         if piped is not None:
             res['pipelined'] = piped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(cfg, args.cpu_seconds)
             res['gpu_over_cpu'] = res['value'] / res['cpu_baseline']['value']
             try:
@@ -1262,10 +1348,12 @@ def run_train(args):
     elapsed, total = timed(step, args.steps, args.warmup)
     ar_tail_ms = sum(a.elapsed_time(b) for a, b in ar_ev) / max(1, args.steps)
     n_params, grad_bytes, n_buckets = sum(p.numel() for p in params), buckets.nbytes, len(buckets.buckets)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_outputs(total, params))
     # the OTHER arithmetic of the 2-D stacks beside it (VERDICT r3/r4 hygiene: the scope table's S5 is fp32, this line's default
     # bf16): the same step on a second model, half the steps; reported as `other_conv_dtype`, never as `value`
     other = None
-    if not args.no_alt_dtype:
+    if args.full and not args.no_alt_dtype:
         od = 'f32' if args.conv_dtype == 'bf16' else 'bf16'
         if not os.environ.get('FBBEV_TRAIN_PROFILE'):
             del model, opt, step

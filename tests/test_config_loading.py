@@ -43,16 +43,19 @@ def test_committed_extraction_builds():
         assert dn.context_conv.out_channels == info['numC_Trans']
 
 
-@pytest.mark.skipif(not LIVE, reason='reference tree not mounted (GPU box)')
-@pytest.mark.parametrize('path', LIVE, ids=[os.path.basename(p) for p in LIVE])
-def test_live_reference_config_loads_and_builds(path):
-    cfg = C.load_config(path)
-    assert cfg['model']['type'] in ('FBOCC', 'FBOCCTRT')
-    assert 'dataset_type' in cfg                                  # came through _base_ / the file itself
-    info = json.load(open(G))[os.path.basename(path)]
-    assert json.loads(json.dumps(C.path_blocks(cfg['model']))) == info['path_blocks']    # the fixture is current
-    fvt, hist = C.build_view_transformation(cfg['model'])
-    _check_built(fvt, hist, info)
+def test_live_reference_config_loads_and_builds():
+    """Every live reference config (one test whatever the machine holds, so its id does not depend on the reference tree)."""
+    if not LIVE:
+        pytest.skip(f'reference configs not found under {REF} (set FBBEV_REFERENCE)')
+    blocks = json.load(open(G))
+    for path in LIVE:
+        cfg = C.load_config(path)
+        assert cfg['model']['type'] in ('FBOCC', 'FBOCCTRT'), path
+        assert 'dataset_type' in cfg, path                            # came through _base_ / the file itself
+        info = blocks[os.path.basename(path)]
+        assert json.loads(json.dumps(C.path_blocks(cfg['model']))) == info['path_blocks'], path    # the fixture is current
+        fvt, hist = C.build_view_transformation(cfg['model'])
+        _check_built(fvt, hist, info)
 
 
 def test_base_merge_semantics(tmp_path):

@@ -10,7 +10,7 @@ timeout 600 python __graft_entry__.py smoke > $OUT/smoke.log 2>&1; echo "smoke r
 timeout 1800 python -m pytest tests -m gpu -q -s --timeout 900 -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/box.txt; tail -3 $OUT/pytest_gpu.log | cut -c1-300
 grep -E "max\|err|max\|coor|vs oracle|vs fp64|worst|deviation|observed|forward:|get_lidar|bits changed|BackwardProjection full" $OUT/pytest_gpu.log | cut -c1-400 > $OUT/gpu_tests_observed.txt
 tail -5 $OUT/pytest_gpu.log > $OUT/pytest_gpu_tail.txt
-timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/box.txt; cut -c1-600 $OUT/bench.json; tail -2 $OUT/bench.err
+timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?" | tee -a $OUT/box.txt; cut -c1-600 $OUT/bench.json; tail -2 $OUT/bench.err
 python tools/time_rows_kernels.py > $OUT/time_rows_kernels.jsonl 2>/dev/null
 python tools/time_bwd.py BL2 16 > $OUT/time_bwd_BL2_B16.jsonl 2>/dev/null; python tools/time_bwd.py BL2 4 >> $OUT/time_bwd_BL2_B16.jsonl 2>/dev/null
 python tools/train_path.py BL2 4 4 --steps 30 --checksum --sites > $OUT/time_train_path_BL2_B4_L4.json 2>/dev/null

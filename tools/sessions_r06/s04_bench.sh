@@ -1,6 +1,6 @@
 #!/bin/bash
 REPO=$(pwd); OUT=$REPO/gpurun_out/s04; mkdir -p $OUT; export TMPDIR=/tmp
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -3 $OUT/bench.err
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/s04/bench.json'))
