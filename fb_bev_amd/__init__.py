@@ -9,3 +9,24 @@ include/fbbev.h (csrc/), and the host-side mirrors of the reference's operator i
 There is no CPU fallback: ops raise if libfbbev_hip.so is missing or tensors are not on the GPU.
 """
 __version__ = '0.1.0'
+
+_deterministic_override = None
+
+
+def set_deterministic(mode):
+    """Deterministic mode of the library's backward kernels: True forces it on, False off, None follows torch
+    (deterministic_enabled).  Process-wide, like torch.use_deterministic_algorithms."""
+    global _deterministic_override
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError('set_deterministic takes True, False or None')
+    _deterministic_override = mode
+
+
+def deterministic_enabled():
+    """True when the library's gradients must be bit-reproducible: set_deterministic(True), or -- with no override --
+    torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic (what the reference's
+    tools/train.py --deterministic sets).  Read on every call, so the mode can change inside one process."""
+    if _deterministic_override is not None:
+        return _deterministic_override
+    import torch
+    return bool(torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic)

@@ -136,6 +136,20 @@ SIGNATURES = {
     'fbbev_da_cross_attn_bwd_planes': (c_int, [c_void_p] * 10 + [c_int] * 10 + [c_float, c_float, c_int, c_int] + [c_void_p] * 4 +
                                        [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     'fbbev_da_cross_attn_bwd_planes_supported': (c_int, [c_int] * 10 + [c_void_p, c_int]),
+    'fbbev_da_bwd_det_ws_bytes': (c_size_t, [c_int] * 7),
+    'fbbev_da_cross_attn_bwd_planes_ex': (c_int, [c_void_p] * 10 + [c_int] * 10 + [c_float, c_float, c_int, c_int] + [c_void_p] * 4 +
+                                          [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'fbbev_da_cross_attn_bwd_ws_grid_ex': (c_int, [c_void_p] * 10 + [c_int] * 10 + [c_float, c_float, c_int, c_int] + [c_void_p] * 4 +
+                                           [c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'fbbev_da_depth_taps_det_ws_bytes': (c_size_t, [c_int] * 5),
+    'fbbev_msda_bwd_det_ws_bytes': (c_size_t, [c_int] * 4),
+    'fbbev_da_cross_attn_bwd_det_ws_bytes': (c_size_t, [c_int] * 10),
+    'fbbev_da_cross_attn_bwd_ex': (c_int, [c_void_p] * 10 + [c_int] * 10 + [c_float, c_float, c_int, c_int] + [c_void_p] * 4 +
+                                   [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    'fbbev_msda_bwd_ex': (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
+    'fbbev_conv3d_wgrad_ws_bytes': (c_size_t, [c_int] * 8),
+    'fbbev_conv3d_wgrad_ndhwc_ex': (c_int, [c_void_p] * 2 + [c_int] * 12 + [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    'fbbev_da_depth_taps_det': (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_float, c_float] + [c_void_p, c_void_p, c_size_t, c_void_p]),
     'fbbev_msda_fwd_fused': (c_int, [c_void_p] * 6 + [c_int] * 9 + [c_void_p, c_void_p]),
     'fbbev_msda_bwd': (c_int, [c_void_p] * 6 + [c_int] * 7 + [c_void_p] * 3 + [c_void_p]),
     'fbbev_msda_bwd_ws_bytes': (c_size_t, [c_int] * 7 + [c_void_p]),
@@ -153,6 +167,9 @@ _lib = None
 
 class FbbevError(RuntimeError):
     pass
+
+
+FLAG_DETERMINISTIC = 0x1          # include/fbbev.h FBBEV_FLAG_DETERMINISTIC
 
 
 def declare(cdll):
@@ -589,6 +606,9 @@ def msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight
     level_hw check msda_bwd_ws_bytes() to know which."""
     B, S, M, Dh = value.shape
     _, Q, _, L, P, _ = sampling_loc.shape
+    if _deterministic():
+        return _msda_bwd_det(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
+                             grad_sampling_loc, grad_attn_weight, level_hw, B, S, M, Dh, L, Q, P)
     with _on(value):
         args = (_dev(value, F32, 'value'), _dev(spatial_shapes, I64, 'spatial_shapes'),
                 _dev(level_start_index, I64, 'level_start_index'), _dev(sampling_loc, F32, 'sampling_loc'),
@@ -601,6 +621,36 @@ def msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight
             _check(lib().fbbev_msda_bwd_ws(*args, _level_hw(level_hw, L), ws.data_ptr(), need, _stream()), 'fbbev_msda_bwd_ws')
         else:
             _check(lib().fbbev_msda_bwd(*args, _stream()), 'fbbev_msda_bwd')
+
+
+def _msda_bwd_det(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value, grad_sampling_loc,
+                  grad_attn_weight, level_hw, B, S, M, Dh, L, Q, P):
+    """Deterministic mode of msda_bwd, same contract as the default mode: with the caller's level_hw and a shape the band-binned
+    kernels take, grad_value is written by them; without level_hw (spatial_shapes read on the host) their result is added to
+    grad_value; else fbbev_msda_bwd_ex (fixed-point global scatter, accumulated into)."""
+    if B * Q * M == 0:
+        return
+    host_read = level_hw is None          # the caller chose the accumulating route: the band-binned result is added, not written
+    if host_read:
+        level_hw = _host_level_hw(spatial_shapes, 'msda_bwd')
+    need = msda_bwd_ws_bytes(B, S, M, Dh, L, Q, P, level_hw)
+    with _on(value):
+        args = (_dev(value, F32, 'value'), _dev(spatial_shapes, I64, 'spatial_shapes'),
+                _dev(level_start_index, I64, 'level_start_index'), _dev(sampling_loc, F32, 'sampling_loc'),
+                _dev(attn_weight, F32, 'attn_weight'), _dev(grad_output, F32, 'grad_output'), B, S, M, Dh, L, Q, P)
+        tail = (_dev(grad_sampling_loc, F32, 'grad_sampling_loc'), _dev(grad_attn_weight, F32, 'grad_attn_weight'))
+        if need:
+            gv = torch.empty_like(grad_value) if host_read else grad_value
+            ws = torch.empty((need + 3) // 4, dtype=torch.int32, device=value.device)
+            _check(lib().fbbev_msda_bwd_ws(*args, _dev(gv, F32, 'grad_value'), *tail, _level_hw(level_hw, L), ws.data_ptr(), need,
+                                           _stream()), 'fbbev_msda_bwd_ws')
+            if host_read:
+                grad_value.add_(gv)
+            return
+        dneed = lib().fbbev_msda_bwd_det_ws_bytes(B, S, M, Dh)
+        ws = torch.empty((dneed + 15) // 16 * 4, dtype=F32, device=value.device)
+        _check(lib().fbbev_msda_bwd_ex(*args, _dev(grad_value, F32, 'grad_value'), *tail, FLAG_DETERMINISTIC, ws.data_ptr(), dneed,
+                                       _stream()), 'fbbev_msda_bwd_ex')
 
 
 def da_cross_attn_fwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
@@ -703,6 +753,9 @@ def da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_
             B, Ncam, S, M, Dh, L, Q, P, Za, DC, float(d0), float(dstep), head_minor, HS,
             _dev(grad_value, F32, 'grad_value'), _dev(grad_pred_depth, F32, 'grad_pred_depth'),
             _dev(grad_offsets, F32, 'grad_offsets'), _dev(grad_attn, F32, 'grad_attn'))
+    if _deterministic():
+        return _da_cross_attn_bwd_det(args, value, spatial_shapes, offsets, grad_offsets, grad_slots, B, Ncam, S, M, Dh, Q, HS, L, P,
+                                      Za, DC, level_hw, bev_w)
     with _on(value):
         # value gradient through fixed-point LDS planes when the shape fits (fbbev_da_cross_attn_bwd_ws: output-owned planes + hit
         # lists, or query chunks + partial planes for small launches), else the global-atomic kernel
@@ -716,6 +769,55 @@ def da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_
                    'fbbev_da_cross_attn_bwd_ws_grid')
         else:
             _check(lib().fbbev_da_cross_attn_bwd(*args, _stream()), 'fbbev_da_cross_attn_bwd')
+
+
+def _deterministic():
+    from . import deterministic_enabled
+    return deterministic_enabled()
+
+
+def _host_level_hw(spatial_shapes, what):
+    """Deterministic mode without level_hw: one host read of spatial_shapes, so that a fixed-point route can be planned."""
+    if spatial_shapes.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise FbbevError(f'{what}: deterministic mode needs level_hw (host (h, w) pairs) inside a stream capture')
+    return [tuple(int(x) for x in hw) for hw in spatial_shapes.tolist()]
+
+
+def _da_det_ws(device, B, Ncam, Q, Za, DC, level_hw):
+    H0, W0 = (int(x) for x in level_hw[0])
+    need = lib().fbbev_da_bwd_det_ws_bytes(B, Ncam, Q, Za, DC, H0, W0)
+    if not need:
+        raise FbbevError('deterministic DA backward: no workspace for this shape')
+    return torch.empty((need + 3) // 4, dtype=F32, device=device), need
+
+
+def _da_cross_attn_bwd_det(args, value, spatial_shapes, offsets, grad_offsets, grad_slots, B, Ncam, S, M, Dh, Q, HS, L, P, Za, DC,
+                           level_hw, bev_w):
+    """Deterministic mode of da_cross_attn_bwd: an LDS-plane route (fixed-point value gradient) with the fixed-point depth taps
+    (fbbev_da_cross_attn_bwd_ws_grid_ex) where one plans the shape, else the global kernel with fixed-point value words
+    (fbbev_da_cross_attn_bwd_ex); lds_planes is ignored, a missing level_hw is read from spatial_shapes on the host."""
+    if B * Q * M == 0:
+        return
+    if level_hw is None:
+        level_hw = _host_level_hw(spatial_shapes, 'da_cross_attn_bwd')
+    arr = _level_hw(level_hw, L)
+    H0, W0 = (int(x) for x in level_hw[0])
+    with _on(value):
+        need = lib().fbbev_da_cross_attn_bwd_ws_bytes_za(B, Ncam, S, M, Dh, Q, HS, L, P, Za, arr)
+        if need:
+            if any(t.data_ptr() % 8 for t in (offsets, grad_offsets, grad_slots)):
+                need = max(need, lib().fbbev_da_cross_attn_bwd_ws_bytes(B, Ncam, S, M, Dh, Q, HS, L, P, arr))
+            ws = torch.empty(need // 4, dtype=torch.float32, device=value.device)
+            det_ws, det_need = _da_det_ws(value.device, B, Ncam, Q, Za, DC, level_hw)
+            code = lib().fbbev_da_cross_attn_bwd_ws_grid_ex(*args, arr, ws.data_ptr(), need, int(bev_w or 0), FLAG_DETERMINISTIC,
+                                                            det_ws.data_ptr(), det_need, _stream())
+            if code != -2:                                 # FBBEV_E_UNSUPPORTED: no LDS-plane route (nothing launched that matters)
+                _check(code, 'fbbev_da_cross_attn_bwd_ws_grid_ex')
+                return
+        dneed = lib().fbbev_da_cross_attn_bwd_det_ws_bytes(B, Ncam, S, M, HS, Q, Za, DC, H0, W0)
+        det_ws = torch.empty((dneed + 15) // 16 * 4, dtype=F32, device=value.device)
+        _check(lib().fbbev_da_cross_attn_bwd_ex(*args, H0, W0, FLAG_DETERMINISTIC, det_ws.data_ptr(), dneed, _stream()),
+               'fbbev_da_cross_attn_bwd_ex')
 
 
 def da_cross_attn_bwd_planes_supported(B, Ncam, S, M, Dh, L, Q, P, Za, HS, level_hw, bev_w):
@@ -738,6 +840,18 @@ def da_cross_attn_bwd_planes(planes, spatial_shapes, level_start_index, pred_dep
     arr = _level_hw(level_hw, L)
     need = lib().fbbev_da_cross_attn_bwd_ws_bytes_za(B, Ncam, S, M, Dh, Q, HS, L, P, Za, arr)
     ws = torch.empty(max(need, 16) // 4, dtype=F32, device=planes.device)
+    if _deterministic():
+        with _on(planes):
+            det_ws, det_need = _da_det_ws(planes.device, B, Ncam, Q, Za, DC, level_hw)
+            _check(lib().fbbev_da_cross_attn_bwd_planes_ex(
+                _dev(planes, F32, 'planes'), _dev(spatial_shapes, I64, 'spatial_shapes'),
+                _dev(level_start_index, I64, 'level_start_index'), _dev(pred_depth, F32, 'pred_depth'), _dev(ref_cam, F32, 'ref_cam'),
+                _dev(mask, torch.uint8, 'mask'), _dev(qdepth, F32, 'qdepth'), _dev(offsets, F32, 'offsets'), _dev(attn, F32, 'attn'),
+                _dev(grad_slots, F32, 'grad_slots'), B, Ncam, S, M, Dh, L, Q, P, Za, DC, float(d0), float(dstep), head_minor, int(HS),
+                _dev(grad_value, F32, 'grad_value'), _dev(grad_pred_depth, F32, 'grad_pred_depth'),
+                _dev(grad_offsets, F32, 'grad_offsets'), _dev(grad_attn, F32, 'grad_attn'), arr, ws.data_ptr(), need, int(bev_w),
+                FLAG_DETERMINISTIC, det_ws.data_ptr(), det_need, _stream()), 'fbbev_da_cross_attn_bwd_planes_ex')
+        return
     with _on(planes):
         _check(lib().fbbev_da_cross_attn_bwd_planes(
             _dev(planes, F32, 'planes'), _dev(spatial_shapes, I64, 'spatial_shapes'), _dev(level_start_index, I64, 'level_start_index'),
@@ -1461,6 +1575,14 @@ def conv3d_wgrad_ndhwc(x, dy, dw, ksize=3, stride=1, pad=1):
     _, Do, Ho, Wo, Cout = dy.shape
     if tuple(dw.shape) != (ksize ** 3, Cout, Cin):
         raise FbbevError('conv3d_wgrad_ndhwc: dw must be (ksize^3, Cout, Cin)')
+    if _deterministic():                 # chunk partials stored, then added in chunk order (no float atomics)
+        with _on(x):
+            need = lib().fbbev_conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, int(ksize), FLAG_DETERMINISTIC)
+            ws = torch.empty(max(need, 4) // 4, dtype=F32, device=x.device)
+            _check(lib().fbbev_conv3d_wgrad_ndhwc_ex(_dev(x, F32, 'x'), _dev(dy, F32, 'dy'), B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout,
+                                                     int(ksize), int(stride), int(pad), _dev(dw, F32, 'dw'), FLAG_DETERMINISTIC,
+                                                     ws.data_ptr(), need, _stream()), 'fbbev_conv3d_wgrad_ndhwc_ex')
+        return dw
     with _on(x):
         _check(lib().fbbev_conv3d_wgrad_ndhwc(_dev(x, F32, 'x'), _dev(dy, F32, 'dy'), B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout,
                                               int(ksize), int(stride), int(pad), _dev(dw, F32, 'dw'), _stream()),

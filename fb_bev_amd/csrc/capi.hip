@@ -22,6 +22,7 @@
 #include "da_bwd_planes_kernels.h"
 #include "msda_bwd_kernels.h"
 #include "conv3d_kernels.h"
+#include "det_kernels.h"
 #include "../../include/fbbev.h"
 
 #include "capi_common.h"
@@ -1194,6 +1195,57 @@ extern "C" int fbbev_msda_bwd(const float* value, const int64_t* spatial_shapes,
     return 0;
 }
 
+extern "C" size_t fbbev_msda_bwd_det_ws_bytes(int batch, int spatial_size, int num_heads, int channels) {
+    if (batch <= 0 || spatial_size <= 0 || num_heads <= 0 || channels <= 0) return 0;
+    return FBBEV_FIX_HDR + (size_t)batch * spatial_size * num_heads * channels * sizeof(unsigned long long);
+}
+// fbbev_msda_bwd with a flags word.  FBBEV_FLAG_DETERMINISTIC: the value gradient as 64-bit fixed point in det_ws (scale from
+// max |grad_output| x max |attn_weight|, at most num_query * num_point adds per word), converted and ADDED to grad_value.
+extern "C" int fbbev_msda_bwd_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                 const float* sampling_loc, const float* attn_weight, const float* grad_output, int batch,
+                                 int spatial_size, int num_heads, int channels, int num_levels, int num_query, int num_point,
+                                 float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int flags, void* det_ws,
+                                 size_t det_ws_bytes, fbbev_stream_t stream_) {
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC))
+        return fbbev_msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, batch, spatial_size,
+                              num_heads, channels, num_levels, num_query, num_point, grad_value, grad_sampling_loc, grad_attn_weight,
+                              stream_);
+    if (batch < 0 || spatial_size <= 0 || num_heads <= 0 || channels <= 0 || num_levels <= 0 ||
+        num_query < 0 || num_point <= 0) return FBBEV_E_BADARG;
+    const long long n_units = (long long)batch * num_query * num_heads;
+    if (n_units == 0) return 0;
+    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight ||
+        !grad_output || !grad_value || !grad_sampling_loc || !grad_attn_weight || !det_ws) return FBBEV_E_BADARG;
+    if (det_ws_bytes < fbbev_msda_bwd_det_ws_bytes(batch, spatial_size, num_heads, channels) || !aligned16(det_ws))
+        return FBBEV_E_WORKSPACE;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    const long long n_val = (long long)batch * spatial_size * num_heads * channels;
+    const long long n_out = n_units * channels, n_attn = n_units * num_levels * num_point;
+    unsigned int* hdr = static_cast<unsigned int*>(det_ws);
+    int e = fbbev_rt_memset_async(det_ws, 0, fbbev_msda_bwd_det_ws_bytes(batch, spatial_size, num_heads, channels), stream);
+    if (e) return e;
+    auto grid = [](long long n) { long long g = (n + 255) / 256; return g > 1024 ? 1024 : (g < 1 ? 1 : g); };
+    FBBEV_LAUNCH(k_da_taps_absmax, grid(n_out), 256, 0, stream, grad_output, n_out, hdr);
+    FBBEV_LAUNCH(k_da_taps_absmax, grid(n_attn), 256, 0, stream, attn_weight, n_attn, hdr + 1);
+    int kq = 0;
+    while ((1ll << kq) < (long long)num_query * num_point) ++kq;
+    FBBEV_LAUNCH(k_fix_scale, 1, 64, 0, stream, 2, kq, hdr);
+    FBBEV_CHECK_LAUNCH();
+    float* fix_ws = static_cast<float*>(det_ws);
+#define FBBEV_MSDA_BWD_FIX(GW)                                                                                     \
+    FBBEV_LAUNCH((k_msda_bwd<GW, true, true>), (n_units * GW + 255) / 256, 256, 0, stream, n_units, value,         \
+                 spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, spatial_size, num_heads, \
+                 channels, num_levels, num_query, num_point, fix_ws, grad_sampling_loc, grad_attn_weight)
+    if (channels <= 16) FBBEV_MSDA_BWD_FIX(16);
+    else if (channels <= 32) FBBEV_MSDA_BWD_FIX(32);
+    else FBBEV_MSDA_BWD_FIX(64);
+#undef FBBEV_MSDA_BWD_FIX
+    FBBEV_CHECK_LAUNCH();
+    FBBEV_LAUNCH(k_fix_to_f32_add, grid(n_val) * 4, 256, 0, stream, (const unsigned int*)hdr, n_val, grad_value);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
 // Band-binned fixed-point backward (msda_bwd_kernels.h).  level_hw_host: HOST array of L (h, w) pairs -- the band count is a
 // launch dimension.  Plan: tokens per LDS plane from the LDS budget (64 KB: two workgroups per CU; FBBEV_MSDA_BWD_LDS_KB,
 // read once, tunes it), a band = whole rows of one level.
@@ -1860,6 +1912,84 @@ extern "C" int fbbev_da_cross_attn_bwd(const float* value, const int64_t* spatia
     return 0;
 }
 
+// ---- deterministic form of the global-atomic kernel (k_da_cross_attn_bwd<GW, true>): det_ws = [fixed-point value words]
+// [per-head depth sums (Ncam, B, Q, M, Za)] [head-summed (Ncam, B, Q, Za)] [taps workspace]
+static size_t da_taps_ws_bytes(int B, int Ncam, int DC, int H0, int W0);
+static size_t da_glob_det_fix_bytes(int B, int Ncam, int S, int M, int HS) {
+    return align_up(FBBEV_FIX_HDR + (size_t)B * Ncam * S * M * HS * sizeof(unsigned long long), 256);
+}
+extern "C" size_t fbbev_da_cross_attn_bwd_det_ws_bytes(int B, int Ncam, int S, int M, int HS, int Q, int Za, int DC, int H0, int W0) {
+    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || HS <= 0 || Q < 0 || Za <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0) return 0;
+    const size_t cbq = (size_t)Ncam * B * Q;
+    return da_glob_det_fix_bytes(B, Ncam, S, M, HS) + align_up(cbq * M * Za * 4, 256) + align_up(cbq * Za * 4, 256) +
+           da_taps_ws_bytes(B, Ncam, DC, H0, W0);
+}
+// fbbev_da_cross_attn_bwd with a flags word.  FBBEV_FLAG_DETERMINISTIC: the value gradient as 64-bit fixed point (scale from
+// max |grad_slots| x max |attn| x max |pred_depth|, at most Q * P adds per word), the depth taps through fbbev_da_depth_taps_det;
+// grad_value / grad_pred_depth accumulated into as by the plain entry.  H0, W0: level 0's shape on the host.
+extern "C" int fbbev_da_cross_attn_bwd_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                          const float* pred_depth, const float* ref_cam, const uint8_t* mask,
+                                          const float* qdepth, const float* offsets, const float* attn,
+                                          const float* grad_slots, int B, int Ncam, int S, int M, int Dh, int L, int Q,
+                                          int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
+                                          float* grad_value, float* grad_pred_depth, float* grad_offsets,
+                                          float* grad_attn, int H0, int W0, int flags, void* det_ws, size_t det_ws_bytes,
+                                          fbbev_stream_t stream_) {
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC))
+        return fbbev_da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                       grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, grad_value,
+                                       grad_pred_depth, grad_offsets, grad_attn, stream_);
+    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0)
+        return FBBEV_E_BADARG;
+    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
+    if (dstep == 0.f) return FBBEV_E_BADARG;
+    const long long units = (long long)B * Q * M;
+    if (units == 0) return 0;
+    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets ||
+        !attn || !grad_slots || !grad_value || !grad_pred_depth || !grad_offsets || !grad_attn || !det_ws) return FBBEV_E_BADARG;
+    if (Dh > 32) return FBBEV_E_UNSUPPORTED;
+    const int HS = head_stride == 0 ? Dh : head_stride;
+    if (HS < Dh) return FBBEV_E_BADARG;
+    if ((head_minor & 4) && HS % 4 != 0) return FBBEV_E_UNSUPPORTED;
+    if ((units * 32 + 255) / 256 >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (det_ws_bytes < fbbev_da_cross_attn_bwd_det_ws_bytes(B, Ncam, S, M, HS, Q, Za, DC, H0, W0) || !aligned16(det_ws))
+        return FBBEV_E_WORKSPACE;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    char* w = static_cast<char*>(det_ws);
+    const size_t fix_b = da_glob_det_fix_bytes(B, Ncam, S, M, HS);
+    const long long cbq = (long long)Ncam * B * Q;
+    float* per_head = reinterpret_cast<float*>(w + fix_b);
+    float* dsum = reinterpret_cast<float*>(w + fix_b + align_up((size_t)cbq * M * Za * 4, 256));
+    char* taps = reinterpret_cast<char*>(dsum) + align_up((size_t)cbq * Za * 4, 256);
+    int e = fbbev_rt_memset_async(w, 0, fix_b + align_up((size_t)cbq * M * Za * 4, 256), stream);
+    if (e) return e;
+    unsigned int* hdr = reinterpret_cast<unsigned int*>(w);
+    auto grid = [](long long n) { long long g = (n + 255) / 256; return g > 1024 ? 1024 : (g < 1 ? 1 : g); };
+    const long long n_g = units * Dh, n_a = units * L * P, n_d = (long long)B * Ncam * DC * H0 * W0;
+    FBBEV_LAUNCH(k_da_taps_absmax, grid(n_g), 256, 0, stream, grad_slots, n_g, hdr);
+    FBBEV_LAUNCH(k_da_taps_absmax, grid(n_a), 256, 0, stream, attn, n_a, hdr + 1);
+    FBBEV_LAUNCH(k_da_taps_absmax, grid(n_d), 256, 0, stream, pred_depth, n_d, hdr + 2);
+    int kq = 0;
+    while ((1ll << kq) < (long long)Q * P) ++kq;
+    FBBEV_LAUNCH(k_fix_scale, 1, 64, 0, stream, 3, kq, hdr);
+    FBBEV_CHECK_LAUNCH();
+    float* fix_ws = reinterpret_cast<float*>(w);
+#define FBBEV_DA_BWD_FIX(GW_)                                                                                           \
+    FBBEV_LAUNCH((k_da_cross_attn_bwd<GW_, true>), (units * GW_ + 255) / 256, 256, 0, stream, units, value,             \
+                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B,    \
+                 Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor & 7, HS, fix_ws, per_head, grad_offsets, grad_attn)
+    if (Dh <= 16) FBBEV_DA_BWD_FIX(16);
+    else FBBEV_DA_BWD_FIX(32);
+#undef FBBEV_DA_BWD_FIX
+    FBBEV_CHECK_LAUNCH();
+    const long long n_v = (long long)B * Ncam * S * M * HS;
+    FBBEV_LAUNCH(k_fix_to_f32_add, grid(n_v) * 4, 256, 0, stream, (const unsigned int*)hdr, n_v, grad_value);
+    FBBEV_LAUNCH(k_da_head_sum, grid(cbq * Za) * 4, 256, 0, stream, (const float*)per_head, cbq, M, Za, dsum);
+    FBBEV_CHECK_LAUNCH();
+    return fbbev_da_depth_taps_det(dsum, ref_cam, qdepth, B, Ncam, Q, Za, DC, H0, W0, d0, dstep, grad_pred_depth, taps,
+                                   da_taps_ws_bytes(B, Ncam, DC, H0, W0), stream_);
+}
+
 // LDS-plane backward (needs a caller-owned partial buffer): k_da_cross_attn_bwd_unit (unit-owned gradients) +
 // k_da_cross_attn_bwd_scatter per token region + k_da_bwd_reduce
 struct da_region { int lvl0, lvl1, tok0, tok1; };
@@ -2097,27 +2227,29 @@ static int da_bwd_unit_launch(fbbev_rt_stream stream, const float* value, const 
                               const float* qdepth, const float* offsets, const float* attn, const float* grad_slots, int B,
                               int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                               int head_minor, int HS, float* grad_pred_depth, float* grad_offsets, float* grad_attn,
-                              unsigned int* gmax_bits) {
+                              unsigned int* gmax_bits, bool det = false) {
     // (A) unit-owned gradients, the forward's launch shape
     const long long units = (long long)B * Q * M;
     long long ub = ((units + 255) / 256 + 7) / 8 * 8;
     if (ub > 65536) ub = 65536;
     const size_t lds_a = (size_t)256 * (4 * P + 1) * sizeof(float);
     const bool qi = (head_minor & 4) != 0;
+#define FBBEV_DA_BWD_UNIT_K(DH_, QI_, DET_)                                                                             \
+    FBBEV_LAUNCH((k_da_cross_attn_bwd_unit<DH_, QI_, DET_>), ub, 256, lds_a, stream, units, value, spatial_shapes,        \
+                 level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, \
+                 DC, d0, dstep, head_minor & 3, HS, grad_pred_depth, grad_offsets, grad_attn, gmax_bits)
 #define FBBEV_DA_BWD_UNIT(DH_)                                                                                          \
     do {                                                                                                                \
-    if (qi) FBBEV_LAUNCH((k_da_cross_attn_bwd_unit<DH_, true>), ub, 256, lds_a, stream, units, value, spatial_shapes, \
-                         level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, \
-                         L, Q, P, Za, DC, d0, dstep, head_minor & 3, HS, grad_pred_depth, grad_offsets, grad_attn, gmax_bits); \
-    else FBBEV_LAUNCH((k_da_cross_attn_bwd_unit<DH_, false>), ub, 256, lds_a, stream, units, value, spatial_shapes, \
-                      level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, \
-                      L, Q, P, Za, DC, d0, dstep, head_minor & 3, HS, grad_pred_depth, grad_offsets, grad_attn, gmax_bits); \
+    if (det) { if (qi) FBBEV_DA_BWD_UNIT_K(DH_, true, true); else FBBEV_DA_BWD_UNIT_K(DH_, false, true); }             \
+    else if (qi) FBBEV_DA_BWD_UNIT_K(DH_, true, false);                                                                 \
+    else FBBEV_DA_BWD_UNIT_K(DH_, false, false);                                                                        \
     } while (0)
     if (Dh == 10) FBBEV_DA_BWD_UNIT(10);
     else if (Dh == 8) FBBEV_DA_BWD_UNIT(8);
     else if (Dh == 4) FBBEV_DA_BWD_UNIT(4);
     else FBBEV_DA_BWD_UNIT(16);
 #undef FBBEV_DA_BWD_UNIT
+#undef FBBEV_DA_BWD_UNIT_K
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2128,7 +2260,7 @@ static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, co
                                const float* qdepth, const float* offsets, const float* attn, const float* grad_slots, int B,
                                int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                                int head_minor, int HS, float* grad_value, float* grad_pred_depth, float* grad_offsets,
-                               float* grad_attn, void* ws, int bev_w, const float* planes_in = nullptr) {
+                               float* grad_attn, void* ws, int bev_w, const float* planes_in = nullptr, bool det = false) {
     char* w = static_cast<char*>(ws);
     float* hit_rec = reinterpret_cast<float*>(w + op.off_list);
     int* hit_count = reinterpret_cast<int*>(w + op.off_count);
@@ -2161,13 +2293,24 @@ static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, co
                      level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, L, Q, \
                      gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn, gmax_bits);           \
     } while (0)
-        if (Dh == 10) FBBEV_DA_UNIT_PLANES(10); else FBBEV_DA_UNIT_PLANES(8);
+#define FBBEV_DA_UNIT_PLANES_DET(DH_)                                                                                 \
+    do {                                                                                                               \
+        e = fbbev_rt_allow_dyn_lds((const void*)k_da_bwd_unit_planes<DH_, 8, true>, lds_u);                            \
+        if (e) return e;                                                                                               \
+        FBBEV_LAUNCH((k_da_bwd_unit_planes<DH_, 8, true>), grid_u, 512, lds_u, stream, (const float*)planes,           \
+                     spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, \
+                     Ncam, S, L, Q, gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn,         \
+                     gmax_bits);                                                                                       \
+    } while (0)
+        if (det) { if (Dh == 10) FBBEV_DA_UNIT_PLANES_DET(10); else FBBEV_DA_UNIT_PLANES_DET(8); }
+        else if (Dh == 10) FBBEV_DA_UNIT_PLANES(10); else FBBEV_DA_UNIT_PLANES(8);
+#undef FBBEV_DA_UNIT_PLANES_DET
 #undef FBBEV_DA_UNIT_PLANES
         FBBEV_CHECK_LAUNCH();
     } else {
         e = da_bwd_unit_launch(stream, value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
                                grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS, grad_pred_depth,
-                               grad_offsets, grad_attn, gmax_bits);
+                               grad_offsets, grad_attn, gmax_bits, det);
         if (e) return e;
     }
     FBBEV_LAUNCH(k_da_bwd_hitlist, (long long)B * ((Q + 255) / 256), 256, 0, stream, spatial_shapes, pred_depth, ref_cam, mask,
@@ -2195,6 +2338,72 @@ static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, co
     return 0;
 }
 
+// ---- deterministic depth taps (det_kernels.h): workspace = [per-(camera, sample, query, anchor) sums][max bits][fixed-point planes]
+static size_t da_taps_ws_bytes(int B, int Ncam, int DC, int H0, int W0) {
+    return 256 + align_up((size_t)B * Ncam * DC * H0 * W0 * sizeof(unsigned long long), 256);
+}
+static int da_taps_kq(int Q, int Za) {
+    int kq = 0;
+    while ((1ll << kq) < (long long)Q * Za) ++kq;
+    return kq;
+}
+extern "C" size_t fbbev_da_depth_taps_det_ws_bytes(int B, int Ncam, int DC, int H0, int W0) {
+    if (B <= 0 || Ncam <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0) return 0;
+    return da_taps_ws_bytes(B, Ncam, DC, H0, W0);
+}
+extern "C" int fbbev_da_depth_taps_det(const float* dsum, const float* ref_cam, const float* qdepth, int B, int Ncam, int Q, int Za, int DC,
+                                       int H0, int W0, float d0, float dstep, float* grad_pred_depth, void* ws, size_t ws_bytes,
+                                       fbbev_stream_t stream_) {
+    if (B <= 0 || Ncam <= 0 || Q < 0 || Za <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0 || dstep == 0.f) return FBBEV_E_BADARG;
+    if (!dsum || !ref_cam || !qdepth || !grad_pred_depth || !ws) return FBBEV_E_BADARG;
+    if (ws_bytes < da_taps_ws_bytes(B, Ncam, DC, H0, W0) || ((uintptr_t)ws & 7) != 0) return FBBEV_E_WORKSPACE;
+    if ((long long)H0 * W0 >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (Q == 0) return 0;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    unsigned int* gmax = static_cast<unsigned int*>(ws);
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + 256);
+    const long long n_sum = (long long)Ncam * B * Q * Za, n_out = (long long)B * Ncam * DC * H0 * W0;
+    int e = fbbev_rt_memset_async(ws, 0, da_taps_ws_bytes(B, Ncam, DC, H0, W0), stream);
+    if (e) return e;
+    const int kq = da_taps_kq(Q, Za);
+    long long gs = (n_sum + 255) / 256, go = (n_out + 255) / 256;
+    gs = gs > 4096 ? 4096 : gs; go = go > 4096 ? 4096 : go;
+    FBBEV_LAUNCH(k_da_taps_absmax, gs > 1024 ? 1024 : gs, 256, 0, stream, dsum, n_sum, gmax);
+    FBBEV_CHECK_LAUNCH();
+    FBBEV_LAUNCH(k_da_taps_i64, gs, 256, 0, stream, dsum, ref_cam, qdepth, B, Ncam, Q, Za, DC, H0, W0, d0, dstep, kq,
+                 (const unsigned int*)gmax, acc);
+    FBBEV_CHECK_LAUNCH();
+    FBBEV_LAUNCH(k_i64_to_f32_add, go, 256, 0, stream, (const unsigned long long*)acc, n_out, kq, (const unsigned int*)gmax,
+                 grad_pred_depth);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" size_t fbbev_da_bwd_det_ws_bytes(int B, int Ncam, int Q, int Za, int DC, int H0, int W0) {
+    if (B <= 0 || Ncam <= 0 || Q <= 0 || Za <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0) return 0;
+    return align_up((size_t)Ncam * B * Q * Za * sizeof(float), 256) + da_taps_ws_bytes(B, Ncam, DC, H0, W0);
+}
+// The unit kernels' DET instantiations store the head-summed d / d depth weight into the front of det_ws (zeroed here first: a unit
+// no camera sees stores nothing), `run` launches the route with that buffer as its grad_pred_depth, then the taps are added.
+template <class Run>
+static int da_bwd_det(int B, int Ncam, int M, int Q, int Za, int DC, const int32_t* level_hw_host, const float* ref_cam,
+                      const float* qdepth, float d0, float dstep, float* grad_pred_depth, void* det_ws, size_t det_ws_bytes,
+                      fbbev_stream_t stream_, Run run) {
+    if (!level_hw_host || !det_ws || !ref_cam || !qdepth || !grad_pred_depth) return FBBEV_E_BADARG;
+    if (B <= 0 || Ncam <= 0 || Q <= 0 || Za <= 0 || DC <= 0 || dstep == 0.f) return FBBEV_E_BADARG;
+    if (M > 64 || (M & (M - 1)) != 0) return FBBEV_E_UNSUPPORTED;                  // the unit kernel's head reduction
+    const int H0 = level_hw_host[0], W0 = level_hw_host[1];
+    if (H0 <= 0 || W0 <= 0) return FBBEV_E_BADARG;
+    if (det_ws_bytes < fbbev_da_bwd_det_ws_bytes(B, Ncam, Q, Za, DC, H0, W0) || !aligned16(det_ws)) return FBBEV_E_WORKSPACE;
+    const size_t sum_bytes = align_up((size_t)Ncam * B * Q * Za * sizeof(float), 256);
+    float* dsum = static_cast<float*>(det_ws);
+    int e = fbbev_rt_memset_async(dsum, 0, sum_bytes, (fbbev_rt_stream)stream_);
+    if (e) return e;
+    e = run(dsum);
+    if (e) return e;
+    return fbbev_da_depth_taps_det(dsum, ref_cam, qdepth, B, Ncam, Q, Za, DC, H0, W0, d0, dstep, grad_pred_depth,
+                                   static_cast<char*>(det_ws) + sum_bytes, det_ws_bytes - sum_bytes, stream_);
+}
+
 static int da_cross_attn_bwd_ws_impl(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                           const float* pred_depth, const float* ref_cam, const uint8_t* mask,
                                           const float* qdepth, const float* offsets, const float* attn,
@@ -2202,7 +2411,7 @@ static int da_cross_attn_bwd_ws_impl(const float* value, const int64_t* spatial_
                                           int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
                                           float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                           float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
-                                          fbbev_stream_t stream_, int bev_w) {
+                                          fbbev_stream_t stream_, int bev_w, bool det = false) {
     if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w < 0)
         return FBBEV_E_BADARG;
     const int HS = head_stride == 0 ? Dh : head_stride;
@@ -2215,14 +2424,14 @@ static int da_cross_attn_bwd_ws_impl(const float* value, const int64_t* spatial_
             da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, L, P, Za, level_hw_host, &op) && ws_bytes >= op.ws)
             return da_bwd_owned_launch(op, (fbbev_rt_stream)stream_, value, spatial_shapes, level_start_index, pred_depth, ref_cam,
                                        mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep,
-                                       head_minor, HS, grad_value, grad_pred_depth, grad_offsets, grad_attn, ws, bev_w);
+                                       head_minor, HS, grad_value, grad_pred_depth, grad_offsets, grad_attn, ws, bev_w, nullptr, det);
     }
     da_bwd_plan pl;
     if (HS < Dh || Q == 0 || !ws || !aligned16(ws) || !aligned16(grad_value) || !aligned16(value) ||
         !da_bwd_tile_plan(B, Ncam, S, M, Dh, Q, HS, L, P, level_hw_host, &pl) || ws_bytes < pl.ws ||
         (long long)B * M * pl.chunks >= (1ll << 31) || (long long)B * Ncam * S * M * HS * 4 >= (1ll << 32) ||
         (((uintptr_t)offsets | (uintptr_t)grad_offsets | (uintptr_t)grad_slots) & 7) != 0)
-        return fbbev_da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
+        return det ? FBBEV_E_UNSUPPORTED : fbbev_da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
                                        attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor,
                                        head_stride, grad_value, grad_pred_depth, grad_offsets, grad_attn, stream_);
     if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
@@ -2244,7 +2453,7 @@ static int da_cross_attn_bwd_ws_impl(const float* value, const int64_t* spatial_
         {
             const int e = da_bwd_unit_launch(stream, value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
                                              attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS,
-                                             grad_pred_depth, grad_offsets, grad_attn, nullptr);
+                                             grad_pred_depth, grad_offsets, grad_attn, nullptr, det);
             if (e) return e;
         }
         // (B) value gradient, one launch per token region
@@ -2307,6 +2516,26 @@ extern "C" int fbbev_da_cross_attn_bwd_ws_grid(const float* value, const int64_t
                                      grad_value, grad_pred_depth, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, stream_,
                                      bev_w);
 }
+// ... with a flags word (FBBEV_FLAG_DETERMINISTIC: the depth taps as 64-bit fixed point, no float atomics; det_ws of
+// fbbev_da_bwd_det_ws_bytes; a shape neither LDS-plane route takes is FBBEV_E_UNSUPPORTED instead of the global-atomic kernel)
+extern "C" int fbbev_da_cross_attn_bwd_ws_grid_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                                  const float* pred_depth, const float* ref_cam, const uint8_t* mask,
+                                                  const float* qdepth, const float* offsets, const float* attn,
+                                                  const float* grad_slots, int B, int Ncam, int S, int M, int Dh, int L, int Q,
+                                                  int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
+                                                  float* grad_value, float* grad_pred_depth, float* grad_offsets,
+                                                  float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
+                                                  int bev_w, int flags, void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream_) {
+    const bool det = (flags & FBBEV_FLAG_DETERMINISTIC) != 0;
+    auto run = [&](float* gpd) {
+        return da_cross_attn_bwd_ws_impl(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                         grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
+                                         grad_value, gpd, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, stream_, bev_w, det);
+    };
+    if (!det) return run(grad_pred_depth);
+    return da_bwd_det(B, Ncam, M, Q, Za, DC, level_hw_host, ref_cam, qdepth, d0, dstep, grad_pred_depth, det_ws, det_ws_bytes, stream_,
+                      run);
+}
 
 // Round 6: the backward of fbbev_da_cross_attn_fused for the training step that runs the one-kernel forward -- the camera tokens arrive as
 // the HEAD PLANES the forward sampled (fbbev_rows_linear_x3_planes: no row copy of them exists), and on this route every output but
@@ -2322,13 +2551,13 @@ extern "C" int fbbev_da_cross_attn_bwd_planes_supported(int B, int Ncam, int S, 
     if (HS < Dh || P % Za != 0 || Za != FBBEV_DAF_ZA || !da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, L, P, Za, level_hw_host, &op)) return 0;
     return op.unit_planes ? 1 : 0;
 }
-extern "C" int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                              const float* pred_depth, const float* ref_cam, const uint8_t* mask,
-                                              const float* qdepth, const float* offsets, const float* attn, const float* grad_slots,
-                                              int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
-                                              float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
-                                              float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
-                                              size_t ws_bytes, int bev_w, fbbev_stream_t stream_) {
+static int da_cross_attn_bwd_planes_impl(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                         const float* pred_depth, const float* ref_cam, const uint8_t* mask,
+                                         const float* qdepth, const float* offsets, const float* attn, const float* grad_slots,
+                                         int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
+                                         float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
+                                         float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
+                                         size_t ws_bytes, int bev_w, fbbev_stream_t stream_, bool det) {
     if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w <= 0)
         return FBBEV_E_BADARG;
     if (!planes || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets || !attn ||
@@ -2344,7 +2573,37 @@ extern "C" int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t
     if (ws_bytes < op.ws) return FBBEV_E_WORKSPACE;
     return da_bwd_owned_launch(op, (fbbev_rt_stream)stream_, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth,
                                offsets, attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS, grad_value,
-                               grad_pred_depth, grad_offsets, grad_attn, ws, bev_w, planes);
+                               grad_pred_depth, grad_offsets, grad_attn, ws, bev_w, planes, det);
+}
+extern "C" int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                              const float* pred_depth, const float* ref_cam, const uint8_t* mask,
+                                              const float* qdepth, const float* offsets, const float* attn, const float* grad_slots,
+                                              int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
+                                              float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
+                                              float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
+                                              size_t ws_bytes, int bev_w, fbbev_stream_t stream_) {
+    return da_cross_attn_bwd_planes_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                         grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, grad_value,
+                                         grad_pred_depth, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, bev_w, stream_, false);
+}
+// ... with a flags word (FBBEV_FLAG_DETERMINISTIC: the depth taps as 64-bit fixed point, det_ws of fbbev_da_bwd_det_ws_bytes)
+extern "C" int fbbev_da_cross_attn_bwd_planes_ex(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                                 const float* pred_depth, const float* ref_cam, const uint8_t* mask,
+                                                 const float* qdepth, const float* offsets, const float* attn, const float* grad_slots,
+                                                 int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
+                                                 float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
+                                                 float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
+                                                 size_t ws_bytes, int bev_w, int flags, void* det_ws, size_t det_ws_bytes,
+                                                 fbbev_stream_t stream_) {
+    const bool det = (flags & FBBEV_FLAG_DETERMINISTIC) != 0;
+    auto run = [&](float* gpd) {
+        return da_cross_attn_bwd_planes_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
+                                             attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
+                                             grad_value, gpd, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, bev_w, stream_, det);
+    };
+    if (!det) return run(grad_pred_depth);
+    return da_bwd_det(B, Ncam, M, Q, Za, DC, level_hw_host, ref_cam, qdepth, d0, dstep, grad_pred_depth, det_ws, det_ws_bytes, stream_,
+                      run);
 }
 
 // ---------------------------------------------------------------- fused lift-splat backward (training)
@@ -3544,9 +3803,15 @@ extern "C" int fbbev_conv3d_dgrad_ndhwc(const float* dy, const float* weight_fra
                          2, dx, stream_);
 }
 
-extern "C" int fbbev_conv3d_wgrad_ndhwc(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do,
-                                        int Ho, int Wo, int Cout, int ksize, int stride, int pad, float* dw,
-                                        fbbev_stream_t stream_) {
+// voxel chunk per wave: enough chunks to fill the chip a few times over, at least 256 voxels (16 loop iterations)
+static long long conv3d_wgrad_chunk(long long nvox) {
+    long long chunk = nvox / 64;
+    if (chunk < 256) chunk = 256;
+    if (chunk > 4096) chunk = 4096;
+    return (chunk + 15) / 16 * 16;
+}
+static int conv3d_wgrad_impl(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
+                             int ksize, int stride, int pad, float* dw, float* part, fbbev_stream_t stream_) {
     if (B < 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
     if (ksize < 1 || ksize > 3 || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
     if (!conv3d_geometry_ok(Di, Do, ksize, stride, pad) || !conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) ||
@@ -3555,23 +3820,50 @@ extern "C" int fbbev_conv3d_wgrad_ndhwc(const float* x, const float* dy, int B, 
     if (!x || !dy || !dw) return FBBEV_E_BADARG;
     if (Cin % 4 != 0 || Cout % 4 != 0 || !aligned16(x) || !aligned16(dy)) return FBBEV_E_UNSUPPORTED;
     const long long nvox = (long long)B * Do * Ho * Wo;
-    // voxel chunk per wave: enough chunks to fill the chip a few times over, at least 256 voxels (16 loop iterations)
     const int cout_blocks = (Cout + 63) / 64, cin_blocks = (Cin + 63) / 64, T = ksize * ksize * ksize;
-    long long chunk = nvox / 64;
-    if (chunk < 256) chunk = 256;
-    if (chunk > 4096) chunk = 4096;
-    chunk = (chunk + 15) / 16 * 16;
+    const long long chunk = conv3d_wgrad_chunk(nvox);
     const long long n_chunks = (nvox + chunk - 1) / chunk;
     const long long tasks = n_chunks * cout_blocks * cin_blocks * T;
     const long long blocks = (tasks + 3) / 4;
     if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-#define FBBEV_WGRAD(KS_)                                                                                             \
-    FBBEV_LAUNCH((k_conv3d_wgrad_ndhwc<KS_>), blocks, 256, 0, (fbbev_rt_stream)stream_, x, dy, dw, B, Di, Hi, Wi, Cin, Do, \
-                 Ho, Wo, Cout, stride, pad, (int)chunk, (int)n_chunks, cout_blocks, cin_blocks)
-    if (ksize == 3) FBBEV_WGRAD(3); else if (ksize == 2) FBBEV_WGRAD(2); else FBBEV_WGRAD(1);
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+#define FBBEV_WGRAD(KS_, DET_, OUT_)                                                                                   \
+    FBBEV_LAUNCH((k_conv3d_wgrad_ndhwc<KS_, DET_>), blocks, 256, 0, stream, x, dy, OUT_, B, Di, Hi, Wi, Cin, Do, Ho, Wo, \
+                 Cout, stride, pad, (int)chunk, (int)n_chunks, cout_blocks, cin_blocks)
+    if (part) {
+        if (ksize == 3) FBBEV_WGRAD(3, true, part); else if (ksize == 2) FBBEV_WGRAD(2, true, part); else FBBEV_WGRAD(1, true, part);
+        FBBEV_CHECK_LAUNCH();
+        const long long n = (long long)T * Cout * Cin;
+        long long g = (n + 255) / 256;
+        g = g > 4096 ? 4096 : g;
+        FBBEV_LAUNCH(k_sum_chunks_add, g, 256, 0, stream, (const float*)part, (int)n_chunks, n, dw);
+    } else {
+        if (ksize == 3) FBBEV_WGRAD(3, false, dw); else if (ksize == 2) FBBEV_WGRAD(2, false, dw); else FBBEV_WGRAD(1, false, dw);
+    }
 #undef FBBEV_WGRAD
     FBBEV_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int fbbev_conv3d_wgrad_ndhwc(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do,
+                                        int Ho, int Wo, int Cout, int ksize, int stride, int pad, float* dw,
+                                        fbbev_stream_t stream_) {
+    return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, nullptr, stream_);
+}
+extern "C" size_t fbbev_conv3d_wgrad_ws_bytes(int B, int Do, int Ho, int Wo, int Cin, int Cout, int ksize, int flags) {
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC) || B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0) return 0;
+    const long long nvox = (long long)B * Do * Ho * Wo, chunk = conv3d_wgrad_chunk(nvox);
+    return (size_t)((nvox + chunk - 1) / chunk) * ksize * ksize * ksize * Cout * Cin * sizeof(float);
+}
+extern "C" int fbbev_conv3d_wgrad_ndhwc_ex(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho,
+                                           int Wo, int Cout, int ksize, int stride, int pad, float* dw, int flags, void* ws,
+                                           size_t ws_bytes, fbbev_stream_t stream_) {
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC))
+        return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, nullptr, stream_);
+    if (B == 0) return 0;
+    if (!ws) return FBBEV_E_BADARG;
+    if (ws_bytes < fbbev_conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, ksize, flags)) return FBBEV_E_WORKSPACE;
+    return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, static_cast<float*>(ws), stream_);
 }
 
 extern "C" int fbbev_blend_levels_ndhwc(const float* level0, const float* const* coarse, const int* coarse_dims,

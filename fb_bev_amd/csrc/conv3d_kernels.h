@@ -232,7 +232,9 @@ k_blend_levels_ndhwc(const float* __restrict__ x0, fbbev_blend_level lv1, fbbev_
 // feed 16 MFMAs, four k-steps (16 voxels) are batched per loop iteration with the next batch in flight (ping-pong).
 // The voxel -> (b,d,h,w) decomposition is carried incrementally and branch-free (v advances by 4 per k-step).  Partial sums of the
 // chunks meet in dW through fp32 atomic adds (dW is small; it must be zero on entry).  Requires Cout % 4 == Cin % 4 == 0.
-template <int KS>
+// DET (deterministic mode, det_kernels.h): dw is the (n_chunks, T, Cout, Cin) partial buffer, every word STORED by its one lane;
+// k_sum_chunks_add then adds the chunks in order.
+template <int KS, bool DET = false>
 __global__ void __launch_bounds__(256)
 k_conv3d_wgrad_ndhwc(const float* __restrict__ x, const float* __restrict__ dy, float* __restrict__ dw, int B, int Di,
                      int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int stride, int pad, int chunk,
@@ -328,7 +330,7 @@ k_conv3d_wgrad_ndhwc(const float* __restrict__ x, const float* __restrict__ dy, 
         fbbev_sched_fence();
     }
     // D register r of a lane: row 4*kk + r -> cout 64mb + 4(4kk + r) + mt ; column i -> cin 64nb + 4i + nt
-    float* dwt = dw + (long long)tap * Cout * Cin;
+    float* dwt = dw + ((DET ? (long long)ch * T : 0ll) + tap) * Cout * Cin;
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
@@ -338,7 +340,9 @@ k_conv3d_wgrad_ndhwc(const float* __restrict__ x, const float* __restrict__ dy, 
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 const int ci = cb + nt;
-                if (ci < Cin) fbbev_atomic_add_f32(dwt + (long long)co * Cin + ci, acc[mt][nt][r]);
+                if (ci >= Cin) continue;
+                if constexpr (DET) dwt[(long long)co * Cin + ci] = acc[mt][nt][r];
+                else fbbev_atomic_add_f32(dwt + (long long)co * Cin + ci, acc[mt][nt][r]);
             }
         }
 }

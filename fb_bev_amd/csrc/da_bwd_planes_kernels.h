@@ -107,7 +107,9 @@ __host__ __device__ inline size_t fbbev_dbp_lds_bytes(int MH, int Ncam) {
 
 // planes (B*Ncam, MH, S, DH); offsets / attn / grad_offsets / grad_attn in the layouts of k_da_cross_attn_bwd_unit (head_minor bits
 // 0 / 1); grad_slots (B, Q, MH*DH); patch = 8 x 8 queries of a bev_w-wide grid (bev_w > 0) or 64 consecutive queries (bev_w == 0).
-template <int DH, int MH>
+// DET (deterministic mode, det_kernels.h): grad_pred_depth is the (Ncam, B, Q, ZA) buffer of the head-summed d / d depth weight,
+// stored (0 where the camera does not see the query) instead of added to the four taps by fp32 atomics.
+template <int DH, int MH, bool DET = false>
 __global__ void __launch_bounds__(64 * MH)
 k_da_bwd_unit_planes(const float* __restrict__ planes, const int64_t* __restrict__ spatial_shapes,
                      const int64_t* __restrict__ level_start, const float* __restrict__ pred_depth,
@@ -307,6 +309,15 @@ k_da_bwd_unit_planes(const float* __restrict__ planes, const int64_t* __restrict
         const int z = m;
         for (int cam = 0; cam < Ncam; ++cam) {
             const float* rec = my_qc + (size_t)cam * 64 * FBBEV_DBP_QC;
+            if constexpr (DET) {
+                float dsum = 0.f;
+                if (fbbev_lds_ld_f32(rec + 3 * ZA) != 0.f) {
+#pragma unroll
+                    for (int h = 0; h < MH; ++h) dsum += dd[((((size_t)h * Ncam) + cam) * 64 + lane) * ZA + z];
+                }
+                grad_pred_depth[(((long long)cam * B + b) * Q + ((long long)qy * gw + qx)) * ZA + z] = dsum;
+                continue;
+            }
             if (fbbev_lds_ld_f32(rec + 3 * ZA) == 0.f) continue;
             float dsum = 0.f;
 #pragma unroll

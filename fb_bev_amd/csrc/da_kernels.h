@@ -20,6 +20,7 @@
 // accumulated in index order; empty hit set -> count clamped to 1.
 #pragma once
 #include "rt.h"
+#include "fixed_point.h"
 #include "msda_kernels.h"
 
 #define FBBEV_DA_MAX_ZA 8
@@ -555,7 +556,9 @@ k_da_cross_attn_fwd_pipe(long long n_units, const float* __restrict__ value, con
 // loc = ref + offset / size and im = loc * size - 0.5, d im / d offset = 1.
 // Control flow is wave-uniform (cameras nobody in the wave hits are skipped by a ballot) because the group
 // reductions are cross-lane shuffles.
-template <int GW>
+// FIX (deterministic mode, det_kernels.h): grad_value is the fixed-point workspace (fixed_point.h; factors grad_slots, attn,
+// pred_depth) and grad_pred_depth the (Ncam, B, Q, M, Za) buffer of per-head d / d depth weight, stored (caller-zeroed) for the taps
+template <int GW, bool FIX = false>
 __global__ void __launch_bounds__(256)
 k_da_cross_attn_bwd(long long n_units, const float* __restrict__ value, const int64_t* __restrict__ spatial_shapes,
                     const int64_t* __restrict__ level_start, const float* __restrict__ pred_depth,
@@ -576,6 +579,15 @@ k_da_cross_attn_bwd(long long n_units, const float* __restrict__ value, const in
     const int q = (int)(bq % Q);
     const int b = (int)(bq / Q);
     const bool chan = active && slot < Dh;
+    double fsc = 0.0;
+    bool fok = false;
+    unsigned long long* facc = nullptr;
+    if constexpr (FIX) {
+        const int* hdr = reinterpret_cast<const int*>(grad_value);
+        fok = hdr[4] > 0;
+        fsc = __builtin_ldexp(1.0, hdr[3]);
+        facc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(grad_value) + FBBEV_FIX_HDR);
+    }
     int count = 0;
     for (int cam = 0; cam < Ncam; ++cam) {
         const long long base = (((long long)cam * B + b) * Q + q) * Za;
@@ -630,10 +642,10 @@ k_da_cross_attn_bwd(long long n_units, const float* __restrict__ value, const in
                     float* gp = grad_value + voff;
                     const float tgv = g * weight;
                     float v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f;
-                    if (s.o1 >= 0) { v1 = vp[s.o1]; fbbev_atomic_add_f32(gp + s.o1, s.w1 * tgv); }
-                    if (s.o2 >= 0) { v2 = vp[s.o2]; fbbev_atomic_add_f32(gp + s.o2, s.w2 * tgv); }
-                    if (s.o3 >= 0) { v3 = vp[s.o3]; fbbev_atomic_add_f32(gp + s.o3, s.w3 * tgv); }
-                    if (s.o4 >= 0) { v4 = vp[s.o4]; fbbev_atomic_add_f32(gp + s.o4, s.w4 * tgv); }
+                    if (s.o1 >= 0) { v1 = vp[s.o1]; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + s.o1), s.w1 * tgv, fsc); } else fbbev_atomic_add_f32(gp + s.o1, s.w1 * tgv); }
+                    if (s.o2 >= 0) { v2 = vp[s.o2]; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + s.o2), s.w2 * tgv, fsc); } else fbbev_atomic_add_f32(gp + s.o2, s.w2 * tgv); }
+                    if (s.o3 >= 0) { v3 = vp[s.o3]; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + s.o3), s.w3 * tgv, fsc); } else fbbev_atomic_add_f32(gp + s.o3, s.w3 * tgv); }
+                    if (s.o4 >= 0) { v4 = vp[s.o4]; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + s.o4), s.w4 * tgv, fsc); } else fbbev_atomic_add_f32(gp + s.o4, s.w4 * tgv); }
                     dot = g * (s.w1 * v1 + s.w2 * v2 + s.w3 * v3 + s.w4 * v4);
                     gy = g * (-s.hw * v1 - s.lw * v2 + s.hw * v3 + s.lw * v4);
                     gx = g * (-s.hh * v1 + s.hh * v2 - s.lh * v3 + s.lh * v4);
@@ -648,6 +660,11 @@ k_da_cross_attn_bwd(long long n_units, const float* __restrict__ value, const in
                     ddw[z] += a * dot;
                 }
             }
+        }
+        if constexpr (FIX) {
+            if (hit && slot == 0)
+                for (int z = 0; z < Za; ++z) grad_pred_depth[((((long long)cam * B + b) * Q + q) * M + m) * Za + z] = ddw[z];
+            continue;
         }
         if (hit && slot == 0) {
             for (int z = 0; z < Za; ++z) {       // dw[z] -> the four corners of the query's bin plane (fbbev_plane_sample)
@@ -722,7 +739,9 @@ __device__ __forceinline__ void fbbev_unit_sample_grad(const float* __restrict__
     }
 }
 
-template <int DH, bool QI>
+// DET (deterministic mode, det_kernels.h; needs the head reduction below: M a power of two <= 64): grad_pred_depth is the
+// (Ncam, B, Q, Za) buffer of the head-summed d / d depth weight (caller-zeroed), stored by head 0 instead of added to the taps
+template <int DH, bool QI, bool DET = false>
 __global__ void __launch_bounds__(256)
 k_da_cross_attn_bwd_unit(long long n_units, const float* __restrict__ value, const int64_t* __restrict__ spatial_shapes,
                          const int64_t* __restrict__ level_start, const float* __restrict__ pred_depth,
@@ -875,6 +894,10 @@ k_da_cross_attn_bwd_unit(long long n_units, const float* __restrict__ value, con
                 if (reduce_heads)
                     for (int o = 1; o < M; o <<= 1) dsum += __shfl_xor(dsum, o, 64);
                 if (reduce_heads && m != 0) continue;
+                if constexpr (DET) {
+                    grad_pred_depth[base + z] = dsum;
+                    continue;
+                }
                 const float h_im = ry[z] * H0 - 0.5f, w_im = rx[z] * W0 - 0.5f;
                 if (!(h_im > -1.f && w_im > -1.f && h_im < (float)H0 && w_im < (float)W0) || dsum == 0.f) continue;
                 const fbbev_bilinear s = fbbev_bilinear_setup(h_im, w_im, H0, W0, 1);

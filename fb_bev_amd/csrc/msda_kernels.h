@@ -16,6 +16,7 @@
 // through hardware fp32 atomics.
 #pragma once
 #include "rt.h"
+#include "fixed_point.h"
 
 struct fbbev_bilinear {
     int o1, o2, o3, o4;        // corner offsets (floats) relative to value_l + m*Dh + c; -1 = padded
@@ -256,7 +257,9 @@ __device__ __forceinline__ float fbbev_group_sum(float v) {
 }
 
 // SCATTER = false: the unit-owned gradients only (grad_value comes from k_msda_bwd_scatter, msda_bwd_kernels.h)
-template <int GW, bool SCATTER = true>
+// FIX (deterministic mode, det_kernels.h): grad_value is the fixed-point workspace (header + 64-bit words), each add is a fixed-point
+// integer add at the header's scale (factors: grad_out, attn)
+template <int GW, bool SCATTER = true, bool FIX = false>
 __global__ void __launch_bounds__(256)
 k_msda_bwd(long long n_units, const float* __restrict__ value,
            const int64_t* __restrict__ spatial_shapes, const int64_t* __restrict__ level_start,
@@ -271,6 +274,15 @@ k_msda_bwd(long long n_units, const float* __restrict__ value,
     const long long b = u / M / Q;
     const int row_stride = M * Dh;
     long long wp = u * L * P, lp = wp * 2;
+    double fsc = 0.0;
+    bool fok = false;                                               // state <= 0: nothing to add, or the convert pass poisons
+    unsigned long long* facc = nullptr;
+    if constexpr (FIX) {
+        const int* hdr = reinterpret_cast<const int*>(grad_value);
+        fok = hdr[4] > 0;
+        fsc = __builtin_ldexp(1.0, hdr[3]);
+        facc = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(grad_value) + FBBEV_FIX_HDR);
+    }
     for (int l = 0; l < L; ++l) {
         const int height = (int)spatial_shapes[2 * l], width = (int)spatial_shapes[2 * l + 1];
         const long long voff = (b * spatial_size + level_start[l]) * row_stride + m * Dh;
@@ -289,10 +301,10 @@ k_msda_bwd(long long n_units, const float* __restrict__ value,
                     float* gp = grad_value + voff + c;
                     (void)gp;
                     float ghw = 0.f, gww = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f;
-                    if (s.o1 >= 0) { v1 = vp[s.o1]; ghw -= s.hw * v1; gww -= s.hh * v1; if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o1, s.w1 * tgv); }
-                    if (s.o2 >= 0) { v2 = vp[s.o2]; ghw -= s.lw * v2; gww += s.hh * v2; if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o2, s.w2 * tgv); }
-                    if (s.o3 >= 0) { v3 = vp[s.o3]; ghw += s.hw * v3; gww -= s.lh * v3; if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o3, s.w3 * tgv); }
-                    if (s.o4 >= 0) { v4 = vp[s.o4]; ghw += s.lw * v4; gww += s.lh * v4; if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o4, s.w4 * tgv); }
+                    if (s.o1 >= 0) { v1 = vp[s.o1]; ghw -= s.hw * v1; gww -= s.hh * v1; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + c + s.o1), s.w1 * tgv, fsc); } else if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o1, s.w1 * tgv); }
+                    if (s.o2 >= 0) { v2 = vp[s.o2]; ghw -= s.lw * v2; gww += s.hh * v2; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + c + s.o2), s.w2 * tgv, fsc); } else if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o2, s.w2 * tgv); }
+                    if (s.o3 >= 0) { v3 = vp[s.o3]; ghw += s.hw * v3; gww -= s.lh * v3; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + c + s.o3), s.w3 * tgv, fsc); } else if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o3, s.w3 * tgv); }
+                    if (s.o4 >= 0) { v4 = vp[s.o4]; ghw += s.lw * v4; gww += s.lh * v4; if constexpr (FIX) { if (fok) fbbev_fix_add(facc + (voff + c + s.o4), s.w4 * tgv, fsc); } else if constexpr (SCATTER) fbbev_atomic_add_f32(gp + s.o4, s.w4 * tgv); }
                     const float val = s.w1 * v1 + s.w2 * v2 + s.w3 * v3 + s.w4 * v4;
                     g_w += top * val;
                     g_x += (float)width * gww * tgv;

@@ -27,6 +27,13 @@ typedef void* fbbev_stream_t; /* hipStream_t */
 #define FBBEV_E_UNSUPPORTED (-2)
 #define FBBEV_E_WORKSPACE (-3)
 
+/* flags word of the *_ex entry points.  FBBEV_FLAG_DETERMINISTIC: deterministic mode -- every gradient the call computes is
+ * bit-identical from run to run (no float atomics: fixed-point integer sums, fixed-order reductions or owner-computes).  Without
+ * the flag an *_ex entry launches exactly what its plain entry launches.  The Python layer sets it from
+ * fb_bev_amd.deterministic_enabled() (torch.use_deterministic_algorithms, torch.backends.cudnn.deterministic, or
+ * fb_bev_amd.set_deterministic), read on every call. */
+#define FBBEV_FLAG_DETERMINISTIC 0x1
+
 /* flags of fbbev_bev_pool_v2_dense_fwd (tuning knobs: none changes the result bits; OUT_BF16 / OUT_F16 select the
  * storage type of `out` -- the sums stay fp32 in-order fmaf chains and are rounded once at the store) */
 #define FBBEV_POOL_STORE_MASK 0x3   /* output store cache policy: 0 plain, 1 nontemporal; with bit 17 set: sc1 nt */
@@ -615,6 +622,64 @@ int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t* spatial_s
                                    int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
                                    float* grad_value, float* grad_pred_depth, float* grad_offsets, float* grad_attn,
                                    const int32_t* level_hw_host, void* ws, size_t ws_bytes, int bev_w, fbbev_stream_t stream);
+
+/* fbbev_da_cross_attn_bwd_planes / fbbev_da_cross_attn_bwd_ws_grid with a flags word.  With FBBEV_FLAG_DETERMINISTIC the unit
+ * kernels store the head-summed d loss / d depth weight of every (camera, sample, query, anchor) into det_ws instead of adding it to
+ * the four bilinear taps of grad_pred_depth by fp32 atomics, and fbbev_da_depth_taps_det adds the taps (grad_pred_depth is still
+ * accumulated into).  det_ws: fbbev_da_bwd_det_ws_bytes bytes, 16-byte aligned, contents ignored; level_hw_host is required.  In
+ * that mode M must be a power of two <= 64, and fbbev_da_cross_attn_bwd_ws_grid_ex returns FBBEV_E_UNSUPPORTED for a shape neither
+ * LDS-plane route takes (then fbbev_da_cross_attn_bwd_ex: the global kernel in fixed point).  Without the flag det_ws is not used. */
+size_t fbbev_da_bwd_det_ws_bytes(int B, int Ncam, int Q, int Za, int DC, int H0, int W0);
+int fbbev_da_cross_attn_bwd_planes_ex(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                      const float* pred_depth, const float* ref_cam, const uint8_t* mask, const float* qdepth,
+                                      const float* offsets, const float* attn, const float* grad_slots, int B, int Ncam, int S, int M,
+                                      int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep, int head_minor,
+                                      int head_stride, float* grad_value, float* grad_pred_depth, float* grad_offsets,
+                                      float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes, int bev_w, int flags,
+                                      void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream);
+int fbbev_da_cross_attn_bwd_ws_grid_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                       const float* pred_depth, const float* ref_cam, const uint8_t* mask, const float* qdepth,
+                                       const float* offsets, const float* attn, const float* grad_slots, int B, int Ncam, int S, int M,
+                                       int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep, int head_minor,
+                                       int head_stride, float* grad_value, float* grad_pred_depth, float* grad_offsets,
+                                       float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes, int bev_w, int flags,
+                                       void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream);
+/* The deterministic depth taps on their own: dsum (Ncam, B, Q, Za) holds d loss / d depth weight per (camera, sample, query,
+ * anchor); each is pushed to the four bilinear taps (ref_cam, H0 x W0) of the query's bin plane (qdepth, d0, dstep, DC) of
+ * grad_pred_depth (B, Ncam, DC, H0, W0), which is accumulated into.  The taps are summed as 64-bit fixed point at the scale
+ * 2^(61 - e - ceil(log2(Q * Za))), max |dsum| < 2^e, then converted and added: the bits do not depend on the order of the adds.
+ * A non-finite dsum sets every word of grad_pred_depth to NaN.  ws: fbbev_da_depth_taps_det_ws_bytes bytes, 8-byte aligned. */
+size_t fbbev_da_depth_taps_det_ws_bytes(int B, int Ncam, int DC, int H0, int W0);
+int fbbev_da_depth_taps_det(const float* dsum, const float* ref_cam, const float* qdepth, int B, int Ncam, int Q, int Za, int DC, int H0,
+                            int W0, float d0, float dstep, float* grad_pred_depth, void* ws, size_t ws_bytes, fbbev_stream_t stream);
+
+/* Deterministic forms of the two remaining float-atomic gradient sites (FBBEV_FLAG_DETERMINISTIC; without the flag the plain entry).
+ * fbbev_msda_bwd_ex: the value gradient as 64-bit fixed point in det_ws (fbbev_msda_bwd_det_ws_bytes, 16-byte aligned), at the scale
+ * 2^(61 - e_g - e_a - ceil(log2(num_query * num_point))), max |grad_output| < 2^e_g, max |attn_weight| < 2^e_a, then converted and
+ * ADDED to grad_value (the boundary's contract: accumulated into); grad_sampling_loc / grad_attn_weight as fbbev_msda_bwd.  A
+ * non-finite grad_output or attn_weight sets every word of grad_value to NaN.
+ * fbbev_conv3d_wgrad_ndhwc_ex: every voxel chunk's partial weight gradient STORED into ws (fbbev_conv3d_wgrad_ws_bytes), then the
+ * chunks added in order into dw. */
+/* fbbev_da_cross_attn_bwd with a flags word: with FBBEV_FLAG_DETERMINISTIC the global kernel's value gradient as 64-bit fixed
+ * point (scale from max |grad_slots| x max |attn| x max |pred_depth|, at most Q * P adds per word) and its depth taps through
+ * fbbev_da_depth_taps_det; both accumulated into as by the plain entry.  H0, W0: level 0's shape (host); det_ws of
+ * fbbev_da_cross_attn_bwd_det_ws_bytes (HS = head_stride or Dh), 16-byte aligned. */
+size_t fbbev_da_cross_attn_bwd_det_ws_bytes(int B, int Ncam, int S, int M, int HS, int Q, int Za, int DC, int H0, int W0);
+int fbbev_da_cross_attn_bwd_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                               const float* pred_depth, const float* ref_cam, const uint8_t* mask, const float* qdepth,
+                               const float* offsets, const float* attn, const float* grad_slots, int B, int Ncam, int S, int M, int Dh,
+                               int L, int Q, int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
+                               float* grad_value, float* grad_pred_depth, float* grad_offsets, float* grad_attn, int H0, int W0,
+                               int flags, void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream);
+size_t fbbev_msda_bwd_det_ws_bytes(int batch, int spatial_size, int num_heads, int channels);
+int fbbev_msda_bwd_ex(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_loc,
+                      const float* attn_weight, const float* grad_output, int batch, int spatial_size, int num_heads, int channels,
+                      int num_levels, int num_query, int num_point, float* grad_value, float* grad_sampling_loc,
+                      float* grad_attn_weight, int flags, void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream);
+size_t fbbev_conv3d_wgrad_ws_bytes(int B, int Do, int Ho, int Wo, int Cin, int Cout, int ksize, int flags);
+int fbbev_conv3d_wgrad_ndhwc_ex(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo,
+                                int Cout, int ksize, int stride, int pad, float* dw, int flags, void* ws, size_t ws_bytes,
+                                fbbev_stream_t stream);
 
 /* Training backward of the fused lift-splat:  replaces QuickCumsumCuda.backward (bev_pool.py:39-78 --
  * argsort of ranks_feat, mask-built intervals [2 host syncs], the permute().contiguous() of the gradient)
