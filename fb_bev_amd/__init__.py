@@ -30,3 +30,11 @@ def deterministic_enabled():
         return _deterministic_override
     import torch
     return bool(torch.are_deterministic_algorithms_enabled() or torch.backends.cudnn.deterministic)
+
+
+def set_rows_linear_mode(name):
+    """Route of the backward projection's row-wise linear layers: 'x3' (split-operand bf16 MFMA, the default), 'f32' (vendor fp32
+    GEMM) or 'f32_mfma' (exact fp32 on the FP32 MFMA, the arithmetic contract of fbbev_rows_linear_f32 in include/fbbev.h).
+    Returns the previous mode; `rows_linear.set_mode` is the same switch.  FBBEV_ROWS_LINEAR only sets the initial mode."""
+    from . import rows_linear
+    return rows_linear.set_mode(name)

@@ -67,6 +67,12 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_void_p]),
     'fbbev_rows_linear_x3_ln': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                         c_float, c_void_p, c_int64, c_void_p]),
+    'fbbev_rows_linear_f32': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    'fbbev_rows_linear_f32_add': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                          c_void_p, c_int64, c_void_p]),
+    'fbbev_rows_linear_f32_ln': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                         c_float, c_void_p, c_int64, c_void_p]),
+    'fbbev_rows_linear_f32_k_order': (c_int, [c_int, c_void_p]),
     'fbbev_rows_ffn_x3': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
                                   c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     'fbbev_rows_tail_ffn_x3': (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
@@ -1093,6 +1099,65 @@ def rows_linear_x3_ln(x, fragments, bias, out_features, residual, ln_weight, ln_
             residual.stride(0) if residual is not None else 0, _dev(ln_weight, F32, 'ln_weight'), _dev(ln_bias, F32, 'ln_bias'),
             float(eps), _dev(out, F32, 'out', contiguous=False), out.stride(0), _stream()), 'fbbev_rows_linear_x3_ln')
     return out
+
+
+def rows_linear_f32(x, weight, bias, relu=False, out=None, addend=None):
+    """x (R, I) f32 rows (row stride >= I, unit column stride) -> out (R, O) = x W^T + bias (+ ReLU) in exact fp32 on the FP32 MFMA
+    (fbbev_rows_linear_f32: one fmaf chain per element, order rows_linear_f32_k_order).  weight (O, I) contiguous f32 -- the
+    nn.Linear parameter.  addend (P, I): the rows are x[r] + addend[r % P] (R % P == 0)."""
+    R, I = x.shape
+    O = weight.shape[0]
+    if x.stride(1) != 1 or weight.dim() != 2 or weight.shape[1] != I:
+        raise FbbevError('rows_linear_f32: rows must have unit column stride; weight must be (out_features, in_features)')
+    if out is None:
+        out = torch.empty((R, O), dtype=F32, device=x.device)
+    if out.shape != (R, O) or out.stride(1) != 1:
+        raise FbbevError('rows_linear_f32: out must be (rows, out_features) with unit column stride')
+    b = _dev(bias, F32, 'bias') if bias is not None else None
+    with _on(x):
+        if addend is None:
+            _check(lib().fbbev_rows_linear_f32(_dev(x, F32, 'x', contiguous=False), x.stride(0), _dev(weight, F32, 'weight'), b, R, I,
+                                               O, 1 if relu else 0, _dev(out, F32, 'out', contiguous=False), out.stride(0),
+                                               _stream()), 'fbbev_rows_linear_f32')
+        else:
+            if addend.dim() != 2 or addend.shape[1] != I or addend.stride(1) != 1 or R % addend.shape[0] != 0:
+                raise FbbevError('rows_linear_f32: addend must be (P, in_features) rows with rows % P == 0')
+            _check(lib().fbbev_rows_linear_f32_add(_dev(x, F32, 'x', contiguous=False), x.stride(0),
+                                                   _dev(addend, F32, 'addend', contiguous=False), addend.stride(0), addend.shape[0],
+                                                   _dev(weight, F32, 'weight'), b, R, I, O, 1 if relu else 0,
+                                                   _dev(out, F32, 'out', contiguous=False), out.stride(0), _stream()),
+                   'fbbev_rows_linear_f32_add')
+    return out
+
+
+def rows_linear_f32_ln(x, weight, bias, residual, ln_weight, ln_bias, eps, out=None):
+    """LayerNorm(x W^T + bias [+ residual]) in one kernel, exact-fp32 product (fbbev_rows_linear_f32_ln); x (R, I), weight (O, I),
+    residual (R, O) rows, out (R, O)."""
+    R, I = x.shape
+    O = weight.shape[0]
+    if (x.stride(1) != 1 or weight.dim() != 2 or weight.shape[1] != I or
+            (residual is not None and (tuple(residual.shape) != (R, O) or residual.stride(1) != 1))):
+        raise FbbevError('rows_linear_f32_ln: rows must have unit column stride; weight (out_features, in_features); residual (rows, out_features)')
+    if out is None:
+        out = torch.empty((R, O), dtype=F32, device=x.device)
+    if tuple(out.shape) != (R, O) or out.stride(1) != 1:
+        raise FbbevError('rows_linear_f32_ln: out must be (rows, out_features) with unit column stride')
+    b = _dev(bias, F32, 'bias') if bias is not None else None
+    with _on(x):
+        _check(lib().fbbev_rows_linear_f32_ln(
+            _dev(x, F32, 'x', contiguous=False), x.stride(0), _dev(weight, F32, 'weight'), b, R, I, O,
+            _dev(residual, F32, 'residual', contiguous=False) if residual is not None else None,
+            residual.stride(0) if residual is not None else 0, _dev(ln_weight, F32, 'ln_weight'), _dev(ln_bias, F32, 'ln_bias'),
+            float(eps), _dev(out, F32, 'out', contiguous=False), out.stride(0), _stream()), 'fbbev_rows_linear_f32_ln')
+    return out
+
+
+def rows_linear_f32_k_order(in_features):
+    """the input channels in the order the fmaf chain of rows_linear_f32 consumes them (host function): a list of in_features ints"""
+    import ctypes
+    buf = (ctypes.c_int * max(1, int(in_features)))()
+    _check(lib().fbbev_rows_linear_f32_k_order(int(in_features), ctypes.cast(buf, ctypes.c_void_p)), 'fbbev_rows_linear_f32_k_order')
+    return list(buf[:int(in_features)])
 
 
 def rows_ffn_x3(x, w1_fragments, b1, w2_fragments, b2, hidden, out_features, residual=None, ln_weight=None, ln_bias=None, eps=1e-5):

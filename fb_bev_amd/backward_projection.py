@@ -184,7 +184,7 @@ class FFN(nn.Module):
             return None
         l1, l2 = real[0][0], real[1]
         I, H, O = l1.in_features, l1.out_features, l2.out_features
-        if not (x3_ok(x, I, H) and I <= 96 and H % 64 == 0 and O <= 80 and O % 4 == 0 and l1.bias is not None and l2.bias is not None
+        if not (_RL.X3 and x3_ok(x, I, H) and I <= 96 and H % 64 == 0 and O <= 80 and O % 4 == 0 and l1.bias is not None and l2.bias is not None
                 and x.is_contiguous() and x.data_ptr() % 16 == 0):     # a misaligned view takes the two-GEMM fallback
             return None
         res = None
@@ -218,6 +218,8 @@ class FFN(nn.Module):
         block's tail -- Linear(E, H) + ReLU, Linear(H, E), add_identity, H % 64 == 0, E % 16 == 0, E <= 80 -- else None."""
         if self.training and self._has_live_dropout():
             # ADVICE r5: train() + no_grad() with ffn_drop > 0 must keep the Dropout layers (FFN.forward keeps `self.layers` then)
+            return None
+        if not _RL.X3:         # x3 fragments for an x3 kernel: not on the f32 / f32_mfma routes
             return None
         real = [l for l in self.layers if not isinstance(l, nn.Dropout)]
         if not (FUSE_TAIL_FFN and FUSE_FFN and self.add_identity and len(real) == 2 and isinstance(real[0], nn.Sequential)
@@ -824,7 +826,7 @@ class DA_SpatialCrossAttention(nn.Module):
         tail_ok = (_norm is not None and _defer_residual and self.layer_scale is None and not torch.is_grad_enabled()
                    and not (self.training and self.dropout.p > 0))
         tail = None
-        if (tail_ok and FUSE_ATTN_TAIL_DA and fn == self._slots_fused and self.embed_dims % 16 == 0
+        if (tail_ok and FUSE_ATTN_TAIL_DA and _RL.X3 and fn == self._slots_fused and self.embed_dims % 16 == 0
                 and _RL.ln_fusable(_norm, inp_residual.contiguous(), query, self.embed_dims)):
             # output_proj + residual + LayerNorm inside the sampler's (8-head) workgroups: fbbev_da_cross_attn_fused_ln (opt-in)
             if not hasattr(self.output_proj, '_x3'):

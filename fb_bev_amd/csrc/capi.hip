@@ -18,6 +18,7 @@
 #include "history_conv_x3_kernels.h"
 #include "history_fused_x3_kernels.h"
 #include "rows_linear_kernels.h"
+#include "rows_linear_f32_kernels.h"
 #include "da_fused_kernels.h"
 #include "da_bwd_planes_kernels.h"
 #include "msda_bwd_kernels.h"
@@ -3430,6 +3431,91 @@ extern "C" int fbbev_rows_linear_x3_ln(const float* x, long long x_row_stride, c
     if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
     return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
                                stream_, 0, 0, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
+}
+
+// ------------------------------------------------------------------------------ row-wise linear layers, exact fp32 (FP32 MFMA)
+// fbbev_rows_linear_f32*: every output element is one fp32 fmaf chain in the order of fbbev_rows_linear_f32_k_order (the arithmetic
+// contract in include/fbbev.h).  The weight is the nn.Linear parameter itself (row-major (out_features, in_features) fp32).
+static int rows_linear_f32_impl(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
+                                int in_features, int out_features, int relu, float* out, long long out_row_stride,
+                                const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
+                                const float* res = nullptr, long long ld_res = 0, const float* ln_w = nullptr,
+                                const float* ln_b = nullptr, float ln_eps = 0.f) {
+    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
+    if (rows == 0) return 0;
+    if (!x || !weight || !out) return FBBEV_E_BADARG;
+    if (x_row_stride == 0) x_row_stride = in_features;
+    if (out_row_stride == 0) out_row_stride = out_features;
+    if (x_row_stride < in_features || out_row_stride < out_features) return FBBEV_E_BADARG;
+    if (in_features % 8 != 0 || out_features % 4 != 0 || x_row_stride % 4 != 0 || out_row_stride % 4 != 0 || !aligned16(x) ||
+        !aligned16(out) || !aligned16(weight) || (bias && !aligned16(bias))) return FBBEV_E_UNSUPPORTED;
+    const int n_oc = (out_features + 127) / 128, n_kc = (in_features + 127) / 128;
+    const long long tiles = (rows + 127) / 128;
+    if (tiles * n_oc >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (ln_w && n_oc != 1) return FBBEV_E_UNSUPPORTED;
+    const int nmt = out_features >= 128 ? 8 : (out_features + 15) / 16;
+    const size_t lds = (size_t)nmt * FBBEV_RLF_TILE_FLOATS * sizeof(float);
+    int e = ln_w ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_f32<true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_f32<false>, lds);
+    if (e) return e;
+    // consecutive row tiles per workgroup (the weight staged once) as long as ~4 workgroups per CU remain; the chain of an element
+    // does not depend on it
+    long long RT = n_kc == 1 ? tiles * n_oc / 1024 : 1;
+    RT = RT < 1 ? 1 : (RT > 8 ? 8 : RT);
+#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: lets a small case walk several row tiles per workgroup
+    { const char* e_rt = getenv("FBBEV_ROWS_LINEAR_RT"); if (e_rt && n_kc == 1 && atoi(e_rt) >= 1 && atoi(e_rt) <= 8) RT = atoi(e_rt); }
+#endif
+    const long long groups = (tiles + RT - 1) / RT;
+    if (ln_w)
+        FBBEV_LAUNCH((k_rows_linear_f32<true>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, out,
+                     out_row_stride, rows, in_features, out_features, relu, n_kc, n_oc, (int)RT, addend, addend_row_stride,
+                     addend_period, res, ld_res, ln_w, ln_b, ln_eps);
+    else
+        FBBEV_LAUNCH((k_rows_linear_f32<false>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, out,
+                     out_row_stride, rows, in_features, out_features, relu, n_kc, n_oc, (int)RT, addend, addend_row_stride,
+                     addend_period, res, ld_res, ln_w, ln_b, ln_eps);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_rows_linear_f32(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
+                                     int in_features, int out_features, int relu, float* out, long long out_row_stride,
+                                     fbbev_stream_t stream_) {
+    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, relu, out, out_row_stride, nullptr,
+                                0, 1, stream_);
+}
+
+extern "C" int fbbev_rows_linear_f32_add(const float* x, long long x_row_stride, const float* addend, long long addend_row_stride,
+                                         long long addend_period, const float* weight, const float* bias, long long rows,
+                                         int in_features, int out_features, int relu, float* out, long long out_row_stride,
+                                         fbbev_stream_t stream_) {
+    if (!addend || addend_period <= 0) return FBBEV_E_BADARG;
+    if (addend_row_stride == 0) addend_row_stride = in_features;
+    if (addend_row_stride < in_features) return FBBEV_E_BADARG;
+    if (addend_row_stride % 4 != 0 || !aligned16(addend)) return FBBEV_E_UNSUPPORTED;
+    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
+                                addend_row_stride, addend_period, stream_);
+}
+
+extern "C" int fbbev_rows_linear_f32_ln(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
+                                        int in_features, int out_features, const float* residual, long long residual_row_stride,
+                                        const float* ln_weight, const float* ln_bias, float ln_eps, float* out,
+                                        long long out_row_stride, fbbev_stream_t stream_) {
+    if (!ln_weight || !ln_bias || out_features <= 0) return FBBEV_E_BADARG;
+    if (out_features > 128) return FBBEV_E_UNSUPPORTED;
+    if (residual) {
+        if (residual_row_stride == 0) residual_row_stride = out_features;
+        if (residual_row_stride < out_features) return FBBEV_E_BADARG;
+        if (residual_row_stride % 4 != 0 || !aligned16(residual)) return FBBEV_E_UNSUPPORTED;
+    }
+    if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
+    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
+                                stream_, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
+}
+
+extern "C" int fbbev_rows_linear_f32_k_order(int in_features, int* order) {
+    if (in_features <= 0 || !order) return FBBEV_E_BADARG;
+    fbbev_rows_linear_f32_order(in_features, order);
+    return 0;
 }
 
 // y = x W^T + b written as HEAD PLANES: rows = (B*Ncam) x S tokens, out_features = M * head_dim (module order (head, channel));

@@ -19,7 +19,13 @@ from . import _capi
 MIN_ROWS = 16384            # below this autograd's plain GEMM is as good
 # Inference: the split-operand bf16-MFMA kernel (fbbev_rows_linear_x3: ~1e-5 relative to fp32, bias / ReLU in its epilogue)
 # instead of the vendor fp32 GEMM.  FBBEV_ROWS_LINEAR=f32 (or X3 = False) keeps the vendor GEMM.
-X3 = os.environ.get('FBBEV_ROWS_LINEAR', 'x3') != 'f32'
+# FBBEV_ROWS_LINEAR=f32_mfma: the exact-fp32 kernel on the FP32 MFMA (fbbev_rows_linear_f32: one fmaf chain per output element in a
+# documented order, bias / ReLU / addend / LayerNorm in its epilogue) takes every layer the split-operand kernel would have taken.
+# X3 keeps its meaning -- "the split-operand kernels and the one-kernel attention routes are on" -- and is False on that route.
+MODES = ('x3', 'f32', 'f32_mfma')
+_env_mode = os.environ.get('FBBEV_ROWS_LINEAR', 'x3')
+X3 = _env_mode not in ('f32', 'f32_mfma')
+F32_MFMA = _env_mode == 'f32_mfma'
 X3_MIN_ROWS = 2048
 # fold `query + query_pos` into the projections' row loads (fbbev_rows_linear_x3_add); FBBEV_ROWS_LINEAR_FOLD=0: a pass of its own
 FOLD_ADDEND = os.environ.get('FBBEV_ROWS_LINEAR_FOLD', '1') != '0'
@@ -57,6 +63,29 @@ def bias_grad(gy):
     return gb
 
 
+def f32_mfma_on():
+    """the exact-fp32 MFMA route is in force.  X3 wins: a caller that sets `X3 = True` by hand (the flag bench.py flips for its A/B)
+    gets the split-operand route with its fragments whatever F32_MFMA holds, so no fourth state exists."""
+    return F32_MFMA and not X3
+
+
+def mode():
+    """the row-wise-layer route in force: 'x3' | 'f32' | 'f32_mfma' (the module flags X3 / F32_MFMA are the state)"""
+    return 'x3' if X3 else ('f32_mfma' if F32_MFMA else 'f32')
+
+
+def set_mode(name):
+    """Select the route of the row-wise linear layers at run time ('x3': split-operand bf16 MFMA, the default; 'f32': the vendor
+    fp32 GEMM; 'f32_mfma': the exact-fp32 MFMA kernel); returns the previous mode.  FBBEV_ROWS_LINEAR only sets the initial one.
+    Weight caches (X3Weights) carry the mode in their key and rebuild on the next call."""
+    global X3, F32_MFMA
+    if name not in MODES:
+        raise ValueError(f'rows_linear.set_mode: unknown mode {name!r} (one of {MODES})')
+    prev = mode()
+    X3, F32_MFMA = name == 'x3', name == 'f32_mfma'
+    return prev
+
+
 class _RowsLinear(torch.autograd.Function):
     """x (R, I) 2-D -> (R, O).  2-D on purpose: F.linear of a 3-D tensor returns a VIEW of its GEMM result, and autograd refuses
     in-place ops (the FFN's ReLU(inplace=True)) on a view created inside a custom Function; `linear_rows` reshapes outside."""
@@ -87,14 +116,17 @@ class X3Weights:
     """Split MFMA fragments of a weight matrix, rebuilt when the SOURCE tensors change (data_ptr + _version, as the other
     folded-weight caches of the package).  `transform(w, b) -> (w', b')` derives the matrix actually applied (row permutation,
     head padding); it runs under no_grad, once per version.  One instance per call site, owned by the module (never keyed on a
-    temporary: a freed temporary's address can come back with version 0)."""
+    temporary: a freed temporary's address can come back with version 0).  On the f32_mfma route the kernel reads the fp32 matrix
+    itself: only the contiguous weight and the aligned bias copy are cached, no fragments are built (`frag` is None); the route is
+    part of the key, so a mode change rebuilds."""
 
     def __init__(self):
         self.key = None
         self.w = self.b = self.frag = None
 
     def get(self, w_src, b_src, transform=None):
-        key = (w_src.data_ptr(), w_src._version, None if b_src is None else (b_src.data_ptr(), b_src._version), str(w_src.device))
+        key = (w_src.data_ptr(), w_src._version, None if b_src is None else (b_src.data_ptr(), b_src._version), str(w_src.device),
+               f32_mfma_on())
         if key != self.key:
             with torch.no_grad():
                 w, b = (w_src, b_src) if transform is None else transform(w_src, b_src)
@@ -102,14 +134,17 @@ class X3Weights:
                 self.w, self.b = w, None if b is None else b.detach().float().contiguous()
                 if self.b is not None and self.b.data_ptr() % 16 != 0:      # a view into a flat parameter buffer: the kernels read the
                     self.b = self.b.clone()                                  # bias in 16-byte pieces (round 5), a private copy is aligned
-                self.frag = _capi.rows_linear_x3_fragments(w)
+                if f32_mfma_on() and self.w.data_ptr() % 16 != 0:
+                    self.w = self.w.clone()
+                self.frag = None if f32_mfma_on() else _capi.rows_linear_x3_fragments(w)
             self.key = key
         return self
 
 
 def x3_ok(x, in_features, out_features):
-    """the split-operand kernel applies: inference on a GPU, fp32 rows with unit column stride, shapes it takes"""
-    return (X3 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and in_features % 8 == 0 and
+    """the split-operand kernel (on the f32_mfma route: the exact-fp32 kernel, which takes the same shapes) applies: inference on a
+    GPU, fp32 rows with unit column stride, shapes it takes"""
+    return ((X3 or F32_MFMA) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and in_features % 8 == 0 and
             out_features % 4 == 0 and x.shape[-1] == in_features and x.numel() // max(1, in_features) >= X3_MIN_ROWS)
 
 
@@ -147,17 +182,23 @@ def ln_fusable(norm, residual, x, out_features):
 
 def linear_x3(x, cache, relu=False, out=None, addend=None, ln=None):
     """x (..., I) [+ addend] -> (..., O) through fbbev_rows_linear_x3 with the fragments of `cache` (an X3Weights after .get()).
-    ln = (residual or None, LayerNorm module): LayerNorm(x W^T + b + residual) in the same kernel (fbbev_rows_linear_x3_ln)."""
+    ln = (residual or None, LayerNorm module): LayerNorm(x W^T + b + residual) in the same kernel (fbbev_rows_linear_x3_ln).
+    A cache built on the f32_mfma route (no fragments) goes through fbbev_rows_linear_f32 / _add / _ln instead."""
     I = x.shape[-1]
     O = cache.w.shape[0]
+    f32 = cache.frag is None
     if ln is not None:
         assert not relu and out is None and addend is None
         res, norm = ln
         x2 = x.reshape(-1, I)
         if x2.stride(1) != 1 or x2.stride(0) % 4 != 0 or x2.data_ptr() % 16 != 0:
             x2 = x2.contiguous()
-        y = _capi.rows_linear_x3_ln(x2, cache.frag, cache.b, O, None if res is None else res.reshape(-1, O), norm.weight, norm.bias,
-                                    norm.eps)
+        if f32:
+            y = _capi.rows_linear_f32_ln(x2, cache.w, cache.b, None if res is None else res.reshape(-1, O), norm.weight, norm.bias,
+                                         norm.eps)
+        else:
+            y = _capi.rows_linear_x3_ln(x2, cache.frag, cache.b, O, None if res is None else res.reshape(-1, O), norm.weight,
+                                        norm.bias, norm.eps)
         return y.view(*x.shape[:-1], O)
     a = None
     if addend is not None:
@@ -167,7 +208,10 @@ def linear_x3(x, cache, relu=False, out=None, addend=None, ln=None):
     x2 = x.reshape(-1, I)
     if x2.stride(1) != 1 or x2.stride(0) % 4 != 0 or x2.data_ptr() % 16 != 0:
         x2 = x2.contiguous()
-    y = _capi.rows_linear_x3(x2, cache.frag, cache.b, O, relu=relu, out=out, addend=a)
+    if f32:
+        y = _capi.rows_linear_f32(x2, cache.w, cache.b, relu=relu, out=out, addend=a)
+    else:
+        y = _capi.rows_linear_x3(x2, cache.frag, cache.b, O, relu=relu, out=out, addend=a)
     return y if out is not None else y.view(*x.shape[:-1], O)
 
 

@@ -827,6 +827,40 @@ int fbbev_rows_linear_x3_ln(const float* x, long long x_row_stride, const void* 
                             int in_features, int out_features, const float* residual, long long residual_row_stride,
                             const float* ln_weight, const float* ln_bias, float ln_eps, float* out, long long out_row_stride,
                             fbbev_stream_t stream);
+/* The same layers in EXACT fp32 on the FP32 matrix instruction (v_mfma_f32_16x16x4_f32) -- the arithmetic of the reference's fp32
+ * nn.Linear under @force_fp32 (spatial_cross_attention_depth.py:432-436,464; the F.linear calls of :494-500, :533-540 and the mmcv
+ * FFN), with a summation order this header defines instead of a vendor library's kernel selection.  `weight` is the nn.Linear
+ * parameter itself: row-major (out_features, in_features) fp32, 16-byte aligned; no prepared fragments.  Strides, shapes and error
+ * codes as fbbev_rows_linear_x3 (in_features % 8 == 0, out_features % 4 == 0, strides % 4 == 0, 16-byte aligned pointers, else
+ * FBBEV_E_UNSUPPORTED; FBBEV_E_BADARG for null x / weight / out or negative sizes; rows == 0: 0 and no launch).  Inference only.
+ *
+ * Arithmetic contract, for every output element (r, o):
+ *   1. xr[k] = x[r, k], or x[r, k] + addend[r % addend_period, k] as one fp32 add (fbbev_rows_linear_f32_add);
+ *   2. acc = +0; for t = 0 .. in_features-1: acc = fmaf(W[o, ord[t]], xr[ord[t]], acc) -- one chain over all of K, no split-K, no
+ *      partial sums.  ord = fbbev_rows_linear_f32_k_order(in_features): a permutation of 0 .. in_features-1 that depends on
+ *      in_features only (not on the row, the output, rows, the launch geometry, the entry or any environment knob);
+ *   3. + bias[o] (one fp32 add, if bias), + residual[r, o] (one fp32 add, _ln only, if residual), ReLU if asked;
+ *   4. _ln: the LayerNorm of fbbev_rows_linear_x3_ln (two-pass mean and biased variance, eps inside the root); its reductions run
+ *      over lanes and their order is not part of the contract.
+ * Steps 1-3 are bit-reproducible on a host with fmaf. */
+int fbbev_rows_linear_f32(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
+                          int in_features, int out_features, int relu, float* out, long long out_row_stride, fbbev_stream_t stream);
+/* x[r, :] + addend[r % addend_period, :] as the row: the `query = query + query_pos` pass (spatial_cross_attention_depth.py:122-123,
+ * mmcv MultiScaleDeformableAttention.forward) folded into the projection, as fbbev_rows_linear_x3_add. */
+int fbbev_rows_linear_f32_add(const float* x, long long x_row_stride, const float* addend, long long addend_row_stride,
+                              long long addend_period, const float* weight, const float* bias, long long rows, int in_features,
+                              int out_features, int relu, float* out, long long out_row_stride, fbbev_stream_t stream);
+/* out = LayerNorm(x W^T + b [+ residual]): the `output_proj -> + residual -> norm` tail of the encoder layer's attention blocks and
+ * the second layer of its FFN (bevformer_encoder.py:250-377), as fbbev_rows_linear_x3_ln.  out_features <= 128.  residual == out is
+ * allowed (an element is read, then written, by one thread); x must not overlap out. */
+int fbbev_rows_linear_f32_ln(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
+                             int in_features, int out_features, const float* residual, long long residual_row_stride,
+                             const float* ln_weight, const float* ln_bias, float ln_eps, float* out, long long out_row_stride,
+                             fbbev_stream_t stream);
+/* order[t] = the input channel consumed at step t of the fmaf chain of fbbev_rows_linear_f32*; a permutation of
+ * 0 .. in_features-1 that depends on in_features only.  Host function, no GPU work.  FBBEV_E_BADARG for in_features <= 0 or a
+ * null pointer. */
+int fbbev_rows_linear_f32_k_order(int in_features, int* order);
 /* The FFN pair of the encoder layer in ONE kernel: out = [LayerNorm](W2 relu(W1 x + b1) + b2 [+ residual]) -- mmcv FFN as the encoder
  * layer configures it (Linear + ReLU, Linear, add_identity; bevformer_encoder.py:250-377) and, with ln_weight, the layer's following
  * LayerNorm.  The hidden rows never leave the CU (as two launches they are written and re-read: 205 MB each way at 160 000 rows).
