@@ -241,7 +241,7 @@ static rank_ws_layout rank_layout(long long n) {
     L.v1 = sort_variant_for((n + 1) / 2);
     L.vi = iv_variant_for((n + 1) / 2);
     // tuning / test knob: FBBEV_RANK_SHAPE="v0,v1,vi" forces the chunk variants (results do not depend on them)
-    if (const char* env = getenv("FBBEV_RANK_SHAPE")) {
+    if (const char* env = fbbev_env_str("FBBEV_RANK_SHAPE")) {
         int a = -1, b = -1, c = -1;
         if (sscanf(env, "%d,%d,%d", &a, &b, &c) == 3 && a >= 0 && a < 7 && b >= 0 && b < 7 && c >= 0 && c < 3) {
             L.v0 = a; L.v1 = b; L.vi = c;
@@ -285,12 +285,7 @@ extern "C" size_t fbbev_rank_workspace_bytes(int64_t n_points) {
     return rank_layout(n_points).total;
 }
 
-static int rank_seg_read_env() { const char* e = getenv("FBBEV_RANK_SEG"); return e ? atoi(e) : -1; }
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: the tests switch modes inside one process
-static int rank_seg_mode() { return rank_seg_read_env(); }
-#else
-static int rank_seg_mode() { static const int m = rank_seg_read_env(); return m; }      // read once per process
-#endif
+static int rank_seg_mode() { FBBEV_KNOB_ONCE(int, m, fbbev_env_int("FBBEV_RANK_SEG", -1)); return m; }
 
 static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const float* frustum, int B, int N, int D,
                            int H, int W,
@@ -365,7 +360,7 @@ static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const 
         FBBEV_CHECK_LAUNCH();
         const unsigned int* kin = keys_a;
         const unsigned int* vin = nullptr;
-        static const int pairs = [] { const char* e = getenv("FBBEV_RANK_PAIRS"); return e ? atoi(e) : 1; }();   // A/B knob, read once
+        static const int pairs = fbbev_env_int("FBBEV_RANK_PAIRS", 1);   // A/B knob, read once
         for (int p = 0; p < passes; ++p) {
             const bool to_out = p == passes - 1;
             // the intermediate (pass 0 -> pass 1) lives in keys_t | vals_t, which are adjacent: as ONE array of (key, value) pairs
@@ -377,7 +372,7 @@ static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const 
                              (pm & 1) ? 2 : 1);
                 FBBEV_CHECK_LAUNCH();
             }
-            static const int swz = [] { const char* e = getenv("FBBEV_RANK_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();   // A/B knob, read once
+            static const int swz = fbbev_env_int("FBBEV_RANK_XCD_SWIZZLE", 1);   // A/B knob, read once
             // XCD-contiguous chunk order when every XCD then owns whole samples' worth of chunks (B >= 8): measured 0.174 -> 0.156 ms
             // per build at BL2 B = 16, 0.192 -> 0.184 at the shipped grid B = 16; with few samples the round-robin order is faster
             // (BL2 B = 4: 0.123 vs 0.129) -- profiles/r04_time_rank_swizzle.jsonl
@@ -407,7 +402,7 @@ static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const 
                 FBBEV_SORT_DISPATCH(k_sort_hist, v, false, wgs, stream, kin, (const int*)counts, p * rb, rb, skip, matrix);
                 FBBEV_CHECK_LAUNCH();
             }
-            static const int swz = [] { const char* e = getenv("FBBEV_RANK_XCD_SWIZZLE"); return e ? atoi(e) : 1; }();   // A/B knob, read once
+            static const int swz = fbbev_env_int("FBBEV_RANK_XCD_SWIZZLE", 1);   // A/B knob, read once
             // pass 0 only: later passes size their grid for n but run on the P kept pairs -- a contiguous split would idle XCDs
             const bool sw = swz == 2 && p == 0;       // off by default: measured slower for the global sort (BL1 B = 1: 0.151 -> 0.156 ms)
             FBBEV_SORT_DISPATCH(k_sort_scatter, v, true, sw ? (wgs + 7) / 8 * 8 : wgs, stream, kin, vin, n, (const int*)matrix, p, rb, skip,
@@ -625,17 +620,13 @@ static int launch_dense2(const dense2_args& a) {
     if (SPLIT > 0) lds += ((size_t)TV + 4) * sizeof(int) + (size_t)FBBEV_POOL_SPLIT_GROUPS * (a.C / a.csplit) * sizeof(float);   // long-interval list + partial sums
     if (T16)                                   // 16-bit tile [CC][TV + 8] instead of fp32 [CC][TV + 4]
         lds = (size_t)(a.C / a.csplit) * (TV + 8) * 2 + ((size_t)3 * TV + 2 * FBBEV_NP_STAGE) * sizeof(int);
-    if (lds > 64 * 1024) {  // > 64 KiB of dynamic LDS must be opted into (160 KiB per CU on gfx950)
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16, 0, SPLIT, GU>, lds);
-        if (e) return e;
-    }
     long long grid = a.n_blocks;
     if (a.swizzle) {  // round up to whole groups of 8 chunks
         const long long g = 8ll << (a.swizzle - 1);
         grid = (a.n_blocks + g - 1) / g * g;
     }
-    FBBEV_LAUNCH((k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16, 0, SPLIT, GU>), grid, NT, lds, a.stream, a.C, a.Z, a.yx, a.tpp,
-                 a.csplit, (int)a.n_blocks, a.swizzle, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out);
+    FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16, 0, SPLIT, GU>), grid, NT, lds, a.stream, a.C, a.Z, a.yx, a.tpp,
+                         a.csplit, (int)a.n_blocks, a.swizzle, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out);
     return fbbev_rt_last_error();
 }
 
@@ -798,11 +789,7 @@ static int pool_dense_fwd_impl(const float* depth, const float* feat,
     a.gather8 = (flags & FBBEV_POOL_GATHER8) != 0 && !a.split;
     if ((flags & FBBEV_POOL_PIPE) && ot == 0 && !a.split && nt == 256 && st >= 2 && (TV == 64 || TV == 128 || TV == 256)) {
         // tiles per workgroup: enough to amortise the pipeline's fill, few enough to keep >= ~8 workgroups per CU's worth of runs
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: the tests switch the run length inside one process
-        const int tpw_env = [] { const char* e = getenv("FBBEV_POOL_PIPE_TPW"); return e ? atoi(e) : 0; }();
-#else
-        static const int tpw_env = [] { const char* e = getenv("FBBEV_POOL_PIPE_TPW"); return e ? atoi(e) : 0; }();   // tuning knob, read once
-#endif
+        FBBEV_KNOB_ONCE(int, tpw_env, fbbev_env_int("FBBEV_POOL_PIPE_TPW", 0));   // tuning knob (the emulator tests switch the run length)
         int tpw = tpw_env > 0 ? (tpw_env > 64 ? 64 : tpw_env) : 4;
         if (tpw_env <= 0) while (tpw > 1 && (n_tiles / tpw) * csplit < 2048) tpw >>= 1;
         const long long groups = (n_tiles + tpw - 1) / tpw;
@@ -814,13 +801,10 @@ static int pool_dense_fwd_impl(const float* depth, const float* feat,
             const long long g = 8ll << (a.swizzle - 1);
             grid = (a.n_blocks + g - 1) / g * g;
         }
-#define FBBEV_POOL_PIPE_LAUNCH(TV_, CPL_)                                                                                  \
-        do {                                                                                                               \
-            if (a.lds > 64 * 1024) { int e = fbbev_rt_allow_dyn_lds((const void*)k_pool_fwd_dense_pipe<TV_, CPL_, 4, 256>, a.lds); if (e) return e; } \
-            FBBEV_LAUNCH((k_pool_fwd_dense_pipe<TV_, CPL_, 4, 256>), grid, 256, a.lds, a.stream, a.C, a.Z, a.yx, a.tpp, a.csplit, \
-                         (int)a.n_blocks, a.swizzle, tpw, (int)n_tiles, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf,    \
-                         a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out);                                      \
-        } while (0)
+#define FBBEV_POOL_PIPE_LAUNCH(TV_, CPL_)                                                                                             \
+        FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense_pipe<TV_, CPL_, 4, 256>), grid, 256, a.lds, a.stream, a.C, a.Z, a.yx, a.tpp, a.csplit, \
+                             (int)a.n_blocks, a.swizzle, tpw, (int)n_tiles, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf,      \
+                             a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out)
         if (TV == 64) { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(64, 8); else FBBEV_POOL_PIPE_LAUNCH(64, 4); }
         else if (TV == 128) { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(128, 8); else FBBEV_POOL_PIPE_LAUNCH(128, 4); }
         else { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(256, 8); else FBBEV_POOL_PIPE_LAUNCH(256, 4); }
@@ -1058,11 +1042,7 @@ static int pool_zmean_impl(const float* depth, const float* feat, const int32_t*
     // fits -- OPT-IN (FBBEV_ZMEAN_COL=1): built to cut the Z dependent round-trip chains of the plane walk, measured SLOWER at the
     // BASELINE configs[2] grid, B = 4 (135.7 vs 103.9 us, S3 1.395 vs 1.360 ms: profiles/r05_exp_zmean_col.md -- 54 KB of LDS = 2
     // workgroups per CU instead of 5, and a lane group's pixels are a serial chain of their own)
-#ifdef FBBEV_TEST_OVERRIDES
-    const bool col_on = [] { const char* e = getenv("FBBEV_ZMEAN_COL"); return e && atoi(e) != 0; }();
-#else
-    static const bool col_on = [] { const char* e = getenv("FBBEV_ZMEAN_COL"); return e && atoi(e) != 0; }();   // read once
-#endif
+    FBBEV_KNOB_ONCE(bool, col_on, fbbev_env_int("FBBEV_ZMEAN_COL", 0) != 0);
     const size_t lds_col = fbbev_zmean_col_lds_bytes(CC, TV, Z);
     if (col_on && !rows_out && z_groups == 1 && Z <= 64 && lds_col <= 64 * 1024) {
 #define FBBEV_ZMEAN_COL(TV_, CPL_)                                                                                   \
@@ -1255,12 +1235,8 @@ static bool msda_bwd_plan_for(int B, int S, int M, int Dh, int L, int Q, int P, 
     if (!level_hw || !(Dh == 4 || Dh == 8 || Dh == 10 || Dh == 16 || Dh == 32) || Q <= 0) return false;
     // measured at BASELINE configs[2] (200 x 200 BEV, B = 4): scatter 2.24 / 0.80 / 0.45 ms with 32 / 64 / 128 KB planes -- the
     // halo of re-evaluated queries per band is what costs, so a band is as tall as LDS allows (one workgroup per CU) ...
-    auto read_kb = [] { const char* e = getenv("FBBEV_MSDA_BWD_LDS_KB"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 150 ? v : 144; };
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: the tests switch budgets inside one process
-    const int lds_kb = read_kb();
-#else
-    static const int lds_kb = read_kb();          // read once: ws_bytes() and the launch must agree
-#endif
+    auto read_kb = [] { const int v = fbbev_env_int("FBBEV_MSDA_BWD_LDS_KB", 0); return v >= 1 && v <= 150 ? v : 144; };
+    FBBEV_KNOB_ONCE(int, lds_kb, read_kb());      // read once: ws_bytes() and the launch must agree (the emulator tests switch budgets)
     int budget = (lds_kb * 1024) / (Dh * (int)sizeof(long long)) - 16;
     long long nb = 0, tokens = 0;
     int max_tok = 0, max_w = 1;
@@ -1353,14 +1329,10 @@ extern "C" int fbbev_msda_bwd_ws(const float* value, const int64_t* spatial_shap
         FBBEV_CHECK_LAUNCH();
     }
     const long long wgs = (long long)B * M * pl.n_bands;
-#define FBBEV_MSDA_BWD_SC(DH_)                                                                                        \
-    do {                                                                                                              \
-        int e_ = fbbev_rt_allow_dyn_lds((const void*)k_msda_bwd_scatter<512, DH_>, pl.lds);                            \
-        if (e_) return e_;                                                                                            \
-        FBBEV_LAUNCH((k_msda_bwd_scatter<512, DH_>), wgs, 512, pl.lds, stream, spatial_shapes, level_start_index,      \
-                     sampling_loc, attn_weight, grad_output, (const unsigned int*)ranges, (const int*)qrange, S, M, L,  \
-                     Q, P, pl.n_bands, pl.budget, grad_value);                                                        \
-    } while (0)
+#define FBBEV_MSDA_BWD_SC(DH_)                                                                                             \
+    FBBEV_LAUNCH_DYN_LDS((k_msda_bwd_scatter<512, DH_>), wgs, 512, pl.lds, stream, spatial_shapes, level_start_index,      \
+                         sampling_loc, attn_weight, grad_output, (const unsigned int*)ranges, (const int*)qrange, S, M, L, \
+                         Q, P, pl.n_bands, pl.budget, grad_value)
     if (Dh == 10) FBBEV_MSDA_BWD_SC(10);
     else if (Dh == 8) FBBEV_MSDA_BWD_SC(8);
     else if (Dh == 4) FBBEV_MSDA_BWD_SC(4);
@@ -1473,7 +1445,7 @@ extern "C" int fbbev_da_cross_attn_fwd(const float* value, const int64_t* spatia
 }
 
 static bool da_pipe_disabled() {
-    static const bool off = [] { const char* e = getenv("FBBEV_DA_PIPE"); return e && atoi(e) == 0; }();   // A/B timing knob, read once
+    static const bool off = fbbev_env_int("FBBEV_DA_PIPE", 1) == 0;   // A/B timing knob, read once
     return off;
 }
 static bool da_pipe_shape_ok(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int head_minor, int HS) {
@@ -1516,7 +1488,7 @@ extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spa
     }
     if (!spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth) return FBBEV_E_BADARG;
     // patch mapping (a workgroup = the 8 heads of an 8 x 4 patch of the BEV grid): needs the grid's row length
-    static const bool patch_off = [] { const char* e = getenv("FBBEV_DA_PATCH"); return e && atoi(e) == 0; }();   // A/B timing knob, read once
+    static const bool patch_off = fbbev_env_int("FBBEV_DA_PATCH", 1) == 0;   // A/B timing knob, read once
     const int pw = (!patch_off && bev_w > 0 && M == 8 && Q % bev_w == 0) ? bev_w : 0;
     const long long wgs = pw ? (long long)B * ((pw + 7) / 8) * ((Q / pw + 3) / 4) : (units + 255) / 256;
     long long ub = (wgs + 7) / 8 * 8;                             // XCD-contiguous order: a multiple of 8 workgroups
@@ -1527,7 +1499,7 @@ extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spa
     FBBEV_LAUNCH((k_da_cross_attn_fwd_pipe<DH_, 4, WPS_>), ub, 256, lds, (fbbev_rt_stream)stream_, units, value,         \
                  spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M, L, \
                  Q, P, DC, d0, dstep, HS, zero_bytes, (head_minor & FBBEV_DA_ATTN_LOGITS) ? 1 : 0, pw, slots)
-    static const int wps = [] { const char* e = getenv("FBBEV_DA_PIPE_WPS"); return e ? atoi(e) : 2; }();   // tuning knob, read once (3: 168 registers, spills outside the loop)
+    static const int wps = fbbev_env_int("FBBEV_DA_PIPE_WPS", 2);   // tuning knob, read once (3: 168 registers, spills outside the loop)
     if (Dh == 10) { if (wps == 2) FBBEV_DA_PIPE(10, 2); else FBBEV_DA_PIPE(10, 3); }
     else { if (wps == 2) FBBEV_DA_PIPE(8, 2); else FBBEV_DA_PIPE(8, 3); }
 #undef FBBEV_DA_PIPE
@@ -1543,7 +1515,7 @@ static bool da_fused_shape_ok(int B, int Ncam, int S, int M, int Dh, int L, int 
 }
 extern "C" int fbbev_da_cross_attn_fused_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int bev_w) {
     if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0) return 0;
-    static const bool off = [] { const char* e = getenv("FBBEV_DA_FUSED"); return e && atoi(e) == 0; }();   // A/B timing knob, read once
+    static const bool off = fbbev_env_int("FBBEV_DA_FUSED", 1) == 0;   // A/B timing knob, read once
     return (!off && da_fused_shape_ok(B, Ncam, S, M, Dh, L, Q, P, Za, bev_w)) ? 1 : 0;
 }
 static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
@@ -1577,50 +1549,36 @@ static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_
         return FBBEV_E_UNSUPPORTED;
     // heads per workgroup: 4 = two 256-thread workgroups per patch and per CU (one's prologue + projections under the other's
     // samples), 8 = one 512-thread workgroup per patch (FBBEV_DA_FUSED_HW, read once)
-    auto read_hw = [] { const char* e = getenv("FBBEV_DA_FUSED_HW"); const int v = e ? atoi(e) : 4; return v == 8 ? 8 : 4; };
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: the tests run both forms inside one process
-    const int hw_env = read_hw();
-#else
-    static const int hw_env = read_hw();
-#endif
+    FBBEV_KNOB_ONCE(int, hw_env, fbbev_env_int("FBBEV_DA_FUSED_HW", 4) == 8 ? 8 : 4);   // (the emulator tests run both forms)
     const int hw = op.w_frag ? 8 : (elem_type ? 4 : hw_env); // the output_proj + LayerNorm tail needs all 8 heads of a query in one workgroup
     const long long wgs = (long long)B * ((bev_w + 7) / 8) * ((Q / bev_w + 7) / 8) * (8 / hw);
     const long long grid = (wgs + 7) / 8 * 8;
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     // round 5: floats of a wave's LDS staging region for coarse levels (the 8 x 22 level of BASELINE configs[2] at Dh = 10: 1 760);
     // a level that fits is sampled from LDS instead of through the vector L1.  FBBEV_DA_FUSED_STAGE=0 turns it off (A/B knob)
-    auto read_stage = [] { const char* e = getenv("FBBEV_DA_FUSED_STAGE"); const int v = e ? atoi(e) : 1760; return v < 0 ? 0 : (v > 8192 ? 8192 : v); };
-#ifdef FBBEV_TEST_OVERRIDES
-    const int stage_floats = read_stage();
-#else
-    static const int stage_floats = read_stage();
-#endif
+    auto read_stage = [] { const int v = fbbev_env_int("FBBEV_DA_FUSED_STAGE", 1760); return v < 0 ? 0 : (v > 8192 ? 8192 : v); };
+    FBBEV_KNOB_ONCE(int, stage_floats, read_stage());
     // (fbbev_da_cross_attn_fused_supported budgets LDS WITHOUT the staging region -- a launch whose staged layout does not
     // fit (8 heads per workgroup with ~25+ cameras) runs unstaged instead of failing after the probe said yes)
     int stage_eff = stage_floats;
     if (fbbev_daf_lds_bytes(E, hw, Ncam, stage_eff) > 160 * 1024) stage_eff = 0;
     const size_t lds = fbbev_daf_lds_bytes(E, hw, Ncam, stage_eff);
     if (lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
-    static const bool pre_off = [] { const char* e = getenv("FBBEV_DA_FUSED_PRE"); return e && atoi(e) == 0; }();   // A/B knob, read once
+    static const bool pre_off = fbbev_env_int("FBBEV_DA_FUSED_PRE", 1) == 0;   // A/B knob, read once
     static const int diag = [] {                                                         // timing diagnostics (wrong results), read once
-        const char* e = getenv("FBBEV_DA_FUSED_DIAG");
-        const int v = e ? (atoi(e) & 63) : 0;
+        const int v = fbbev_env_int("FBBEV_DA_FUSED_DIAG", 0) & 63;
         if (v) fprintf(stderr, "libfbbev_hip: FBBEV_DA_FUSED_DIAG=%d -- fbbev_da_cross_attn_fused runs its timing-diagnostic build: RESULTS ARE WRONG BY DESIGN\n", v);
         return v;
     }();
     const int stage_arg = stage_eff | (pre_off ? 0x40000000 : 0) | (diag << 24);
 #define FBBEV_DA_FUSED(DH_, NP_, HW_) FBBEV_DA_FUSED3(DH_, NP_, HW_, false, 0)
 #define FBBEV_DA_FUSED2(DH_, NP_, HW_, OP_) FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, 0)
-#define FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, ET_)                                                                       \
-    do {                                                                                                               \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_da_cross_attn_fused<DH_, 8, NP_, HW_, OP_, ET_>, lds);          \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_da_cross_attn_fused<DH_, 8, NP_, HW_, OP_, ET_>), grid, 64 * HW_, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes, \
-                     level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend,           \
-                     addend_row_stride, addend_period, static_cast<const unsigned short*>(offsets_fragments),         \
-                     offsets_bias, static_cast<const unsigned short*>(attn_fragments), attn_bias, B, Ncam, S, L, Q,    \
-                     bev_w, DC, d0, dstep, slots, op, stage_arg);                                                      \
-    } while (0)
+#define FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, ET_)                                                                                                     \
+    FBBEV_LAUNCH_DYN_LDS((k_da_cross_attn_fused<DH_, 8, NP_, HW_, OP_, ET_>), grid, 64 * HW_, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes, \
+                         level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend,                                      \
+                         addend_row_stride, addend_period, static_cast<const unsigned short*>(offsets_fragments),                                    \
+                         offsets_bias, static_cast<const unsigned short*>(attn_fragments), attn_bias, B, Ncam, S, L, Q,                              \
+                         bev_w, DC, d0, dstep, slots, op, stage_arg)
     // (three samples in flight per lane -- FBBEV_DA_FUSED_NP=3 in round 4 -- measured no gain and, with the staged levels' second
     // sample loop, no longer fits the register file: the instantiations are gone, two in flight is the form)
     // (round 5, 16-bit planes: three / four samples in flight per lane -- 234 registers / 256 with 5 spills -- measured 401.3 / 405.1 us
@@ -1634,12 +1592,10 @@ static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_
     } else if (hw == 8) {
         if (Dh == 10) FBBEV_DA_FUSED(10, 2, 8); else FBBEV_DA_FUSED(8, 2, 8);
     } else if (diag && Dh == 10) {     // FBBEV_DA_FUSED_DIAG: the instantiation with the timing-diagnostic bits (wrong results by design)
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_da_cross_attn_fused<10, 8, 2, 4, false, 0, true>, lds);
-        if (e) return e;
-        FBBEV_LAUNCH((k_da_cross_attn_fused<10, 8, 2, 4, false, 0, true>), grid, 256, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,
-                     level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend, addend_row_stride, addend_period,
-                     static_cast<const unsigned short*>(offsets_fragments), offsets_bias, static_cast<const unsigned short*>(attn_fragments),
-                     attn_bias, B, Ncam, S, L, Q, bev_w, DC, d0, dstep, slots, op, stage_arg);
+        FBBEV_LAUNCH_DYN_LDS((k_da_cross_attn_fused<10, 8, 2, 4, false, 0, true>), grid, 256, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,
+                             level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend, addend_row_stride, addend_period,
+                             static_cast<const unsigned short*>(offsets_fragments), offsets_bias, static_cast<const unsigned short*>(attn_fragments),
+                             attn_bias, B, Ncam, S, L, Q, bev_w, DC, d0, dstep, slots, op, stage_arg);
     } else {
         if (Dh == 10) FBBEV_DA_FUSED(10, 2, 4); else FBBEV_DA_FUSED(8, 2, 4);
     }
@@ -1750,7 +1706,7 @@ extern "C" int fbbev_value_rows_to_head_planes(const float* value, long long n_t
 }
 extern "C" int fbbev_da_cross_attn_fwd_planes_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za) {
     if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0) return 0;
-    static const bool off = [] { const char* e = getenv("FBBEV_DA_FWD_PLANES"); return e && atoi(e) == 0; }();   // A/B timing knob, read once
+    static const bool off = fbbev_env_int("FBBEV_DA_FWD_PLANES", 1) == 0;   // A/B timing knob, read once
     return (!off && M == 8 && (Dh == 10 || Dh == 8) && P == FBBEV_DAF_P && Za == FBBEV_DAF_ZA && (long long)S * Dh * 4 < (1ll << 31) &&
             fbbev_dfp_lds_bytes(Ncam) <= 156 * 1024) ? 1 : 0;
 }
@@ -1772,14 +1728,10 @@ extern "C" int fbbev_da_cross_attn_fwd_planes(const float* planes, const int64_t
     const long long grid = (wgs + 7) / 8 * 8;
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = fbbev_dfp_lds_bytes(Ncam);
-#define FBBEV_DA_FWD_PLANES(DH_)                                                                                       \
-    do {                                                                                                               \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_da_fwd_planes<DH_, 8>, lds);                                     \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_da_fwd_planes<DH_, 8>), grid, 512, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,       \
-                     level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, L, Q, gw, DC, d0,  \
-                     dstep, head_minor & 3, slots);                                                                    \
-    } while (0)
+#define FBBEV_DA_FWD_PLANES(DH_)                                                                                            \
+    FBBEV_LAUNCH_DYN_LDS((k_da_fwd_planes<DH_, 8>), grid, 512, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,       \
+                         level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, L, Q, gw, DC, d0, \
+                         dstep, head_minor & 3, slots)
     if (Dh == 10) FBBEV_DA_FWD_PLANES(10); else FBBEV_DA_FWD_PLANES(8);
 #undef FBBEV_DA_FWD_PLANES
     FBBEV_CHECK_LAUNCH();
@@ -1789,7 +1741,7 @@ extern "C" int fbbev_da_cross_attn_fwd_planes(const float* planes, const int64_t
 // ---- fbbev_msda_self_fused: BEV self-attention, query rows -> attention output in one kernel (da_fused_kernels.h)
 extern "C" int fbbev_msda_self_fused_supported(int B, int S, int M, int Dh, int L, int Q, int P, int bev_w) {
     if (B <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0) return 0;
-    static const bool off = [] { const char* e = getenv("FBBEV_MSDA_FUSED"); return e && atoi(e) == 0; }();   // A/B timing knob, read once
+    static const bool off = fbbev_env_int("FBBEV_MSDA_FUSED", 1) == 0;   // A/B timing knob, read once
     return (!off && M == 8 && (Dh == 10 || Dh == 8) && L == 1 && P == FBBEV_MSF_P && bev_w > 0 && Q % bev_w == 0 &&
             (long long)S * Dh * 4 < (1ll << 31)) ? 1 : 0;
 }
@@ -1823,15 +1775,11 @@ static int msda_self_fused_impl(const float* planes, const float* reference_poin
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = fbbev_msf_lds_bytes(E, M);
 #define FBBEV_MSDA_SELF(DH_) do { if (op.w_frag) FBBEV_MSDA_SELF2(DH_, true); else FBBEV_MSDA_SELF2(DH_, false); } while (0)
-#define FBBEV_MSDA_SELF2(DH_, OP_)                                                                                      \
-    do {                                                                                                               \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_msda_self_fused<DH_, 8, OP_>, lds);                             \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_msda_self_fused<DH_, 8, OP_>), grid, 512, lds, (fbbev_rt_stream)stream_, planes, reference_points,  \
-                     query, query_row_stride, addend, addend_row_stride, addend_period,                                \
-                     static_cast<const unsigned short*>(offsets_fragments), offsets_bias,                              \
-                     static_cast<const unsigned short*>(attn_fragments), attn_bias, B, Q, bev_w, S, level_h, level_w, out, op); \
-    } while (0)
+#define FBBEV_MSDA_SELF2(DH_, OP_)                                                                                             \
+    FBBEV_LAUNCH_DYN_LDS((k_msda_self_fused<DH_, 8, OP_>), grid, 512, lds, (fbbev_rt_stream)stream_, planes, reference_points, \
+                         query, query_row_stride, addend, addend_row_stride, addend_period,                                    \
+                         static_cast<const unsigned short*>(offsets_fragments), offsets_bias,                                  \
+                         static_cast<const unsigned short*>(attn_fragments), attn_bias, B, Q, bev_w, S, level_h, level_w, out, op)
     if (Dh == 10) FBBEV_MSDA_SELF(10); else FBBEV_MSDA_SELF(8);
 #undef FBBEV_MSDA_SELF
 #undef FBBEV_MSDA_SELF2
@@ -2038,19 +1986,12 @@ static int da_bwd_regions(int L, const int32_t* level_hw, int S, int budget, da_
 // the two calls must not be able to make them disagree.  Unset = the measured defaults.
 struct da_bwd_overrides { int tokens, chunks, threads, copies, lds_kb, prepass; };
 static da_bwd_overrides da_bwd_read_env() {
-    auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
-    return da_bwd_overrides{num("FBBEV_DA_BWD_TOKENS"), num("FBBEV_DA_BWD_CHUNKS"), num("FBBEV_DA_BWD_THREADS"),
-                            num("FBBEV_DA_BWD_COPIES"), num("FBBEV_DA_BWD_LDS_KB"),
-                            getenv("FBBEV_DA_BWD_PREPASS") ? num("FBBEV_DA_BWD_PREPASS") : -1};
+    return da_bwd_overrides{fbbev_env_int("FBBEV_DA_BWD_TOKENS", 0), fbbev_env_int("FBBEV_DA_BWD_CHUNKS", 0),
+                            fbbev_env_int("FBBEV_DA_BWD_THREADS", 0), fbbev_env_int("FBBEV_DA_BWD_COPIES", 0),
+                            fbbev_env_int("FBBEV_DA_BWD_LDS_KB", 0), fbbev_env_int("FBBEV_DA_BWD_PREPASS", -1)};
 }
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build only (tests/emu/rt.h): the tests switch plans inside one process
-static da_bwd_overrides da_bwd_env() { return da_bwd_read_env(); }
-#else
-static const da_bwd_overrides& da_bwd_env() {
-    static const da_bwd_overrides o = da_bwd_read_env();
-    return o;
-}
-#endif
+// (the CPU emulator build re-reads them on every call: its tests switch plans inside one process)
+static da_bwd_overrides da_bwd_env() { FBBEV_KNOB_ONCE(da_bwd_overrides, o, da_bwd_read_env()); return o; }
 
 // LDS bytes of the fixed-point planes of one workgroup: 68 KB = two workgroups per CU (FBBEV_DA_BWD_LDS_KB tunes it)
 static int da_bwd_plane_kb() { const int v = da_bwd_env().lds_kb; return v >= 8 && v <= 144 ? v : 68; }
@@ -2101,12 +2042,9 @@ struct da_own_plan { fbbev_da_bwd_region_tab tab; int threads, info_stride, unit
 // FBBEV_DA_BWD_OWNED: 1 = whenever the shape is supported, 0 = never, unset = when the launch has at least one workgroup per CU
 // (the shipped single-level shape at B = 4 has 192 (sample, camera, head) planes: the chunked scatter's 512 workgroups win there)
 static int da_bwd_owned_mode() {
-#ifdef FBBEV_TEST_OVERRIDES
-    const char* e = getenv("FBBEV_DA_BWD_OWNED"); return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-#else
-    static const int mode = [] { const char* e = getenv("FBBEV_DA_BWD_OWNED"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
+    auto read = [] { const char* e = fbbev_env_str("FBBEV_DA_BWD_OWNED"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; };   // unset is a third state
+    FBBEV_KNOB_ONCE(int, mode, read());
     return mode;
-#endif
 }
 // LDS bytes of an owned plane: 136 KB = one 512-thread workgroup per CU; fewer, larger regions beat two workgroups per CU
 // (configs[2] pyramid: 1.06 ms at 136 KB / 512 threads, 1.38 ms at 68 KB / 256, 2.18 ms at 68 KB / 512, 3.47 ms at 34 KB)
@@ -2177,11 +2115,7 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
     pl->unit_planes = 0;
     pl->off_planes = pl->ws;
     {
-#ifdef FBBEV_TEST_OVERRIDES
-        const char* e = getenv("FBBEV_DA_BWD_UNIT_PLANES"); const bool on = !(e && atoi(e) == 0);
-#else
-        static const bool on = [] { const char* e = getenv("FBBEV_DA_BWD_UNIT_PLANES"); return !(e && atoi(e) == 0); }();
-#endif
+        FBBEV_KNOB_ONCE(bool, on, fbbev_env_int("FBBEV_DA_BWD_UNIT_PLANES", 1) != 0);
         bool wide = level_hw != nullptr;
         for (int l = 0; wide && l < L; ++l) wide = level_hw[2 * l + 1] >= 2;
         if (on && wide && M == 8 && (Dh == 10 || Dh == 8) && P == FBBEV_DAF_P && (long long)S * Dh * 4 < (1ll << 31) &&
@@ -2286,26 +2220,13 @@ static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, co
         const long long grid_u = (wgs_u + 7) / 8 * 8;
         const size_t lds_u = fbbev_dbp_lds_bytes(M, Ncam);
         if (grid_u >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-#define FBBEV_DA_UNIT_PLANES(DH_)                                                                                     \
-    do {                                                                                                               \
-        e = fbbev_rt_allow_dyn_lds((const void*)k_da_bwd_unit_planes<DH_, 8>, lds_u);                                  \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_da_bwd_unit_planes<DH_, 8>), grid_u, 512, lds_u, stream, (const float*)planes, spatial_shapes,  \
-                     level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, L, Q, \
-                     gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn, gmax_bits);           \
-    } while (0)
-#define FBBEV_DA_UNIT_PLANES_DET(DH_)                                                                                 \
-    do {                                                                                                               \
-        e = fbbev_rt_allow_dyn_lds((const void*)k_da_bwd_unit_planes<DH_, 8, true>, lds_u);                            \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_da_bwd_unit_planes<DH_, 8, true>), grid_u, 512, lds_u, stream, (const float*)planes,           \
-                     spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, \
-                     Ncam, S, L, Q, gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn,         \
-                     gmax_bits);                                                                                       \
-    } while (0)
-        if (det) { if (Dh == 10) FBBEV_DA_UNIT_PLANES_DET(10); else FBBEV_DA_UNIT_PLANES_DET(8); }
-        else if (Dh == 10) FBBEV_DA_UNIT_PLANES(10); else FBBEV_DA_UNIT_PLANES(8);
-#undef FBBEV_DA_UNIT_PLANES_DET
+#define FBBEV_DA_UNIT_PLANES(DH_, DET_)                                                                                       \
+    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_unit_planes<DH_, 8, DET_>), grid_u, 512, lds_u, stream, (const float*)planes,             \
+                         spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, \
+                         Ncam, S, L, Q, gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn,         \
+                         gmax_bits)
+        if (det) { if (Dh == 10) FBBEV_DA_UNIT_PLANES(10, true); else FBBEV_DA_UNIT_PLANES(8, true); }
+        else if (Dh == 10) FBBEV_DA_UNIT_PLANES(10, false); else FBBEV_DA_UNIT_PLANES(8, false);
 #undef FBBEV_DA_UNIT_PLANES
         FBBEV_CHECK_LAUNCH();
     } else {
@@ -2319,15 +2240,11 @@ static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, co
     FBBEV_CHECK_LAUNCH();
     const fbbev_da_bwd_region_tab& tab = op.tab;
     const long long wgs = (long long)tab.n * B * Ncam * M;
-#define FBBEV_DA_OWN(NT_, DH_)                                                                                          \
-    do {                                                                                                                \
-        e = fbbev_rt_allow_dyn_lds((const void*)k_da_bwd_scatter_owned<NT_, DH_>, op.lds);                              \
-        if (e) return e;                                                                                                \
-        FBBEV_LAUNCH((k_da_bwd_scatter_owned<NT_, DH_>), wgs, NT_, op.lds, stream, spatial_shapes, level_start_index,   \
-                     ref_cam, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, head_minor & 3, HS, tab,            \
-                     (const float*)hit_rec, (const int*)hit_count,                                                       \
-                     (const unsigned int*)gmax_bits, (head_minor & 4) ? 1 : 0, grad_value);                              \
-    } while (0)
+#define FBBEV_DA_OWN(NT_, DH_)                                                                                            \
+    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_scatter_owned<NT_, DH_>), wgs, NT_, op.lds, stream, spatial_shapes, level_start_index, \
+                         ref_cam, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, head_minor & 3, HS, tab,         \
+                         (const float*)hit_rec, (const int*)hit_count,                                                    \
+                         (const unsigned int*)gmax_bits, (head_minor & 4) ? 1 : 0, grad_value)
 #define FBBEV_DA_OWN_NT(DH_) do { if (op.threads == 512) FBBEV_DA_OWN(512, DH_); else FBBEV_DA_OWN(256, DH_); } while (0)   /* 1024 threads measured slower */
     if (Dh == 10) FBBEV_DA_OWN_NT(10);
     else if (Dh == 8) FBBEV_DA_OWN_NT(8);
@@ -2669,12 +2586,8 @@ static int pool_dense_bwd_impl(const float* out_grad, long long og_stride_b, lon
     FBBEV_LAUNCH(k_tile_lower_bound2, (l.n_tiles + 1 + 255) / 256, 256, 0, stream, (int)l.n_tiles, l.tpp, (int)yx,
                  128, interval_rank, interval_starts, counts, n_intervals_max, (const int*)nullptr, meta);
     FBBEV_CHECK_LAUNCH();
-    if (lds > 64 * 1024) {
-        e = fbbev_rt_allow_dyn_lds((const void*)k_pool_bwd_rows<128>, lds);
-        if (e) return e;
-    }
-    FBBEV_LAUNCH(k_pool_bwd_rows<128>, l.n_tiles, 256, lds, stream, C, Z, (int)yx, l.tpp, og_stride_b, og_stride_c,
-                 out_grad, interval_rank, meta, rows, zgrad, zscale);
+    FBBEV_LAUNCH_DYN_LDS(k_pool_bwd_rows<128>, l.n_tiles, 256, lds, stream, C, Z, (int)yx, l.tpp, og_stride_b, og_stride_c,
+                         out_grad, interval_rank, meta, rows, zgrad, zscale);
     FBBEV_CHECK_LAUNCH();
     const long long n_pixels = (long long)B * N * H * W;
     const long long blocks = (n_pixels + 7) / 8;      // 8 half-waves per 256-thread workgroup
@@ -2743,7 +2656,7 @@ extern "C" int fbbev_history_warp_e(const void* history, long long history_strid
     // FBBEV_HISTORY_WARP=lds selects the LDS-staged brick kernel (k_history_warp_lds: bit-identical, but as built --
     // one 1024-thread workgroup per CU, staging and taps of a channel serialised by two barriers -- 3x SLOWER than the
     // gather kernel on MI355X, profiles/r02_time_history_lds_vs_gather.jsonl; kept for the next iteration, not the default)
-    const char* mode = getenv("FBBEV_HISTORY_WARP");
+    const char* mode = fbbev_env_str("FBBEV_HISTORY_WARP");      // read on every call
     const bool lds = mode && mode[0] == 'l';
     if (lds && zyx >= 4096 && X >= 16) {
         int TX = 64;
@@ -2817,7 +2730,7 @@ static int history_warp_vm_plan(const void* history, long long& history_stride_b
     if (frame * (elem_type == 0 ? 4 : 2) >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;      // 32-bit byte offsets inside a frame
     pl.n_xc = (X * pl.groups + 255) / 256;                        // workgroups per grid row
     int YB = 128 / Z;                                             // rows per band: a (z, y) slab of ~128 workgroups per x chunk
-    if (const char* e = getenv("FBBEV_HISTORY_VM_YB")) YB = atoi(e);        // tuning knob (profiles/r02_time_history_bf16_voxel_major.jsonl)
+    YB = fbbev_env_int("FBBEV_HISTORY_VM_YB", YB);                // tuning knob, read on every call (profiles/r02_time_history_bf16_voxel_major.jsonl)
     if (YB < 1) YB = 1;
     if (YB > Y) YB = Y;
     pl.YB = YB;
@@ -2836,20 +2749,14 @@ static int history_warp_vm_bands(const void* history, long long history_stride_b
     if (blocks == 0) return 0;
     const int per_xcd = (int)((blocks + 7) / 8);
     // occupancy experiment knob (round 3, profiles/r03_exp_history_occupancy.jsonl): dynamic LDS the kernel does not use, in KB
-    static const size_t warp_pad = [] { const char* e = getenv("FBBEV_HISTORY_WARP_LDS_PAD_KB"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();
-    if (warp_pad > 64 * 1024) {
-        fbbev_rt_allow_dyn_lds((const void*)k_history_warp_vm<0, TU, 1>, warp_pad);
-        fbbev_rt_allow_dyn_lds((const void*)k_history_warp_vm<1, TU, 1>, warp_pad);
-        fbbev_rt_allow_dyn_lds((const void*)k_history_warp_vm<2, TU, 1>, warp_pad);
-        fbbev_rt_allow_dyn_lds((const void*)k_history_warp_vm<2, 4, 1>, warp_pad);
-    }
-#define FBBEV_HWVM(ET_, TU_, ST_)                                                                                            \
-    FBBEV_LAUNCH((k_history_warp_vm<ET_, TU_, ST_>), (long long)per_xcd * 8, 256, warp_pad, stream, history, history_stride_b, rt_flow, \
-                 T, C, Z, Y, X, groups, n_xc, YB, nyb_c, per_xcd, (int)blocks, out, out_stride_b, yb0)
+    static const size_t warp_pad = (size_t)fbbev_env_int("FBBEV_HISTORY_WARP_LDS_PAD_KB", 0) * 1024;
+#define FBBEV_HWVM(ET_, TU_, ST_)                                                                                                               \
+    FBBEV_LAUNCH_DYN_LDS((k_history_warp_vm<ET_, TU_, ST_>), (long long)per_xcd * 8, 256, warp_pad, stream, history, history_stride_b, rt_flow, \
+                         T, C, Z, Y, X, groups, n_xc, YB, nyb_c, per_xcd, (int)blocks, out, out_stride_b, yb0)
     // ST = 1: non-temporal ring stores (A/B on one box: 4.0 vs 4.2 ms at 400x400x16, 0.56 vs 0.61 ms at 100x100x8 B=4)
     // fp16 ring: four frames (32 taps) in flight per thread -- the widening rides in the multiply (v_fma_mix_f32), which left the
     // registers for it (round 6: 3.45 -> 3.33 ms at 400x400x16); FBBEV_HISTORY_VM_TU=2 restores two
-    static const int tu2 = [] { const char* e = getenv("FBBEV_HISTORY_VM_TU"); return e && atoi(e) == 2 ? 1 : 0; }();
+    static const int tu2 = fbbev_env_int("FBBEV_HISTORY_VM_TU", 0) == 2 ? 1 : 0;
     if (elem_type == 0) FBBEV_HWVM(0, TU, 1);
     else if (elem_type == 1) FBBEV_HWVM(1, TU, 1);
     else if (tu2) FBBEV_HWVM(2, TU, 1);
@@ -2884,14 +2791,9 @@ extern "C" int fbbev_history_frame_vm(const float* curr, int B, int C, int N, in
     if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)C * 65 * sizeof(float);
     fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    if (lds > 64 * 1024) {
-        const void* k = elem_type == 0 ? (const void*)k_history_frame_vm<0> : elem_type == 1 ? (const void*)k_history_frame_vm<1> : (const void*)k_history_frame_vm<2>;
-        const int e = fbbev_rt_allow_dyn_lds(k, lds);
-        if (e) return e;
-    }
-    if (elem_type == 0) FBBEV_LAUNCH(k_history_frame_vm<0>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
-    else if (elem_type == 1) FBBEV_LAUNCH(k_history_frame_vm<1>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
-    else FBBEV_LAUNCH(k_history_frame_vm<2>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
+    if (elem_type == 0) FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<0>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
+    else if (elem_type == 1) FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<1>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
+    else FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<2>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2999,14 +2901,11 @@ static int history_conv_bf16_launch(const void* feats, long long feats_stride_b,
     FBBEV_LAUNCH(k_history_weight_fragments_bf16, (nfrag + 255) / 256, 256, 0, stream, w1, w2, MT1, MT2, C, T1, w1f);
     const size_t a2s = (size_t)((MT2 * KS * 64 + 255) / 256) * 256 * 8;                                 // padded staging buffer
     size_t lds = (2 * a2s + (size_t)4 * 16 * (KS * 32 + 8)) * sizeof(unsigned short);           // W2_t x 2 + Y rows
-    static const size_t conv_pad = [] { const char* e = getenv("FBBEV_HISTORY_CONV_LDS_PAD_KB"); return e ? (size_t)atoi(e) * 1024 : (size_t)0; }();   // occupancy experiment knob
-    if (conv_pad > lds) {
-        lds = conv_pad;
-        if (lds > 64 * 1024) fbbev_rt_allow_dyn_lds((const void*)k_history_conv_bf16<5, 5, ET, VM>, lds);
-    }
+    static const size_t conv_pad = (size_t)fbbev_env_int("FBBEV_HISTORY_CONV_LDS_PAD_KB", 0) * 1024;   // occupancy experiment knob
+    if (conv_pad > lds) lds = conv_pad;
     if (C == 80)
-        FBBEV_LAUNCH((k_history_conv_bf16<5, 5, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
-                     (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, T1, N, tiles_per_b, out);
+        FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16<5, 5, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
+                             (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, T1, N, tiles_per_b, out);
     else
         FBBEV_LAUNCH((k_history_conv_bf16<1, 1, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
                      (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, T1, N, tiles_per_b, out);
@@ -3082,14 +2981,10 @@ static int history_conv_x3_segments(const void* feats, long long feats_stride_b,
     if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     // one frame per workgroup barrier (FPB = 2, four W2 buffers: measured 2 % slower, profiles/r06_exp_history_step.md)
     const size_t lds = ((size_t)2 * ((pl.pieces + nt - 1) / nt) * nt * 8 + 2 * pl.part1) * sizeof(unsigned short);
-#define FBBEV_HX3(MT_, ET_, PF_, NW_, FPB_)                                                                            \
-    do {                                                                                                              \
-        int e_ = fbbev_rt_allow_dyn_lds((const void*)k_history_conv_bf16x3<MT_, MT_, ET_, PF_, NW_, FPB_>, lds);        \
-        if (e_) return e_;                                                                                            \
-        FBBEV_LAUNCH((k_history_conv_bf16x3<MT_, MT_, ET_, PF_, NW_, FPB_>), blocks, 64 * NW_, lds, stream, feats, feats_stride_b, \
-                     (const unsigned short*)pl.w1x, (const float*)pl.biasx, (const unsigned short*)pl.w2x, bias2, T1, N, \
-                     (int)tiles_per_b, out, seg0, seg_stride, seg_len, tiles_per_seg);                                 \
-    } while (0)
+#define FBBEV_HX3(MT_, ET_, PF_, NW_, FPB_)                                                                                            \
+    FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16x3<MT_, MT_, ET_, PF_, NW_, FPB_>), blocks, 64 * NW_, lds, stream, feats, feats_stride_b, \
+                         (const unsigned short*)pl.w1x, (const float*)pl.biasx, (const unsigned short*)pl.w2x, bias2, T1, N,           \
+                         (int)tiles_per_b, out, seg0, seg_stride, seg_len, tiles_per_seg)
     /* two frames of X in flight: three spill (256 registers at 2 waves / SIMD) */
 #define FBBEV_HX3P(MT_, ET_) do { if (nw == 4) FBBEV_HX3(MT_, ET_, 2, 4, 1); else FBBEV_HX3(MT_, ET_, 2, 8, 1); } while (0)
     if (C == 80) { if (elem_type == 1) FBBEV_HX3P(5, 1); else FBBEV_HX3P(5, 2); }
@@ -3109,7 +3004,7 @@ extern "C" int fbbev_history_conv_bf16x3(const void* feats, long long feats_stri
     const int e = history_conv_x3_prepare(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace,
                                           workspace_bytes, elem_type, stream, pl);
     if (e || B <= 0 || N <= 0) return e;
-    static const int nw = [] { const char* e = getenv("FBBEV_HX3_WAVES"); return e && atoi(e) == 4 ? 4 : 8; }();     // tuning: 256-thread workgroups
+    static const int nw = fbbev_env_int("FBBEV_HX3_WAVES", 8) == 4 ? 4 : 8;     // tuning: 256-thread workgroups
     return history_conv_x3_segments(feats, feats_stride_b, bias2, B, T1, C, N, out, elem_type, pl, 0, 0, N, 1, nw, stream);
 }
 
@@ -3144,14 +3039,10 @@ extern "C" int fbbev_history_fused_x3_vm(const void* history, long long history_
     // two W2 / bias blocks + W1 (hi | lo) + two operand tiles [128 voxels][FBBEV_HFX_PITCH] + the voxel table [128][16 dwords]: 154 KB
     const size_t lds = ((size_t)2 * ((cp.pieces + 511) / 512) * 512 * 8 + 2 * cp.part1 + (size_t)2 * 128 * FBBEV_HFX_PITCH) * sizeof(unsigned short) +
                        (size_t)128 * 16 * sizeof(unsigned int);
-#define FBBEV_HFX(ET_)                                                                                                 \
-    do {                                                                                                              \
-        int e_ = fbbev_rt_allow_dyn_lds((const void*)k_history_fused_x3<ET_>, lds);                                    \
-        if (e_) return e_;                                                                                            \
-        FBBEV_LAUNCH((k_history_fused_x3<ET_>), (long long)per_xcd * 8, 512, lds, stream, history, history_stride_b,   \
-                     next, next_stride_b, rt_flow, (const unsigned short*)cp.w1x, (const float*)cp.biasx,             \
-                     (const unsigned short*)cp.w2x, bias2, T1, Z, Y, X, n_xt, n_yt, per_xcd, (int)blocks, out, dump);  \
-    } while (0)
+#define FBBEV_HFX(ET_)                                                                                                   \
+    FBBEV_LAUNCH_DYN_LDS((k_history_fused_x3<ET_>), (long long)per_xcd * 8, 512, lds, stream, history, history_stride_b, \
+                         next, next_stride_b, rt_flow, (const unsigned short*)cp.w1x, (const float*)cp.biasx,            \
+                         (const unsigned short*)cp.w2x, bias2, T1, Z, Y, X, n_xt, n_yt, per_xcd, (int)blocks, out, dump)
     if (elem_type == 1) FBBEV_HFX(1); else FBBEV_HFX(2);
 #undef FBBEV_HFX
     FBBEV_CHECK_LAUNCH();
@@ -3176,8 +3067,7 @@ static fbbev_side_stream* history_side_stream() {
         // the convolutions' stream is created at the device's highest priority: built to let their workgroups in ahead of the thousands
         // of queued warp workgroups -- measured: no effect on the dispatch (profiles/r06_exp_history_step.md).
         // FBBEV_HISTORY_STEP_PRIORITY=0: equal priorities
-        const char* pe = getenv("FBBEV_HISTORY_STEP_PRIORITY");
-        table[d].ok = fbbev_rt_stream_create(&table[d].stream, pe && atoi(pe) == 0 ? 0 : 1) == 0;
+        table[d].ok = fbbev_rt_stream_create(&table[d].stream, fbbev_env_int("FBBEV_HISTORY_STEP_PRIORITY", 1) == 0 ? 0 : 1) == 0;
         for (int i = 0; i < 2 + 64 && table[d].ok; ++i) table[d].ok = fbbev_rt_event_create(&table[d].ev[i]) == 0;
     }
     return table[d].ok ? &table[d] : nullptr;
@@ -3210,7 +3100,7 @@ extern "C" int fbbev_history_step_x3_vm(const void* history, long long history_s
     if (e) return e;
     if (chunks == 0) chunks = 10;
     // the convolutions of the pipeline in 256-thread workgroups: half a CU's registers, so that warp waves share the CU with them
-    static const int step_nw = [] { const char* e = getenv("FBBEV_HISTORY_STEP_WAVES"); return e && atoi(e) == 8 ? 8 : 4; }();
+    static const int step_nw = fbbev_env_int("FBBEV_HISTORY_STEP_WAVES", 4) == 8 ? 8 : 4;
     if (chunks > wp.nyb) chunks = wp.nyb;
     fbbev_side_stream* side = chunks > 1 ? history_side_stream() : nullptr;
     if (!side) {                                                                                  // one chunk: the two kernels back to back
@@ -3256,7 +3146,45 @@ extern "C" int fbbev_rows_linear_x3_fragments(const float* weight, int in_featur
     return 0;
 }
 
-static bool rows_linear_nt1() { static const bool v = [] { const char* e = getenv("FBBEV_ROWS_LINEAR_NT"); return e && atoi(e) == 1; }(); return v; }   // tuning knob, read once
+// What the split-bf16 (x3) and the exact-fp32 (f32) entries have in common: the checks of the addend and of the LayerNorm tail's
+// operands, which the entries make before anything else is looked at, ...
+static int rows_linear_addend_check(const float* addend, long long* addend_row_stride, long long addend_period, int in_features) {
+    if (!addend || addend_period <= 0) return FBBEV_E_BADARG;
+    return row_operand(addend, addend_row_stride, in_features);
+}
+static int rows_linear_ln_check(const float* residual, long long* residual_row_stride, const float* ln_weight, const float* ln_bias,
+                                int out_features) {
+    if (!ln_weight || !ln_bias || out_features <= 0) return FBBEV_E_BADARG;
+    if (out_features > 128) return FBBEV_E_UNSUPPORTED;
+    if (residual) { if (const int e = row_operand(residual, residual_row_stride, out_features)) return e; }
+    if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
+    return 0;
+}
+// ... and the checks of x / weights / bias / out with the launch geometry.  `weights`: the fragment buffer (x3) or the weight matrix
+// (f32).  A nonzero result, or rows == 0, ends the call.
+struct rows_linear_geom { int n_oc, n_kc, nmt; long long tiles, RT, groups; };
+static int rows_linear_prepare(const float* x, long long* x_row_stride, const void* weights, const float* bias, long long rows,
+                               int in_features, int out_features, const float* out, long long* out_row_stride, rows_linear_geom* g) {
+    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
+    if (rows == 0) return 0;
+    if (!x || !weights || !out) return FBBEV_E_BADARG;
+    if (const int e = row_worse(row_operand(x, x_row_stride, in_features), row_operand(out, out_row_stride, out_features))) return e;
+    if (in_features % 8 != 0 || out_features % 4 != 0 || !aligned16(weights) || (bias && !aligned16(bias))) return FBBEV_E_UNSUPPORTED;
+    g->n_oc = (out_features + 127) / 128; g->n_kc = (in_features + 127) / 128;
+    g->tiles = (rows + 127) / 128;
+    if (g->tiles * g->n_oc >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    g->nmt = out_features >= 128 ? 8 : (out_features + 15) / 16;
+    // consecutive row tiles per workgroup (fragments / the weight staged once) as long as ~4 workgroups per CU remain; the chain of
+    // an f32 element does not depend on it
+    g->RT = g->n_kc == 1 ? g->tiles * g->n_oc / 1024 : 1;
+    g->RT = g->RT < 1 ? 1 : (g->RT > 8 ? 8 : g->RT);
+    const int rt_emu = FBBEV_KNOB_EMU_INT("FBBEV_ROWS_LINEAR_RT", 0);   // lets a small case walk several row tiles per workgroup
+    if (g->n_kc == 1 && rt_emu >= 1 && rt_emu <= 8) g->RT = rt_emu;
+    g->groups = (g->tiles + g->RT - 1) / g->RT;
+    return 0;
+}
+
+static bool rows_linear_nt1() { static const bool v = fbbev_env_int("FBBEV_ROWS_LINEAR_NT", 0) == 1; return v; }   // tuning knob, read once
 static int rows_linear_x3_impl(const float* x, long long x_row_stride, const void* fragments, const float* bias, long long rows,
                                int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
@@ -3275,10 +3203,7 @@ extern "C" int fbbev_rows_linear_x3_add(const float* x, long long x_row_stride, 
                                         long long addend_period, const void* fragments, const float* bias, long long rows,
                                         int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                         fbbev_stream_t stream_) {
-    if (!addend || addend_period <= 0) return FBBEV_E_BADARG;
-    if (addend_row_stride == 0) addend_row_stride = in_features;
-    if (addend_row_stride < in_features) return FBBEV_E_BADARG;
-    if (addend_row_stride % 4 != 0 || !aligned16(addend)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
     return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
                                addend_row_stride, addend_period, stream_);
 }
@@ -3288,55 +3213,34 @@ static int rows_linear_x3_impl(const float* x, long long x_row_stride, const voi
                                const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
                                int plane_S, int plane_TS, const float* res, long long ld_res, const float* ln_w, const float* ln_b,
                                float ln_eps, const float* mask, long long ld_mask, bool train_epi) {
-    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
-    if (rows == 0) return 0;
-    if (!x || !fragments || !out) return FBBEV_E_BADARG;
-    if (x_row_stride == 0) x_row_stride = in_features;
-    if (out_row_stride == 0) out_row_stride = out_features;
-    if (x_row_stride < in_features || out_row_stride < out_features) return FBBEV_E_BADARG;
-    if (in_features % 8 != 0 || out_features % 4 != 0 || x_row_stride % 4 != 0 || out_row_stride % 4 != 0 || !aligned16(x) ||
-        !aligned16(out) || !aligned16(fragments) || (bias && !aligned16(bias))) return FBBEV_E_UNSUPPORTED;
-    const int n_oc = (out_features + 127) / 128, n_kc = (in_features + 127) / 128;
-    const long long tiles = (rows + 127) / 128;
-    if (tiles * n_oc >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int nmt = out_features >= 128 ? 8 : (out_features + 15) / 16;
-    const size_t lds = (size_t)nmt * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short);
-    int e = ln_w ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, false>, lds);
+    rows_linear_geom g;
+    int e = rows_linear_prepare(x, &x_row_stride, fragments, bias, rows, in_features, out_features, out, &out_row_stride, &g);
+    if (e || rows == 0) return e;
+    const int n_oc = g.n_oc, n_kc = g.n_kc;
+    const long long tiles = g.tiles, RT = g.RT, groups = g.groups;
+    const size_t lds = (size_t)g.nmt * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short);
+    // (kept ahead of the dispatch although most calls launch k_rows_linear_x3p: as the first use of these two kernels in the file it
+    // also fixes their place in the code object, and device code is compared byte for byte across host-only changes)
+    e = ln_w ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, false>, lds);
     if (e) return e;
-    // consecutive row tiles per workgroup (fragments staged once) as long as ~4 workgroups per CU remain
-    long long RT = n_kc == 1 ? tiles * n_oc / 1024 : 1;
-    RT = RT < 1 ? 1 : (RT > 8 ? 8 : RT);
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: lets a small case walk several row tiles per workgroup
-    { const char* e_rt = getenv("FBBEV_ROWS_LINEAR_RT"); if (e_rt && n_kc == 1 && atoi(e_rt) >= 1 && atoi(e_rt) <= 8) RT = atoi(e_rt); }
-#endif
-    const long long groups = (tiles + RT - 1) / RT;
     // round 6: the persistent form (k_rows_linear_x3p: fragments staged once per workgroup, the next tile's rows in flight under the
     // MFMAs, fragment reads under the MFMAs of the tile before) for one K chunk, no addend, no LayerNorm tail.  Same bits.
     // FBBEV_ROWS_LINEAR_P=0: off (A/B knob)
-#ifdef FBBEV_TEST_OVERRIDES
-    const bool persist = [] { const char* e_ = getenv("FBBEV_ROWS_LINEAR_P"); return !(e_ && atoi(e_) == 0); }();
-#else
-    static const bool persist = [] { const char* e_ = getenv("FBBEV_ROWS_LINEAR_P"); return !(e_ && atoi(e_) == 0); }();
-#endif
+    FBBEV_KNOB_ONCE(bool, persist, fbbev_env_int("FBBEV_ROWS_LINEAR_P", 1) != 0);
     // (the training epilogue at 8 output tiles x 4 k-steps -- 96 < I <= 128 and O > 80: no layer of the model -- would spill: old kernel)
     if (persist && n_kc == 1 && !ln_w && !addend && !(rows_linear_nt1() && !train_epi) &&
         !(train_epi && out_features > 80 && in_features > 96)) {
         const int nmtp = out_features <= 80 ? 5 : 8, ksp = in_features <= 96 ? 3 : 4;
         long long n_slots = 512 / n_oc;
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: lets a small case walk several row tiles per workgroup
-        { const char* e_sl = getenv("FBBEV_ROWS_LINEAR_SLOTS"); if (e_sl && atoi(e_sl) >= 1) n_slots = atoi(e_sl); }
-#endif
+        const int slots_emu = FBBEV_KNOB_EMU_INT("FBBEV_ROWS_LINEAR_SLOTS", 0);   // lets a small case walk several row tiles per workgroup
+        if (slots_emu >= 1) n_slots = slots_emu;
         if (n_slots < 1) n_slots = 1;
         if (n_slots > tiles) n_slots = tiles;
         const size_t ldsp = (size_t)nmtp * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short) + (size_t)16 * nmtp * sizeof(float);
-#define FBBEV_RLP(NMT_, KS_, EPI_)                                                                                      \
-    do {                                                                                                              \
-        e = fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3p<NMT_, KS_, EPI_>, ldsp);                              \
-        if (e) return e;                                                                                              \
-        FBBEV_LAUNCH((k_rows_linear_x3p<NMT_, KS_, EPI_>), n_slots * n_oc, 256, ldsp, (fbbev_rt_stream)stream_, x, x_row_stride, \
-                     static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu, \
-                     n_oc, (int)n_slots, plane_S, plane_TS, res, ld_res, mask, ld_mask);                              \
-    } while (0)
+#define FBBEV_RLP(NMT_, KS_, EPI_)                                                                                                        \
+    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3p<NMT_, KS_, EPI_>), n_slots * n_oc, 256, ldsp, (fbbev_rt_stream)stream_, x, x_row_stride,      \
+                         static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu, \
+                         n_oc, (int)n_slots, plane_S, plane_TS, res, ld_res, mask, ld_mask)
         if (train_epi) {
             if (nmtp == 5) { if (ksp == 3) FBBEV_RLP(5, 3, 1); else FBBEV_RLP(5, 4, 1); }
             else FBBEV_RLP(8, 3, 1);
@@ -3349,12 +3253,10 @@ static int rows_linear_x3_impl(const float* x, long long x_row_stride, const voi
         return 0;
     }
     if (train_epi) {
-        e = fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, false, 1>, lds);
-        if (e) return e;
-        FBBEV_LAUNCH((k_rows_linear_x3<2, false, 1>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                     static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                     n_kc, n_oc, (int)RT, addend, addend_row_stride, addend_period, 0, 0, res, ld_res, (const float*)nullptr,
-                     (const float*)nullptr, 0.f, mask, ld_mask);
+        FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3<2, false, 1>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
+                             static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
+                             n_kc, n_oc, (int)RT, addend, addend_row_stride, addend_period, 0, 0, res, ld_res, (const float*)nullptr,
+                             (const float*)nullptr, 0.f, mask, ld_mask);
     } else if (ln_w) {
         if (n_oc != 1) return FBBEV_E_UNSUPPORTED;
         FBBEV_LAUNCH((k_rows_linear_x3<2, true>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
@@ -3366,12 +3268,10 @@ static int rows_linear_x3_impl(const float* x, long long x_row_stride, const voi
         const long long tiles1 = (rows + 63) / 64;
         long long RT1 = tiles1 * n_oc / 2048;
         RT1 = RT1 < 1 ? 1 : (RT1 > 8 ? 8 : RT1);
-        e = fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<1, false>, lds);
-        if (e) return e;
-        FBBEV_LAUNCH((k_rows_linear_x3<1, false>), (tiles1 + RT1 - 1) / RT1 * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                     static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                     n_kc, n_oc, (int)RT1, addend, addend_row_stride, addend_period, plane_S, plane_TS, res, ld_res, ln_w, ln_b, ln_eps,
-                     (const float*)nullptr, 0ll);
+        FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3<1, false>), (tiles1 + RT1 - 1) / RT1 * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
+                             static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
+                             n_kc, n_oc, (int)RT1, addend, addend_row_stride, addend_period, plane_S, plane_TS, res, ld_res, ln_w, ln_b, ln_eps,
+                             (const float*)nullptr, 0ll);
     } else {
         FBBEV_LAUNCH((k_rows_linear_x3<2, false>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
                      static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
@@ -3391,23 +3291,12 @@ extern "C" int fbbev_rows_linear_x3_train(const float* x, long long x_row_stride
                                           fbbev_stream_t stream_) {
     if (out_features <= 0 || in_features <= 0) return FBBEV_E_BADARG;
     if (addend) {
-        if (addend_period <= 0) return FBBEV_E_BADARG;
-        if (addend_row_stride == 0) addend_row_stride = in_features;
-        if (addend_row_stride < in_features) return FBBEV_E_BADARG;
-        if (addend_row_stride % 4 != 0 || !aligned16(addend)) return FBBEV_E_UNSUPPORTED;
+        if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
     } else {
         addend_period = 1;
     }
-    if (residual) {
-        if (residual_row_stride == 0) residual_row_stride = out_features;
-        if (residual_row_stride < out_features) return FBBEV_E_BADARG;
-        if (residual_row_stride % 4 != 0 || !aligned16(residual)) return FBBEV_E_UNSUPPORTED;
-    }
-    if (mask) {
-        if (mask_row_stride == 0) mask_row_stride = out_features;
-        if (mask_row_stride < out_features) return FBBEV_E_BADARG;
-        if (mask_row_stride % 4 != 0 || !aligned16(mask)) return FBBEV_E_UNSUPPORTED;
-    }
+    if (residual) { if (const int e = row_operand(residual, &residual_row_stride, out_features)) return e; }
+    if (mask) { if (const int e = row_operand(mask, &mask_row_stride, out_features)) return e; }
     return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
                                addend_row_stride, addend_period, stream_, 0, 0, residual, residual_row_stride, nullptr, nullptr, 0.f,
                                mask, mask_row_stride, true);
@@ -3421,14 +3310,7 @@ extern "C" int fbbev_rows_linear_x3_ln(const float* x, long long x_row_stride, c
                                        int in_features, int out_features, const float* residual, long long residual_row_stride,
                                        const float* ln_weight, const float* ln_bias, float ln_eps, float* out,
                                        long long out_row_stride, fbbev_stream_t stream_) {
-    if (!ln_weight || !ln_bias || out_features <= 0) return FBBEV_E_BADARG;
-    if (out_features > 128) return FBBEV_E_UNSUPPORTED;
-    if (residual) {
-        if (residual_row_stride == 0) residual_row_stride = out_features;
-        if (residual_row_stride < out_features) return FBBEV_E_BADARG;
-        if (residual_row_stride % 4 != 0 || !aligned16(residual)) return FBBEV_E_UNSUPPORTED;
-    }
-    if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = rows_linear_ln_check(residual, &residual_row_stride, ln_weight, ln_bias, out_features)) return e;
     return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
                                stream_, 0, 0, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
 }
@@ -3441,38 +3323,17 @@ static int rows_linear_f32_impl(const float* x, long long x_row_stride, const fl
                                 const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
                                 const float* res = nullptr, long long ld_res = 0, const float* ln_w = nullptr,
                                 const float* ln_b = nullptr, float ln_eps = 0.f) {
-    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
-    if (rows == 0) return 0;
-    if (!x || !weight || !out) return FBBEV_E_BADARG;
-    if (x_row_stride == 0) x_row_stride = in_features;
-    if (out_row_stride == 0) out_row_stride = out_features;
-    if (x_row_stride < in_features || out_row_stride < out_features) return FBBEV_E_BADARG;
-    if (in_features % 8 != 0 || out_features % 4 != 0 || x_row_stride % 4 != 0 || out_row_stride % 4 != 0 || !aligned16(x) ||
-        !aligned16(out) || !aligned16(weight) || (bias && !aligned16(bias))) return FBBEV_E_UNSUPPORTED;
-    const int n_oc = (out_features + 127) / 128, n_kc = (in_features + 127) / 128;
-    const long long tiles = (rows + 127) / 128;
-    if (tiles * n_oc >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (ln_w && n_oc != 1) return FBBEV_E_UNSUPPORTED;
-    const int nmt = out_features >= 128 ? 8 : (out_features + 15) / 16;
-    const size_t lds = (size_t)nmt * FBBEV_RLF_TILE_FLOATS * sizeof(float);
-    int e = ln_w ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_f32<true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_f32<false>, lds);
-    if (e) return e;
-    // consecutive row tiles per workgroup (the weight staged once) as long as ~4 workgroups per CU remain; the chain of an element
-    // does not depend on it
-    long long RT = n_kc == 1 ? tiles * n_oc / 1024 : 1;
-    RT = RT < 1 ? 1 : (RT > 8 ? 8 : RT);
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: lets a small case walk several row tiles per workgroup
-    { const char* e_rt = getenv("FBBEV_ROWS_LINEAR_RT"); if (e_rt && n_kc == 1 && atoi(e_rt) >= 1 && atoi(e_rt) <= 8) RT = atoi(e_rt); }
-#endif
-    const long long groups = (tiles + RT - 1) / RT;
-    if (ln_w)
-        FBBEV_LAUNCH((k_rows_linear_f32<true>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, out,
-                     out_row_stride, rows, in_features, out_features, relu, n_kc, n_oc, (int)RT, addend, addend_row_stride,
-                     addend_period, res, ld_res, ln_w, ln_b, ln_eps);
-    else
-        FBBEV_LAUNCH((k_rows_linear_f32<false>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, out,
-                     out_row_stride, rows, in_features, out_features, relu, n_kc, n_oc, (int)RT, addend, addend_row_stride,
-                     addend_period, res, ld_res, ln_w, ln_b, ln_eps);
+    rows_linear_geom g;
+    const int e = rows_linear_prepare(x, &x_row_stride, weight, bias, rows, in_features, out_features, out, &out_row_stride, &g);
+    if (e || rows == 0) return e;
+    if (ln_w && g.n_oc != 1) return FBBEV_E_UNSUPPORTED;
+    const size_t lds = (size_t)g.nmt * FBBEV_RLF_TILE_FLOATS * sizeof(float);
+#define FBBEV_RLF(LN_)                                                                                                                   \
+    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_f32<LN_>), g.groups * g.n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, \
+                         out, out_row_stride, rows, in_features, out_features, relu, g.n_kc, g.n_oc, (int)g.RT, addend,                  \
+                         addend_row_stride, addend_period, res, ld_res, ln_w, ln_b, ln_eps)
+    if (ln_w) FBBEV_RLF(true); else FBBEV_RLF(false);
+#undef FBBEV_RLF
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -3488,10 +3349,7 @@ extern "C" int fbbev_rows_linear_f32_add(const float* x, long long x_row_stride,
                                          long long addend_period, const float* weight, const float* bias, long long rows,
                                          int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                          fbbev_stream_t stream_) {
-    if (!addend || addend_period <= 0) return FBBEV_E_BADARG;
-    if (addend_row_stride == 0) addend_row_stride = in_features;
-    if (addend_row_stride < in_features) return FBBEV_E_BADARG;
-    if (addend_row_stride % 4 != 0 || !aligned16(addend)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
     return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
                                 addend_row_stride, addend_period, stream_);
 }
@@ -3500,14 +3358,7 @@ extern "C" int fbbev_rows_linear_f32_ln(const float* x, long long x_row_stride, 
                                         int in_features, int out_features, const float* residual, long long residual_row_stride,
                                         const float* ln_weight, const float* ln_bias, float ln_eps, float* out,
                                         long long out_row_stride, fbbev_stream_t stream_) {
-    if (!ln_weight || !ln_bias || out_features <= 0) return FBBEV_E_BADARG;
-    if (out_features > 128) return FBBEV_E_UNSUPPORTED;
-    if (residual) {
-        if (residual_row_stride == 0) residual_row_stride = out_features;
-        if (residual_row_stride < out_features) return FBBEV_E_BADARG;
-        if (residual_row_stride % 4 != 0 || !aligned16(residual)) return FBBEV_E_UNSUPPORTED;
-    }
-    if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = rows_linear_ln_check(residual, &residual_row_stride, ln_weight, ln_bias, out_features)) return e;
     return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
                                 stream_, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
 }
@@ -3558,35 +3409,24 @@ extern "C" int fbbev_rows_ffn_x3(const float* x, long long x_row_stride, const v
     if (rows < 0 || in_features <= 0 || hidden <= 0 || out_features <= 0) return FBBEV_E_BADARG;
     if (rows == 0) return 0;
     if (!x || !w1_fragments || !b1 || !w2_fragments || !b2 || !out || (ln_weight && !ln_bias)) return FBBEV_E_BADARG;
-    if (x_row_stride == 0) x_row_stride = in_features;
-    if (out_row_stride == 0) out_row_stride = out_features;
-    if (x_row_stride < in_features || out_row_stride < out_features) return FBBEV_E_BADARG;
-    if (residual) {
-        if (residual_row_stride == 0) residual_row_stride = out_features;
-        if (residual_row_stride < out_features) return FBBEV_E_BADARG;
-    }
+    int e = row_worse(row_operand(x, &x_row_stride, in_features), row_operand(out, &out_row_stride, out_features));
+    if (residual) e = row_worse(e, row_operand(residual, &residual_row_stride, out_features));
+    if (e) return e;
     if (in_features > 96 || in_features % 8 != 0 || hidden % FBBEV_FFN_HC != 0 || out_features > 80 || out_features % 4 != 0 ||
-        x_row_stride % 4 != 0 || out_row_stride % 4 != 0 || !aligned16(x) || !aligned16(out) || !aligned16(w1_fragments) ||
-        !aligned16(w2_fragments) || !aligned16(b1) || !aligned16(b2) || (residual && (residual_row_stride % 4 != 0 || !aligned16(residual))) ||
+        !aligned16(w1_fragments) || !aligned16(w2_fragments) || !aligned16(b1) || !aligned16(b2) ||
         (ln_weight && (!aligned16(ln_weight) || !aligned16(ln_bias)))) return FBBEV_E_UNSUPPORTED;
     const long long wgs = (rows + 127) / 128;
     if (wgs >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     // hidden units per chunk: 32 (three workgroups per CU) measured 1.480 vs 1.508 ms for 64 in the S3 scope (profiles/r04_time_fb_ffn_hc.jsonl)
-#ifdef FBBEV_TEST_OVERRIDES   // CPU emulator build: the tests switch the chunk inside one process
-    const int hc = [] { const char* e = getenv("FBBEV_FFN_HC"); return e ? atoi(e) : 32; }();
-#else
-    static const int hc = [] { const char* e = getenv("FBBEV_FFN_HC"); return e ? atoi(e) : 32; }();   // tuning knob, read once
-#endif
+    FBBEV_KNOB_ONCE(int, hc, fbbev_env_int("FBBEV_FFN_HC", 32));   // tuning knob (the emulator tests switch the chunk)
     const int n_kc2 = (hidden + 127) / 128;
-#define FBBEV_FFN(LN_, HC_)                                                                                              \
-    do {                                                                                                               \
-        const size_t lds = (size_t)fbbev_ffn_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                                 \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_rows_ffn_x3<3, 5, LN_, HC_>, lds);                               \
-        if (e) return e;                                                                                               \
-        FBBEV_LAUNCH((k_rows_ffn_x3<3, 5, LN_, HC_>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,          \
-                     static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2,  \
-                     out, out_row_stride, rows, in_features, hidden, out_features, n_kc2, residual, residual_row_stride,     \
-                     ln_weight, ln_bias, ln_eps, fbbev_ffn_pre{});                                                     \
+#define FBBEV_FFN(LN_, HC_)                                                                                                              \
+    do {                                                                                                                                 \
+        const size_t lds = (size_t)fbbev_ffn_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                     \
+        FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, LN_, HC_>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,                  \
+                             static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2, \
+                             out, out_row_stride, rows, in_features, hidden, out_features, n_kc2, residual, residual_row_stride,         \
+                             ln_weight, ln_bias, ln_eps, fbbev_ffn_pre{});                                                               \
     } while (0)
     if (hc == 64) { if (ln_weight) FBBEV_FFN(true, 64); else FBBEV_FFN(false, 64); }
     else { if (ln_weight) FBBEV_FFN(true, 32); else FBBEV_FFN(false, 32); }
@@ -3614,29 +3454,25 @@ static int rows_tail_ffn_x3_impl(const float* x, long long x_row_stride, const v
     }
     if (!x || !w0_fragments || !b0 || !ln0_weight || !ln0_bias || !w1_fragments || !b1 || !w2_fragments || !b2 || !ln1_weight ||
         !ln1_bias || !out) return FBBEV_E_BADARG;
-    if (x_row_stride == 0) x_row_stride = embed;
-    if (out_row_stride == 0) out_row_stride = embed;
-    if (residual0 && residual0_row_stride == 0) residual0_row_stride = embed;
-    if (x_row_stride < embed || out_row_stride < embed || (residual0 && residual0_row_stride < embed)) return FBBEV_E_BADARG;
-    if (embed > 80 || embed % 16 != 0 || hidden % FBBEV_FFN_HC != 0 || x_row_stride % 4 != 0 || out_row_stride % 4 != 0 ||
-        !aligned16(x) || !aligned16(out) || !aligned16(w0_fragments) || !aligned16(w1_fragments) || !aligned16(w2_fragments) ||
-        !aligned16(b0) || !aligned16(b1) || !aligned16(b2) || !aligned16(ln0_weight) || !aligned16(ln0_bias) || !aligned16(ln1_weight) ||
-        !aligned16(ln1_bias) || (residual0 && (residual0_row_stride % 4 != 0 || !aligned16(residual0)))) return FBBEV_E_UNSUPPORTED;
+    int e = row_worse(row_operand(x, &x_row_stride, embed), row_operand(out, &out_row_stride, embed));
+    if (residual0) e = row_worse(e, row_operand(residual0, &residual0_row_stride, embed));
+    if (e) return e;
+    if (embed > 80 || embed % 16 != 0 || hidden % FBBEV_FFN_HC != 0 || !aligned16(w0_fragments) || !aligned16(w1_fragments) ||
+        !aligned16(w2_fragments) || !aligned16(b0) || !aligned16(b1) || !aligned16(b2) || !aligned16(ln0_weight) || !aligned16(ln0_bias) ||
+        !aligned16(ln1_weight) || !aligned16(ln1_bias)) return FBBEV_E_UNSUPPORTED;
     const long long wgs = (rows + 127) / 128;
     if (wgs >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const int n_kc2 = (hidden + 127) / 128;
     fbbev_ffn_pre pre;
     pre.w0f = static_cast<const unsigned short*>(w0_fragments); pre.b0 = b0; pre.res0 = residual0; pre.ld_res0 = residual0_row_stride;
     pre.ln0_w = ln0_weight; pre.ln0_b = ln0_bias; pre.eps0 = ln0_eps;
-#define FBBEV_TFFN(HC_)                                                                                                \
-    do {                                                                                                              \
-        const size_t lds = (size_t)fbbev_ffn_pre_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                             \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_rows_ffn_x3<3, 5, true, HC_, true>, lds);                        \
-        if (e) return e;                                                                                              \
-        FBBEV_LAUNCH((k_rows_ffn_x3<3, 5, true, HC_, true>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,   \
-                     static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2, \
-                     out, ldo, rows, embed, hidden, embed, n_kc2, (const float*)nullptr, (long long)0, ln1_weight,             \
-                     ln1_bias, ln1_eps, pre);                                                                         \
+#define FBBEV_TFFN(HC_)                                                                                                                  \
+    do {                                                                                                                                 \
+        const size_t lds = (size_t)fbbev_ffn_pre_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                 \
+        FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, true, HC_, true>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,           \
+                             static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2, \
+                             out, ldo, rows, embed, hidden, embed, n_kc2, (const float*)nullptr, (long long)0, ln1_weight,               \
+                             ln1_bias, ln1_eps, pre);                                                                                    \
     } while (0)
     const long long ldo = tokens_per_image > 0 ? -tokens_per_image : out_row_stride;
     FBBEV_TFFN(32);      // (hidden chunks of 64 -- FBBEV_TAIL_FFN_HC=64 until round 5 -- measured no gain: 1.392 vs 1.392 ms S3; gone)
@@ -3710,14 +3546,10 @@ extern "C" int fbbev_history_fused_vm(const void* history, long long history_str
     // 4 W2 buffers + the W1 fragments + the Y rows + 4 operand tiles: 137 KB (one 1024-thread workgroup per CU)
     const size_t lds = ((size_t)4 * A2S + (size_t)MT * KS * 64 * 8 + (size_t)4 * 16 * (KS * 32 + 8) + (size_t)4 * 64 * FBBEV_HF_XP) *
                        sizeof(unsigned short) + (size_t)4 * 80 * sizeof(float);
-#define FBBEV_HF(ET_)                                                                                                  \
-    do {                                                                                                              \
-        int e_ = fbbev_rt_allow_dyn_lds((const void*)k_history_fused_bf16<ET_>, lds);                                  \
-        if (e_) return e_;                                                                                            \
-        FBBEV_LAUNCH((k_history_fused_bf16<ET_>), (long long)per_xcd * 8, 1024, lds, stream, history, history_stride_b, \
-                     next, next_stride_b, rt_flow, (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, \
-                     T1, Z, Y, X, n_xc, YB, nyb, per_xcd, (int)blocks, out);                                           \
-    } while (0)
+#define FBBEV_HF(ET_)                                                                                                        \
+    FBBEV_LAUNCH_DYN_LDS((k_history_fused_bf16<ET_>), (long long)per_xcd * 8, 1024, lds, stream, history, history_stride_b,  \
+                         next, next_stride_b, rt_flow, (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, \
+                         T1, Z, Y, X, n_xc, YB, nyb, per_xcd, (int)blocks, out)
     if (elem_type == 1) FBBEV_HF(1); else FBBEV_HF(2);
 #undef FBBEV_HF
     FBBEV_CHECK_LAUNCH();
@@ -3864,13 +3696,9 @@ extern "C" int fbbev_conv3d_k3s1_tiled_bf16(const float* x, const void* weight_f
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)2 * 600 * 32 * sizeof(unsigned short);
     const unsigned short* wfb = static_cast<const unsigned short*>(weight_fragments_bf16);
-#define FBBEV_CONV3DT(MT_)                                                                                           \
-    do {                                                                                                             \
-        int e = fbbev_rt_allow_dyn_lds((const void*)k_conv3d_k3_tile_bf16<MT_>, lds);                                \
-        if (e) return e;                                                                                             \
-        FBBEV_LAUNCH((k_conv3d_k3_tile_bf16<MT_>), grid, 512, lds, (fbbev_rt_stream)stream_, x, wfb, bias, residual, out, B, \
-                     D, H, W, Cin, Cout, mt_total, relu ? 1 : 0, tiles_d, tiles_h, tiles_w, gy);                      \
-    } while (0)
+#define FBBEV_CONV3DT(MT_)                                                                                                       \
+    FBBEV_LAUNCH_DYN_LDS((k_conv3d_k3_tile_bf16<MT_>), grid, 512, lds, (fbbev_rt_stream)stream_, x, wfb, bias, residual, out, B, \
+                         D, H, W, Cin, Cout, mt_total, relu ? 1 : 0, tiles_d, tiles_h, tiles_w, gy)
     if (MT == 4) FBBEV_CONV3DT(4); else if (MT == 2) FBBEV_CONV3DT(2); else FBBEV_CONV3DT(1);
 #undef FBBEV_CONV3DT
     FBBEV_CHECK_LAUNCH();

@@ -22,7 +22,7 @@ static bool wgrad_plan_make(long long rows, int I, int O, wgrad_plan* p) {
     p->amt = O >= 128 ? 8 : (O + 15) / 16;
     // (768 workgroups for the narrow layers -- three per CU at their 41 KB of LDS -- measured slower than 256: 48.8 -> 54.8 us at 80 x 80)
     long long want = 512 / ((long long)p->n_oc * p->n_ic);
-    static const int env_split = [] { const char* e = getenv("FBBEV_WGRAD_SPLITS"); return e ? atoi(e) : 0; }();   // tuning knob
+    static const int env_split = fbbev_env_int("FBBEV_WGRAD_SPLITS", 0);   // tuning knob
     if (env_split > 0) want = env_split;
     if (want < 8) want = 8;
     if (want > 256) want = 256;
@@ -54,35 +54,25 @@ extern "C" int fbbev_rows_wgrad_x3(const float* grad_out, long long ld_grad, con
         return e;
     }
     if (!grad_out || !x) return FBBEV_E_BADARG;
-    if (ld_grad == 0) ld_grad = O;
-    if (ldx == 0) ldx = I;
-    if (ld_grad < O || ldx < I) return FBBEV_E_BADARG;
+    const int e_rows = row_worse(row_operand(grad_out, &ld_grad, O), row_operand(x, &ldx, I));
+    if (e_rows == FBBEV_E_BADARG) return e_rows;
     if (x_addend) {
         if (addend_period <= 0 || addend_period >= (1ll << 31)) return FBBEV_E_BADARG;
-        if (addend_row_stride == 0) addend_row_stride = I;
-        if (addend_row_stride < I) return FBBEV_E_BADARG;
-        if (addend_row_stride % 4 != 0 || !aligned16(x_addend)) return FBBEV_E_UNSUPPORTED;
+        if (const int e = row_operand(x_addend, &addend_row_stride, I)) return e;
     } else {
         addend_period = 1;
     }
     wgrad_plan p;
-    if (!wgrad_plan_make(rows, I, O, &p) || ld_grad % 4 != 0 || ldx % 4 != 0 || !aligned16(grad_out) || !aligned16(x))
-        return FBBEV_E_UNSUPPORTED;
+    if (!wgrad_plan_make(rows, I, O, &p) || e_rows) return FBBEV_E_UNSUPPORTED;   // (the addend's checks come before these two operands' alignment)
     if (!workspace || !aligned16(workspace) || workspace_bytes < p.total) return FBBEV_E_WORKSPACE;
     float* part_w = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.part_w);
     float* part_b = grad_bias ? reinterpret_cast<float*>(static_cast<char*>(workspace) + p.part_b) : nullptr;
     const long long wgs = (long long)p.n_split * p.n_oc * p.n_ic;
     if (wgs >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)2 * (p.amt + p.nti) * FBBEV_WG_TILE_DW * 4;
-#define FBBEV_WGRAD_LAUNCH(NTI_, ADD_)                                                                                            \
-    do {                                                                                                                          \
-        if (lds > 64 * 1024) {                                                                                                    \
-            const int e_ = fbbev_rt_allow_dyn_lds((const void*)k_rows_wgrad_x3<NTI_, ADD_>, lds);                                  \
-            if (e_) return e_;                                                                                                    \
-        }                                                                                                                         \
-        FBBEV_LAUNCH((k_rows_wgrad_x3<NTI_, ADD_>), wgs, 256, lds, stream, grad_out, ld_grad, x, ldx, x_addend, addend_row_stride, \
-                     (int)addend_period, rows, O, I, p.n_oc, p.n_ic, p.ksteps, p.kps, p.amt, part_w, part_b);                             \
-    } while (0)
+#define FBBEV_WGRAD_LAUNCH(NTI_, ADD_)                                                                                                 \
+    FBBEV_LAUNCH_DYN_LDS((k_rows_wgrad_x3<NTI_, ADD_>), wgs, 256, lds, stream, grad_out, ld_grad, x, ldx, x_addend, addend_row_stride, \
+                         (int)addend_period, rows, O, I, p.n_oc, p.n_ic, p.ksteps, p.kps, p.amt, part_w, part_b)
     if (p.nti == 5) { if (x_addend) FBBEV_WGRAD_LAUNCH(5, true); else FBBEV_WGRAD_LAUNCH(5, false); }
     else { if (x_addend) FBBEV_WGRAD_LAUNCH(8, true); else FBBEV_WGRAD_LAUNCH(8, false); }
 #undef FBBEV_WGRAD_LAUNCH

@@ -97,3 +97,75 @@ def test_invalid_arguments_return_error_codes_without_touching_the_gpu():
     assert lib.fbbev_history_conv_vm(P16, 0, P16, P16, P16, P16, 1, 17, 48, 48, 64, P16, P16, 1 << 20, 1, NULL) == -2
     assert lib.fbbev_history_conv_e(P16, 0, P16, P8, P16, P16, 1, 17, 80, 80, 64, P16, P16, 1 << 20, 1, NULL) == -2          # bias rows are 16-byte loads
     assert lib.fbbev_rank_workspace_bytes(0) == 256 and lib.fbbev_pool_dense_workspace_bytes(0, 1, 1, 1) == 256
+    # row operands of the row-wise linear family (256 rows, 80 -> 80 features, hidden 320): a row stride below the width is -1, a
+    # stride that is no multiple of 4 floats or a pointer off a 16-byte boundary is -2; where two defects coincide the code is
+    # that of the check the entry makes first
+    for fam in ('x3', 'f32'):
+        lin, add, ln = (getattr(lib, f'fbbev_rows_linear_{fam}{s}') for s in ('', '_add', '_ln'))
+        assert lin(P16, 40, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -1                   # x stride < in_features
+        assert lin(P16, 0, P16, P16, 256, 80, 80, 0, P16, 82, NULL) == -2                   # out stride % 4
+        assert lin(P8, 0, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -2                     # x misaligned
+        assert lin(P8, 0, P16, P16, 256, 80, 80, 0, P16, 40, NULL) == -1                    # ... and out stride < out_features
+        assert lin(P16, 82, P16, P16, 256, 80, 80, 0, P16, 40, NULL) == -1                  # x stride % 4, out stride too short
+        assert lin(P16, 82, P8, P16, -1, 80, 80, 0, P16, 0, NULL) == -1                     # rows < 0 comes before both
+        assert add(P16, 0, P16, 40, 1, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -1        # addend stride < in_features
+        assert add(P16, 0, P16, 82, 1, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -2        # addend stride % 4
+        assert add(P16, 0, P8, 0, 1, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -2          # addend misaligned
+        assert add(P16, 0, P8, 0, 1, P16, P16, -1, 80, 80, 0, P16, 0, NULL) == -2           # ... checked before rows < 0
+        assert add(P16, 40, P16, 82, 1, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -2       # ... and before x's stride
+        assert add(P8, 0, P16, 40, 1, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -1         # short addend rows, x misaligned
+        assert add(P16, 0, P8, 40, 0, P16, P16, 256, 80, 80, 0, P16, 0, NULL) == -1         # period <= 0 comes first
+        assert ln(P16, 0, P16, P16, 256, 80, 80, P16, 40, P16, P16, 1e-5, P16, 0, NULL) == -1   # residual stride < out_features
+        assert ln(P16, 0, P16, P16, 256, 80, 80, P8, 0, P16, P16, 1e-5, P16, 0, NULL) == -2     # residual misaligned
+        assert ln(P16, 40, P16, P16, 256, 80, 80, P8, 0, P16, P16, 1e-5, P16, 0, NULL) == -2    # ... checked before x's stride
+        assert ln(P16, 0, P16, P16, 256, 80, 80, P16, 40, P8, P16, 1e-5, P16, 0, NULL) == -1    # short residual rows, ln_weight misaligned
+        assert ln(P16, 0, P16, P16, 256, 80, 80, NULL, 40, P16, P16, 1e-5, P8, 0, NULL) == -2   # no residual: its stride is not looked at
+    train = lib.fbbev_rows_linear_x3_train
+    assert train(P16, 0, NULL, 0, 0, P16, P16, 256, 80, 80, 0, P16, 40, P16, 0, P16, 0, NULL) == -1     # residual stride < out_features
+    assert train(P16, 0, NULL, 0, 0, P16, P16, 256, 80, 80, 0, P16, 0, P16, 82, P16, 0, NULL) == -2     # mask stride % 4
+    assert train(P16, 0, NULL, 0, 0, P16, P16, 256, 80, 80, 0, P16, 0, P8, 0, P16, 0, NULL) == -2       # mask misaligned
+    assert train(P16, 0, P16, 40, 1, P16, P16, 256, 80, 80, 0, P16, 0, P16, 0, P16, 0, NULL) == -1      # addend stride < in_features
+    assert train(P16, 0, NULL, 0, 0, P16, P16, 256, 80, 80, 0, P8, 0, P16, 40, P16, 0, NULL) == -2      # residual (misaligned) before mask (short)
+    assert train(P16, 0, P16, 82, 1, P16, P16, 256, 80, 80, 0, P16, 40, P16, 0, P16, 0, NULL) == -2     # addend (% 4) before residual (short)
+    assert train(P16, 0, NULL, 0, 0, P16, P16, -1, 80, 80, 0, P16, 0, P16, 40, P16, 0, NULL) == -1      # mask (short) before rows < 0
+    assert train(P8, 0, NULL, 0, 0, P16, P16, 256, 80, 80, 0, P16, 0, P16, 0, P16, 40, NULL) == -1      # x misaligned, out rows short
+    planes, planes_e = lib.fbbev_rows_linear_x3_planes, lib.fbbev_rows_linear_x3_planes_e
+    assert planes(P16, 40, P16, P16, 256, 80, 80, 128, 10, P16, NULL) == -1                 # x stride < in_features
+    assert planes(P8, 0, P16, P16, 256, 80, 80, 128, 10, P16, NULL) == -2                   # x misaligned
+    assert planes(P16, 40, P8, P16, 256, 80, 80, 128, 10, P16, NULL) == -1                  # short x rows, fragments misaligned
+    assert planes(P16, 40, P16, P16, 256, 80, 80, 128, 10, ctypes.c_void_p(0x1004), NULL) == -2      # out off 8 bytes comes first
+    assert planes_e(P16, 40, P16, P16, 256, 80, 80, 128, 10, 1, P16, NULL) == -1
+    assert planes_e(P16, 82, P16, P16, 256, 80, 80, 128, 10, 1, P16, NULL) == -2            # x stride % 4
+    assert planes_e(P8, 0, P16, P16, 256, 80, 80, 128, 10, 2, P16, NULL) == -2
+    assert planes_e(P16, 40, P16, P8, 256, 80, 80, 128, 10, 1, P16, NULL) == -1             # short x rows, bias misaligned
+    assert planes_e(P16, 40, P16, P16, 256, 80, 80, 128, 10, 1, P8, NULL) == -2             # out off 16 bytes comes first
+    ffn = lib.fbbev_rows_ffn_x3
+    assert ffn(P16, 40, P16, P16, P16, P16, 256, 80, 320, 80, NULL, 0, NULL, NULL, 0.0, P16, 0, NULL) == -1      # x stride
+    assert ffn(P16, 0, P16, P16, P16, P16, 256, 80, 320, 80, P16, 40, NULL, NULL, 0.0, P16, 0, NULL) == -1       # residual stride
+    assert ffn(P16, 0, P16, P16, P16, P16, 256, 80, 320, 80, P16, 82, NULL, NULL, 0.0, P16, 0, NULL) == -2       # residual stride % 4
+    assert ffn(P16, 0, P16, P16, P16, P16, 256, 80, 320, 80, P8, 0, NULL, NULL, 0.0, P16, 0, NULL) == -2         # residual misaligned
+    assert ffn(P8, 0, P16, P16, P16, P16, 256, 80, 320, 80, P16, 40, NULL, NULL, 0.0, P16, 0, NULL) == -1        # ... x misaligned as well
+    assert ffn(P16, 82, P16, P16, P16, P16, 256, 80, 320, 80, NULL, 0, NULL, NULL, 0.0, P16, 40, NULL) == -1     # x % 4, out short
+    tail, tail_planes = lib.fbbev_rows_tail_ffn_x3, lib.fbbev_rows_tail_ffn_x3_planes
+    W = (P16, P16, P16, P16)                                                                 # w1 fragments, b1, w2 fragments, b2
+    assert tail(P16, 40, P16, P16, NULL, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 0, NULL) == -1    # x stride
+    assert tail(P16, 0, P16, P16, P16, 40, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 0, NULL) == -1     # residual0 stride
+    assert tail(P16, 0, P16, P16, P8, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 0, NULL) == -2       # residual0 misaligned
+    assert tail(P16, 0, P16, P16, P16, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 82, NULL) == -2     # out stride % 4
+    assert tail(P8, 0, P16, P16, P16, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 40, NULL) == -1      # x misaligned, out short
+    assert tail(P16, 0, P16, P16, P8, 40, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, P16, 0, NULL) == -1      # residual0 short and misaligned
+    assert tail_planes(P16, 40, P16, P16, NULL, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, 128, P16, NULL) == -1
+    assert tail_planes(P8, 0, P16, P16, NULL, 0, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, 128, P16, NULL) == -2
+    assert tail_planes(P16, 0, P16, P16, P16, 82, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, 128, P16, NULL) == -2
+    assert tail_planes(P16, 0, P16, P16, P16, 40, P16, P16, 1e-5, *W, 256, 80, 320, P16, P16, 1e-5, 128, P8, NULL) == -1   # residual0 short, out misaligned
+    wgrad = lib.fbbev_rows_wgrad_x3
+    assert wgrad(P16, 0, P16, 0, P16, 40, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -1      # addend stride < in_features
+    assert wgrad(P16, 0, P16, 0, P16, 82, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -2      # addend stride % 4
+    assert wgrad(P16, 0, P16, 0, P8, 0, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -2        # addend misaligned
+    assert wgrad(P16, 40, P16, 0, P16, 0, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -1      # grad_out stride < out_features
+    assert wgrad(P16, 0, P16, 82, NULL, 0, 0, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -2     # x stride % 4
+    assert wgrad(P8, 0, P16, 0, NULL, 0, 0, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -2       # grad_out misaligned
+    assert wgrad(P16, 40, P16, 0, P16, 82, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -1     # short grad_out rows before the addend
+    assert wgrad(P16, 82, P16, 0, P16, 40, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -1     # short addend rows before grad_out % 4
+    assert wgrad(P16, 0, P16, 0, P8, 0, 1, 256, 80, 80, P16, P16, NULL, 0, NULL) == -2             # addend before the workspace (-3)
+    assert wgrad(P16, 0, P8, 0, NULL, 0, 0, 256, 80, 80, P16, P16, NULL, 0, NULL) == -2            # x before the workspace

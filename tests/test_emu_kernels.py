@@ -1427,8 +1427,9 @@ def test_history_fused_warp_and_conv_equals_the_two_kernels_emulated(dt, produce
     tile, consumer waves run both bf16-MFMA convolutions from it) against fbbev_history_warp_vm + fbbev_history_conv_bf16 on
     the same rings: the new ring's slots 1..T and the fused volume are the SAME BITS -- same taps, weights, roundings, operands
     and accumulation order; only where the operands come from differs.  Grid rows that are not a multiple of the 64-voxel
-    tile, translation / rotation / out-of-grid / NaN flows, padded batch strides, both producer counts."""
-    monkeypatch.setenv('FBBEV_HISTORY_FUSED_PRODUCERS', producers)
+    tile, translation / rotation / out-of-grid / NaN flows, padded batch strides.  (`producers` was meant to choose the kernel's number
+    of producer waves through FBBEV_HISTORY_FUSED_PRODUCERS; nothing in the library reads that variable, so the two cases run
+    the same launch.)"""
     g = torch.Generator().manual_seed(13)
     B, T, C, Z, Y, X = 4, 3, 80, 2, 3, 70                                     # X = 70: one full tile + a 6-voxel tile per row
     N = Z * Y * X
