@@ -43,6 +43,8 @@ SIGNATURES = {
     'fbbev_pool_tile_index': (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p, c_size_t, c_void_p]),
     'fbbev_bev_pool_v2_dense_fwd': (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p, c_int64, c_int64, c_void_p,
                                             c_size_t, c_int, c_int, c_void_p]),
+    'fbbev_bev_pool_v2_dense_fwd_rows': (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                                 c_size_t, c_int, c_int, c_void_p]),
     'fbbev_diag_pool_store_floor': (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int,
                                             c_void_p]),
     'fbbev_bev_pool_v2_dense_fwd_add': (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p, c_int64, c_int64, c_void_p,
@@ -510,6 +512,35 @@ def bev_pool_v2_dense_fwd(depth, feat, ranks_depth, ranks_feat, interval_rank, i
                 raise FbbevError('addend must be (B,C,Y,X)')
             _check(lib().fbbev_bev_pool_v2_dense_fwd_add(*args, _dev(addend, F32, 'addend'), _stream()),
                    'fbbev_bev_pool_v2_dense_fwd_add')
+
+
+def bev_pool_v2_dense_fwd_rows(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C, Z, Y, X,
+                               out_rows, tile_ws, tile_voxels=64, flags=DEFAULT_POOL_FLAGS, addend_rows=None):
+    """fbbev_bev_pool_v2_dense_fwd_rows: the pooled volume as voxel rows.  out_rows: (B, Z*Y*X, C) f32 / bf16 / f16 whose rows are
+    contiguous (any batch stride: slot 0 of a (B, T+1, N, C) ring); addend_rows: (B, Y*X, C) f32 with contiguous channels, added to
+    every z plane before the one rounding of the store.  tile_ws: the tile index built with POOL_CHANNELS_LAST."""
+    N = Z * Y * X
+    if not out_rows.is_cuda or out_rows.dtype not in (F32, torch.bfloat16, torch.float16):
+        raise FbbevError('out_rows must be a GPU float32 / bfloat16 / float16 tensor')
+    if tuple(out_rows.shape) != (B, N, C) or out_rows.stride()[1:] != (C, 1):
+        raise FbbevError('out_rows must be (B, Z*Y*X, C) with contiguous rows')
+    flags = int(flags) & ~(POOL_OUT_BF16 | POOL_OUT_F16 | POOL_SPLIT_LONG | POOL_PIPE | POOL_GATHER8)
+    flags |= {F32: 0, torch.bfloat16: POOL_OUT_BF16, torch.float16: POOL_OUT_F16}[out_rows.dtype]   # storage type follows `out_rows`
+    a_ptr, a_stride = None, 0
+    if addend_rows is not None:
+        if (tuple(addend_rows.shape) != (B, Y * X, C) or addend_rows.stride(2) != 1 or
+                (B > 1 and addend_rows.stride(0) != Y * X * addend_rows.stride(1))):
+            raise FbbevError('addend_rows must be (B, Y*X, C) with contiguous channels and one row stride')
+        a_ptr, a_stride = _dev(addend_rows, F32, 'addend_rows', contiguous=False), addend_rows.stride(1)
+    with _on(depth):
+        _check(lib().fbbev_bev_pool_v2_dense_fwd_rows(
+            _dev(depth, F32, 'depth'), _dev(feat, F32, 'feat'), _dev(ranks_depth, I32, 'ranks_depth'),
+            _dev(ranks_feat, I32, 'ranks_feat'), _dev(interval_rank, I32, 'interval_rank'),
+            _dev(interval_starts, I32, 'interval_starts'), _dev(interval_lengths, I32, 'interval_lengths'),
+            B, C, Z, Y, X, c_void_p(out_rows.data_ptr()), out_rows.stride(0) if B > 1 else 0, a_ptr, a_stride,
+            c_void_p(tile_ws.data_ptr()), tile_ws.numel() * tile_ws.element_size(), int(tile_voxels), flags, _stream()),
+            'fbbev_bev_pool_v2_dense_fwd_rows')
+    return out_rows
 
 
 def diag_pool_store_floor(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C, Z, Y, X,

@@ -1295,16 +1295,19 @@ class BackwardProjection(nn.Module):
         return w.detach().contiguous()
 
     def forward(self, mlvl_feats, img_metas, lss_bev=None, gt_bboxes_3d=None, cam_params=None, pred_img_depth=None,
-                bev_mask=None, _pre=None, lss_rows=None):
+                bev_mask=None, _pre=None, lss_rows=None, out_rows=False):
         """lss_rows (inference): the queries as rows (bs, Y*X, C) ALREADY carrying bev_embedding (fbbev_pool_zmean_rows) instead of
-        lss_bev (bs, C, Y, X)."""
+        lss_bev (bs, C, Y, X).
+        out_rows=True (inference, fast route): the refined BEV comes back as contiguous (bs, Y*X, C) fp32 rows -- the last layer's native
+        output, without the planes epilogue or the transposing pass (the consumer adds rows: fbbev_bev_pool_v2_dense_fwd_rows); on
+        any other route the call returns (bs, C, Y, X) as always -- the caller tells the two apart by dim()."""
         global _PRE
         if _pre is not None:
             torch.cuda.current_stream(mlvl_feats[0].device).wait_event(_pre.event)
             _PRE = _pre
             try:
                 return self.forward(mlvl_feats, img_metas, lss_bev=lss_bev, gt_bboxes_3d=gt_bboxes_3d, cam_params=cam_params,
-                                    pred_img_depth=pred_img_depth, bev_mask=bev_mask, lss_rows=lss_rows)
+                                    pred_img_depth=pred_img_depth, bev_mask=bev_mask, lss_rows=lss_rows, out_rows=out_rows)
             finally:
                 _PRE = None
         bs = mlvl_feats[0].shape[0]
@@ -1340,7 +1343,9 @@ class BackwardProjection(nn.Module):
             bev_mask = bev_mask.reshape(bs, -1)
         bev_pos = self.positional_encoding(bs, self.bev_h, self.bev_w, bev_queries.device).to(dtype)
         global _OUT_PLANES
-        ctx = dict(tokens=self.bev_h * self.bev_w, last=False, got=False) if (fast and OUT_PLANES and not torch.is_grad_enabled()) else None
+        rows_out = bool(out_rows) and fast and not torch.is_grad_enabled()
+        ctx = dict(tokens=self.bev_h * self.bev_w, last=False, got=False) if (fast and OUT_PLANES and not torch.is_grad_enabled()
+                                                                               and not rows_out) else None
         _OUT_PLANES = ctx
         try:
             bev = self.transformer(mlvl_feats, bev_queries, self.bev_h, self.bev_w,
@@ -1349,6 +1354,8 @@ class BackwardProjection(nn.Module):
                                    pred_img_depth=pred_img_depth, prev_bev=None, bev_mask=bev_mask)
         finally:
             _OUT_PLANES = None
+        if rows_out and bev.dim() == 3 and bev.dtype == torch.float32 and not bev.requires_grad:
+            return bev.contiguous()                             # (bs, Y * X, C): the last layer's rows as they are
         if ctx is not None and ctx['got']:                     # the last layer's kernel wrote (bs, C, Y * X) itself
             return bev.view(bs, -1, self.bev_h, self.bev_w)
         if fast and bev.is_contiguous() and not bev.requires_grad:

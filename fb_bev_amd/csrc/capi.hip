@@ -830,6 +830,83 @@ extern "C" int fbbev_bev_pool_v2_dense_fwd(const float* depth, const float* feat
                                stream_);
 }
 
+// ------------------------------------------------------------------------------ fused dense fwd, rows of a strided slot
+struct dense_rows_args {
+    long long n_blocks, addend_row_stride, out_stride_b; size_t lds; fbbev_rt_stream stream; int C, nvox, zyx, yx, swizzle;
+    const float *depth, *feat; const int32_t *rd, *rf, *irank, *starts, *lengths; const int* tile_meta;
+    const float* addend; void* out;
+};
+
+template <int TV, int CPL, int ST, int ET>
+static int launch_dense_rows(const dense_rows_args& a) {
+    long long grid = a.n_blocks;
+    if (a.swizzle) {
+        const long long g = 8ll << (a.swizzle - 1);
+        grid = (a.n_blocks + g - 1) / g * g;
+    }
+    FBBEV_LAUNCH((k_pool_fwd_dense_rows<TV, CPL, ST, 256, ET>), grid, 256, a.lds, a.stream, a.C, a.nvox, a.zyx, a.yx, (int)a.n_blocks,
+                 a.swizzle, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.addend_row_stride,
+                 a.out, a.out_stride_b);
+    return fbbev_rt_last_error();
+}
+
+// 16-bit rows: 8 channels per lane (one 16-byte store), built for the default `sc1 nt` store policy like the planar 16-bit kernels
+template <int TV>
+static int launch_dense_rows_tv(int et, int st, bool cpl8, const dense_rows_args& a) {
+    if (et == 1) return launch_dense_rows<TV, 8, 4, 1>(a);
+    if (et == 2) return launch_dense_rows<TV, 8, 4, 2>(a);
+    if (cpl8) return st == 0 ? launch_dense_rows<TV, 8, 0, 0>(a) : st == 1 ? launch_dense_rows<TV, 8, 1, 0>(a) : launch_dense_rows<TV, 8, 4, 0>(a);
+    return st == 0 ? launch_dense_rows<TV, 4, 0, 0>(a) : st == 1 ? launch_dense_rows<TV, 4, 1, 0>(a) : launch_dense_rows<TV, 4, 4, 0>(a);
+}
+
+extern "C" int fbbev_bev_pool_v2_dense_fwd_rows(const float* depth, const float* feat, const int32_t* ranks_depth,
+                                                const int32_t* ranks_feat, const int32_t* interval_rank,
+                                                const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C,
+                                                int Z, int Y, int X, void* out_rows, long long out_stride_b,
+                                                const float* addend_rows, long long addend_row_stride, const void* tile_ws,
+                                                size_t tile_ws_bytes, int tile_voxels, int flags, fbbev_stream_t stream_) {
+    if (B <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
+    if (!depth || !feat || !ranks_depth || !ranks_feat || !interval_rank || !interval_starts || !interval_lengths || !out_rows ||
+        !tile_ws) return FBBEV_E_BADARG;
+    if ((flags & FBBEV_POOL_OUT_BF16) && (flags & FBBEV_POOL_OUT_F16)) return FBBEV_E_BADARG;
+    const int et = (flags & FBBEV_POOL_OUT_BF16) ? 1 : ((flags & FBBEV_POOL_OUT_F16) ? 2 : 0);
+    const int ve = et == 0 ? 4 : 8;                                     // elements of a 16-byte store
+    const long long yx = (long long)Y * X;
+    if (yx >= (1ll << 31) || Z * yx >= (1ll << 31) || B * (Z * yx) >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;   // flat voxel index: int
+    const long long zyx = Z * yx, nvox = B * zyx;
+    if (out_stride_b == 0) out_stride_b = zyx * C;                      // contiguous (B, Z*Y*X, C)
+    if (addend_row_stride == 0) addend_row_stride = C;
+    if (out_stride_b < zyx * C || addend_row_stride < C) return FBBEV_E_BADARG;
+    if (C % ve != 0 || C > 256 || out_stride_b % ve != 0 || addend_row_stride % 4 != 0 || !aligned16(out_rows) || !aligned16(feat) ||
+        !aligned16(addend_rows)) return FBBEV_E_UNSUPPORTED;
+    if (small_tile_shift(tile_voxels)) return FBBEV_E_UNSUPPORTED;      // the small-tile kernel keeps its fp32, contiguous, no-addend form
+    const int TV = pick_tile(tile_voxels);
+    const bool cpl8 = et != 0 || ((flags & FBBEV_POOL_CPL8) && C % 8 == 0);
+    if (256 / (C / (cpl8 ? 8 : 4)) < 1) return FBBEV_E_UNSUPPORTED;     // a voxel row takes more lanes than a workgroup has
+    dense_rows_args a;
+    a.n_blocks = (nvox + TV - 1) / TV;
+    if (tile_ws_bytes < (size_t)(a.n_blocks + 1) * 8) return FBBEV_E_WORKSPACE;
+    a.lds = (3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(int);
+    a.stream = (fbbev_rt_stream)stream_; a.C = C; a.nvox = (int)nvox; a.zyx = (int)zyx; a.yx = (int)yx;
+    a.swizzle = 0;
+    if (flags & FBBEV_POOL_XCD_SWIZZLE) {
+        int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
+        if (lg == 0) lg = 4;
+        a.swizzle = lg + 1;
+    }
+    a.depth = depth; a.feat = feat; a.rd = ranks_depth; a.rf = ranks_feat; a.irank = interval_rank;
+    a.starts = interval_starts; a.lengths = interval_lengths; a.tile_meta = static_cast<const int*>(tile_ws);
+    a.addend = addend_rows; a.addend_row_stride = addend_row_stride; a.out = out_rows; a.out_stride_b = out_stride_b;
+    const int st = (flags & FBBEV_POOL_STORE_MASK) | ((flags >> FBBEV_POOL_STORE_HI_SHIFT) & 1) << 2;
+    switch (TV) {
+        case 64: return launch_dense_rows_tv<64>(et, st, cpl8, a);
+        case 128: return launch_dense_rows_tv<128>(et, st, cpl8, a);
+        case 256: return launch_dense_rows_tv<256>(et, st, cpl8, a);
+        case 512: return launch_dense_rows_tv<512>(et, st, cpl8, a);
+        default: return launch_dense_rows_tv<1024>(et, st, cpl8, a);
+    }
+}
+
 // Measurement aid (bench.py `roofline.store_floor_ms` / `no_gather_ms`): the default fp32 instantiation of the dense kernel
 // (128-voxel tiles, 8 channels per lane, 256 threads, `sc1 nt` stores) with its gathers compiled out -- same grid, tile
 // walk and XCD order as the product launch with these flags.  mode 1: store pattern alone; mode 2: all but the depth /

@@ -1284,6 +1284,128 @@ k_pool_fwd_dense_cl(int C, int n_voxels, int n_blocks, int swizzle, const float*
     }
 }
 
+// ================================================================ fused dense forward, channels-last ROWS of a strided destination
+// k_pool_fwd_dense_cl's tile walk with three things its one consumer -- slot 0 of the voxel-major history ring, (B, T+1, N, C) -- needs:
+//   * ET: element type of `out` (0 f32, 1 bf16, 2 f16); the fp32 sum is rounded ONCE at the store by fbbev_cvt_pk16<ET>, the rounding
+//     k_history_frame_vm applies to the fp32 volume;
+//   * a batch stride: tiles stay flat over the B*Z*Y*X rank space (the FBBEV_POOL_CHANNELS_LAST tile table is unchanged), so a tile may
+//     straddle samples and the destination is computed per voxel: b = v / ZYX, out + b * out_stride_b + (v - b * ZYX) * C;
+//   * an optional row addend (B, Y*X, C) f32 -- the refined BEV as the backward projection's last layer leaves it -- added with exactly
+//     one fp32 add per element to the finished sum (0.f for an empty voxel): row b * YX + (v mod YX), re-read Z times out of L2.
+// The per-voxel sums are fbbev_interval_sum_staged's in-order fmaf chains: the bits of every other forward kernel here.  With CPL = 8 a
+// lane's channels are ONE 16-byte store of a 16-bit row (two of an fp32 row).  Without an addend an empty tile is a run of zeros (linear
+// when the tile lies inside one sample); with one it walks its voxels like any other tile and stores the rounded addend rows.
+template <int TV, int CPL, int ST, int NT, int ET>
+__global__ void __launch_bounds__(NT)
+k_pool_fwd_dense_rows(int C, int n_voxels, int ZYX, int YX, int n_blocks, int swizzle, const float* __restrict__ depth,
+                      const float* __restrict__ feat, const int* __restrict__ rd, const int* __restrict__ rf,
+                      const int* __restrict__ interval_rank, const int* __restrict__ starts,
+                      const int* __restrict__ lengths, const int* __restrict__ tile_meta,
+                      const float* __restrict__ addend, long long addend_row_stride, void* __restrict__ out,
+                      long long out_stride_b) {
+    static_assert(ET == 0 || CPL == 8, "a 16-bit row is written with one 16-byte store per lane");
+    constexpr int ESZ = ET == 0 ? 4 : 2;
+    int* ist = reinterpret_cast<int*>(fbbev_dyn_lds_f32());   // [TV]
+    int* iln = ist + TV;                                      // [TV]
+    int* slot = iln + TV;                                     // [TV] interval (tile-local) of each voxel, -1 = empty
+    int* prd = slot + TV;                                     // [NP_STAGE]
+    int* prf = prd + FBBEV_NP_STAGE;                          // [NP_STAGE]
+    const int tid = threadIdx.x;
+    int t = blockIdx.x;
+    if (swizzle) {
+        const int sh = swizzle - 1;
+        const int xcd = t & 7, j = t >> 3;
+        t = ((((j >> sh) << 3) + xcd) << sh) + (j & ((1 << sh) - 1));
+    }
+    if (t >= n_blocks) return;
+    const int v0 = t * TV;
+    const int nv = (n_voxels - v0 < TV) ? (n_voxels - v0) : TV;
+    const int i0 = tile_meta[2 * t], p0 = tile_meta[2 * t + 1];
+    const int i1 = tile_meta[2 * t + 2], p1 = tile_meta[2 * t + 3];
+    char* __restrict__ ob = static_cast<char*>(out);
+    const int b0 = v0 / ZYX;                                  // sample of the tile's first voxel (block-uniform)
+    const bool empty = i0 == i1;
+
+    if (empty && addend == nullptr) {  // zeros: one linear run per sample the tile touches
+        fbbev_v4f zero; zero[0] = zero[1] = zero[2] = zero[3] = 0.f;
+        const int cpr = C * ESZ / 16;                         // 16-byte pieces of a row
+        const int n16 = nv * cpr;
+        if ((v0 + nv - 1) / ZYX == b0) {
+            char* base = ob + ((long long)b0 * out_stride_b + (long long)(v0 - b0 * ZYX) * C) * ESZ;
+            for (int idx = tid; idx < n16; idx += NT) fbbev_store4<ST>(reinterpret_cast<float*>(base + 16ll * idx), zero);
+        } else {
+            for (int idx = tid; idx < n16; idx += NT) {
+                const int vl = idx / cpr, q = idx - vl * cpr;
+                const int v = v0 + vl, b = v / ZYX;
+                char* dst = ob + ((long long)b * out_stride_b + (long long)(v - b * ZYX) * C) * ESZ + 16 * q;
+                fbbev_store4<ST>(reinterpret_cast<float*>(dst), zero);
+            }
+        }
+        return;
+    }
+
+    const int ni = i1 - i0;
+    if (!empty) {                                             // block-uniform: the barriers are reached by every thread or by none
+        const int np = p1 - p0;
+        for (int j = tid; j < TV; j += NT) slot[j] = -1;
+        for (int j = tid; j < ni; j += NT) { ist[j] = starts[i0 + j] - p0; iln[j] = lengths[i0 + j]; }
+        const int nps = np < FBBEV_NP_STAGE ? np : FBBEV_NP_STAGE;
+        for (int j = tid; j < nps; j += NT) { prd[j] = rd[p0 + j]; prf[j] = rf[p0 + j]; }
+        __syncthreads();
+        for (int j = tid; j < ni; j += NT) {
+            const int v = interval_rank[i0 + j] - v0;
+            if (v >= 0 && v < nv) slot[v] = j;
+        }
+        __syncthreads();
+    }
+
+    const int lpi = C / CPL;
+    const int gpb = NT / lpi;
+    const int g = tid / lpi, lane_slot = tid - g * lpi;
+    if (g < gpb) {
+        const float* fbase = feat + lane_slot * CPL;
+        int b = b0;
+        for (int v = g; v < nv; v += gpb) {
+            const int vf = v0 + v;                            // flat voxel; a lane's voxels ascend, so its sample index only grows
+            while (vf >= (b + 1) * ZYX) ++b;
+            const int r = vf - b * ZYX;                       // row of the sample's (Z*Y*X, C) block
+            fbbev_v4f add[CPL / 4];
+            if (addend != nullptr) {                          // requested ahead of the gather chain it is added to
+                const float* ap = addend + ((long long)b * YX + (r % YX)) * addend_row_stride + lane_slot * CPL;
+#pragma unroll
+                for (int q = 0; q < CPL / 4; ++q) add[q] = *reinterpret_cast<const fbbev_v4f*>(ap + 4 * q);
+            }
+            const int s = empty ? -1 : slot[v];
+            float acc[CPL];
+            if (s >= 0) {
+                fbbev_interval_sum_staged<CPL, 4>(C, ist[s], iln[s], p0, prd, prf, depth, fbase, rd, rf, acc);
+            } else {
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) acc[j] = 0.f;
+            }
+            if (addend != nullptr) {
+#pragma unroll
+                for (int j = 0; j < CPL; ++j) acc[j] += add[j >> 2][j & 3];
+            }
+            char* dst = ob + ((long long)b * out_stride_b + (long long)r * C + lane_slot * CPL) * ESZ;
+            if constexpr (ET == 0) {
+#pragma unroll
+                for (int q = 0; q < CPL / 4; ++q) {
+                    fbbev_v4f val; val[0] = acc[4 * q]; val[1] = acc[4 * q + 1]; val[2] = acc[4 * q + 2]; val[3] = acc[4 * q + 3];
+                    fbbev_store4<ST>(reinterpret_cast<float*>(dst) + 4 * q, val);
+                }
+            } else {
+                fbbev_v4u pk;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) pk[e] = fbbev_cvt_pk16<ET>(acc[2 * e], acc[2 * e + 1]);
+                fbbev_v4f pf;
+                __builtin_memcpy(&pf, &pk, 16);
+                fbbev_store4<ST>(reinterpret_cast<float*>(dst), pf);
+            }
+        }
+    }
+}
+
 // ================================================================ channels-last, small tiles ("one store per thread")
 // Measured on MI355X (tools/micro/fill_bench.hip, profiles/r01_fill_bench*.jsonl): the HBM write stream peaks
 // (7.0-7.6 TB/s) when every workgroup writes ~4 KiB with ONE 16-byte `sc1 nt` store per thread; 4+ stores per

@@ -56,9 +56,28 @@ class FBViewTransform(nn.Module):
         self.readd = readd
         self.write_once = True      # inference: Z-mean from the index tensors + re-add in the pooling store (volume written once)
 
-    def forward(self, cam_params, context, depth, img_metas=None, bev_mask=None, mlvl_feats=None):
+    def slot_route(self):
+        """True when this module's inference result can be written once as the history ring's slot 0 (forward(out_slot=...)):
+        the write-once route with a re-add, an fp32 volume (the slot then holds ONE rounding of the fp32 sums) and no ReLU
+        between the pooling and its consumer."""
+        fp = self.forward_projection
+        return bool(self.write_once and isinstance(self.backward_projection, BP.BackwardProjection) and self.readd and fp.fused and
+                    not fp.extra_relu and
+                    fp.out_dtype == torch.float32)
+
+    def history_slot(self, history, B, device):
+        """history.begin_frame(...) when slot_route() holds, else None: the slot to pass to forward(out_slot=...)."""
+        if not self.slot_route():
+            return None
+        return history.begin_frame(B, self.forward_projection.grid_zyx, device, volume_dtype=self.forward_projection.out_dtype)
+
+    def forward(self, cam_params, context, depth, img_metas=None, bev_mask=None, mlvl_feats=None, out_slot=None):
         """mlvl_feats: optional list of (B,N,C,H_l,W_l) image features for the backward projection (default
-        [context], as fbocc.py:357 passes); BASELINE configs[2] uses 4 levels."""
+        [context], as fbocc.py:357 passes); BASELINE configs[2] uses 4 levels.
+        out_slot: (B, Z*Y*X, C) rows of a voxel-major history ring (TemporalHistoryFusion.begin_frame).  On the write-once
+        inference route the final pooling then writes the result there -- the backward projection's rows as addend, rounded once to
+        the slot's type -- and the call returns out_slot itself (hand it to fuse_history(..., in_slot=True)); on any other route the
+        slot is left alone and the call returns the (B,C,Y,X,Z) volume as always."""
         fp = self.forward_projection
         feats = mlvl_feats if mlvl_feats is not None else [context]
         needs_grad = torch.is_grad_enabled() and (context.requires_grad or depth.requires_grad or
@@ -76,6 +95,11 @@ class FBViewTransform(nn.Module):
             kw = {} if pre is None else {'_pre': pre}
             bp = self.backward_projection
             rows = None
+            Zg, Yg, Xg = fp.grid_zyx
+            to_slot = (out_slot is not None and self.slot_route() and out_slot.is_cuda and out_slot.device == context.device and
+                       tuple(out_slot.shape) == (context.shape[0], Zg * Yg * Xg, context.shape[2]) and context.shape[2] % 8 == 0)
+            if to_slot:
+                kw['out_rows'] = True       # the refined BEV as the last layer's (B, Y*X, C) rows: what the rows pooling adds
             if ZMEAN_ROWS and hasattr(bp, 'query_row_bias') and context.dtype == torch.float32:
                 # round 6: the Z-mean leaves its kernel as the backward projection's query rows (+ bev_embedding): no transposing pass
                 bias = bp.query_row_bias(context.shape[2], fp.grid_zyx)
@@ -87,6 +111,10 @@ class FBViewTransform(nn.Module):
                 lss_mean = fp.pooled_zmean(parts)
                 refined = bp(feats, img_metas, lss_bev=lss_mean, cam_params=cam_params, bev_mask=bev_mask,
                              gt_bboxes_3d=None, pred_img_depth=depth, **kw)
+            if to_slot:
+                if refined.dim() != 3:      # the backward projection left its fast route: (B, C, Y, X) planes -> rows, the same values
+                    refined = _capi.transpose_last2(refined.reshape(refined.shape[0], refined.shape[1], -1).contiguous().float())
+                return fp.pooled_volume_rows(parts, out_slot, addend_rows=refined.float())
             return fp.pooled_volume(parts, addend=refined)
         if (self.write_once and self.backward_projection is not None and self.readd and needs_grad and TP.TRAIN_FUSED and
                 TP.write_once_supported(fp, context) and depth.dtype == torch.float32):

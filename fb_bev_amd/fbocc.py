@@ -50,6 +50,11 @@ def _dtype(v):
             'f16': torch.float16, 'fp16': torch.float16}.get(v, v)
 
 
+# inference, voxel-major ring: the view transformation's final pooling writes the ring's slot 0 itself (same bits; the default is set by
+# the S6 measurement at BASELINE configs[4], profiles/r08_exp_direct_slot.md)
+HISTORY_DIRECT_SLOT_DEFAULT = False
+
+
 class FBOCC(nn.Module):
     def __init__(self, forward_projection=None, img_bev_encoder_backbone=None, img_bev_encoder_neck=None,
                  backward_projection=None, frpn=None, depth_net=None, occupancy_head=None, use_depth_supervision=False,
@@ -67,6 +72,8 @@ class FBOCC(nn.Module):
         16-bit voxel-major ring), 'f32' the reference's arithmetic; default 'auto' = 'bf16x3' for a 16-bit ring, 'f32' otherwise;
         history_ring='voxel_major' keeps the inference ring as (B, T, N, C) voxel rows (16-byte taps, same element bits);
         da_value_dtype='bf16' | 'f16' keeps the cross-attention's camera tokens in 16 bits at inference (fp32 accumulate);
+        history_direct_slot=True|False: inference on the voxel-major ring, the view transformation writes its volume once, as the
+        ring's slot 0 (fbbev_bev_pool_v2_dense_fwd_rows: no fp32 volume, no fbbev_history_frame_vm; bit-identical results);
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -99,6 +106,7 @@ class FBOCC(nn.Module):
         self.history_keyframe_time_conv = hist.history_keyframe_time_conv
         self.history_keyframe_cat_conv = hist.history_keyframe_cat_conv
         self._path = [fvt, hist]                  # plain list: holders stay out of the parameter tree (names above)
+        self.history_direct_slot = bool(ex.get('history_direct_slot', HISTORY_DIRECT_SLOT_DEFAULT))
         self.img_bev_encoder_backbone = _build(img_bev_encoder_backbone, **cp, compute_dtype=_dtype(ex.get('voxel_dtype')))
         self.img_bev_encoder_neck = _build(img_bev_encoder_neck, **cp, compute_dtype=_dtype(ex.get('voxel_dtype')))
         self.occupancy_head = _build(occupancy_head, **cp, compute_dtype=_dtype(ex.get('head_dtype')))
@@ -227,9 +235,15 @@ class FBOCC(nn.Module):
             mlp_input = self.depth_net.get_mlp_input(*cam_params)
             context, depth = self.depth_net(context, mlp_input)
             ret['depth'], ret['context'] = depth, context
-        bev_feat = self.view_transform(cam_params, context.float(), depth.float(), img_metas=img_metas)   # :344-368
+        # inference on the voxel-major ring: the view transformation writes its result ONCE, as slot 0 of the ring buffer the
+        # history step assembles (execution=dict(history_direct_slot=...)); None on every other route
+        slot = self.view_transform.history_slot(self.history, context.shape[0], context.device) if self.history_direct_slot else None
+        bev_feat = self.view_transform(cam_params, context.float(), depth.float(), img_metas=img_metas, out_slot=slot)   # :344-368
         ret['cam_params'] = cam_params
-        bev_feat = self.history.fuse_history(bev_feat, img_metas, img[6])                                # :371
+        if slot is not None and bev_feat is slot:                                                         # the frame already sits in the ring
+            bev_feat = self.history.fuse_history(bev_feat, img_metas, img[6], in_slot=True)               # :371
+        else:
+            bev_feat = self.history.fuse_history(bev_feat, img_metas, img[6])                             # :371
         if self._use_mfma(bev_feat):
             from .mfma_conv3d import to_ndhwc
             backbone, neck = self._mfma_stacks()[:2]

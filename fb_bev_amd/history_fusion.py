@@ -97,6 +97,7 @@ class TemporalHistoryFusion(nn.Module):
         self._bufs = None
         self._grid = None                     # (Z,Y,X) of the last frame
         self._fold = None                     # cached folded weights (_folded_pair)
+        self._pending = None                  # begin_frame's promise: (slot view, its ring buffer, B, (Z, Y, X))
 
     def _voxel_major(self):
         C = self.single_bev_num_channels
@@ -147,15 +148,74 @@ class TemporalHistoryFusion(nn.Module):
                 self._fold = (key, (w1[:, :C].contiguous(), w1[:, C].contiguous(), b1.contiguous(), w2.contiguous(), b2.contiguous()))
         return self._fold[1]
 
+    # ------------------------------------------------------------------ the current frame written straight into the ring
+    def _next_buffer(self, device, B, n):
+        """The ring buffer the history does NOT live in -- where the next inference step on the voxel-major ring assembles its
+        T + 1 frames (the choice _fuse_infer_vm makes)."""
+        a, b = self._frame_buffers_vm(device, B, n)
+        h = self.history_bev
+        if h is None or h.dim() == 5:                                  # a new / planar history is copied into `a` first
+            return b
+        if h.dtype != self.history_dtype:                              # re-typed between frames: the converted copy lives in neither
+            return a
+        return b if h.data_ptr() == a.data_ptr() else a
+
+    def begin_frame(self, B, grid_zyx, device, volume_dtype=torch.float32):
+        """Slot 0 of the buffer the next fuse_history call will fill, as a (B, N, C) view (N = Z*Y*X voxel rows, batch stride
+        (T+1)*N*C) -- for a producer that writes the current frame there itself (fbbev_bev_pool_v2_dense_fwd_rows) and then calls
+        fuse_history(slot, ..., in_slot=True): the fp32 volume and its transposing copy (fbbev_history_frame_vm) are never made.
+        Only when that call will take the voxel-major inference route -- eval mode, gradients off, ring_layout='voxel_major' with
+        channel counts the row kernels take -- and the producer's volume is fp32 (the slot holds ONE rounding of the fp32 sums; a
+        16-bit volume would be rounded twice on today's route).  None otherwise: the caller hands over the volume as before."""
+        self._pending = None
+        device = torch.device(device)
+        if (self.training or torch.is_grad_enabled() or not self._voxel_major() or device.type != 'cuda' or
+                volume_dtype != torch.float32 or self.history_dtype not in (torch.float32, torch.bfloat16, torch.float16)):
+            return None
+        Z, Y, X = (int(v) for v in grid_zyx)
+        nxt = self._next_buffer(device, B, Z * Y * X)
+        slot = nxt[:, 0]
+        self._pending = (slot, nxt, B, (Z, Y, X))
+        return slot
+
+    def _take_pending(self, slot):
+        """The ring buffer whose slot 0 holds the current frame, or None when what begin_frame promised no longer holds (mode, ring
+        layout or type, shape, device or the history itself changed in between): the caller then rebuilds the volume from the rows."""
+        pend, self._pending = self._pending, None
+        if pend is None or self.training or torch.is_grad_enabled() or not self._voxel_major():
+            return None
+        pslot, nxt, B, (Z, Y, X) = pend
+        if (slot.data_ptr() != pslot.data_ptr() or tuple(slot.shape) != tuple(pslot.shape) or slot.stride() != pslot.stride() or
+                slot.dtype != self.history_dtype or nxt.dtype != self.history_dtype or slot.device != nxt.device):
+            return None
+        if self._bufs is None or not any(nxt is t for t in self._bufs) or self._next_buffer(slot.device, B, Z * Y * X) is not nxt:
+            return None
+        return nxt
+
     # ------------------------------------------------------------------ fuse_history (fbocc.py:207-319)
-    def fuse_history(self, curr_bev, img_metas, bda):
-        if curr_bev.dim() != 5:
+    def fuse_history(self, curr_bev, img_metas, bda, in_slot=False):
+        """in_slot=True: curr_bev is the (B, N, C) view begin_frame returned and already holds the current frame as voxel rows."""
+        rows = nxt_slot = None
+        if in_slot:
+            if self._pending is None or curr_bev.dim() != 3:
+                raise ValueError('fuse_history(in_slot=True) takes the view the preceding begin_frame call returned')
+            (Z, Y, X), rows = self._pending[3], curr_bev
+            nxt_slot = self._take_pending(curr_bev)
+            if nxt_slot is None:      # no guessing: today's path on the volume the rows stand for (they carry the ring's rounding)
+                B, n, C = rows.shape
+                curr_bev, rows = rows.float().transpose(1, 2).reshape(B, C, Z, Y, X).permute(0, 1, 3, 4, 2), None
+        else:
+            self._pending = None
+        if rows is None and curr_bev.dim() != 5:
             raise NotImplementedError('2-D BEV history (nx[-1] == 1) is outside the built path: FB-OCC fuses a voxel grid')
         _capi.require_gpu(curr_bev, 'curr_bev')
         T, C = self.history_cat_num, self.single_bev_num_channels
         dev = curr_bev.device
-        curr = curr_bev.permute(0, 1, 4, 2, 3).float()                 # n, c, z, h, w   (:212)
-        B, _, Z, Y, X = curr.shape
+        if rows is not None:
+            curr, B = None, rows.shape[0]
+        else:
+            curr = curr_bev.permute(0, 1, 4, 2, 3).float()             # n, c, z, h, w   (:212)
+            B, _, Z, Y, X = curr.shape
         self._grid = (Z, Y, X)
         seq_ids = torch.LongTensor([m['sequence_group_idx'] for m in img_metas])
         start = torch.BoolTensor([bool(m['start_of_sequence']) for m in img_metas])
@@ -165,10 +225,10 @@ class TemporalHistoryFusion(nn.Module):
         # Like BatchNorm itself, the route is decided by the module's MODE: a module in training mode normalises with batch
         # statistics and updates the running ones even under no_grad (a validation loss computed without .eval());
         # only eval mode without gradients takes the folded-statistics MFMA kernel
-        train_path = self.training or (torch.is_grad_enabled() and curr.requires_grad)
+        train_path = rows is None and (self.training or (torch.is_grad_enabled() and curr.requires_grad))
 
         if self.history_bev is None:                                   # first batch (:227-238)
-            self.history_bev = self._new_history(curr, train_path)
+            self.history_bev = self._new_history(curr, train_path, rows)
             self.history_seq_ids = seq_ids.clone()
             self.history_forward_augs = fwd.clone()
             self.history_sweep_time = torch.zeros(B, T)
@@ -178,7 +238,11 @@ class TemporalHistoryFusion(nn.Module):
         self.history_sweep_time = self.history_sweep_time + 1          # :252
         if bool(start.any()):                                          # :253-261 (indices known on the host: no sync)
             for b in torch.nonzero(start).flatten().tolist():
-                if self.history_bev.dim() == 4:                        # voxel-major ring: (T, N, C) rows
+                if rows is not None and self.history_bev.dim() == 4:   # the slot's rows: the values the transposing copy below rounds to
+                    self.history_bev[b].copy_(rows[b].unsqueeze(0).expand(T, Z * Y * X, C))
+                elif rows is not None:                                 # planar history (the mode changed): the same values as planes
+                    self.history_bev[b].view(T, C, Z * Y * X).copy_(rows[b].t().unsqueeze(0).expand(T, C, Z * Y * X))
+                elif self.history_bev.dim() == 4:                      # voxel-major ring: (T, N, C) rows
                     self.history_bev[b].copy_(curr[b].detach().reshape(C, -1).t().unsqueeze(0).expand(T, Z * Y * X, C))
                 else:
                     self.history_bev[b].view(T, C, Z, Y, X).copy_(curr[b].detach().unsqueeze(0).expand(T, C, Z, Y, X))
@@ -194,7 +258,10 @@ class TemporalHistoryFusion(nn.Module):
             self.history_bev = h.clone() if feats_cat.requires_grad else h      # (the row path built feats_cat for this alone)
         else:
             with torch.no_grad():
-                if self._voxel_major():
+                if rows is not None:
+                    out, nxt = self._fuse_infer_vm(None, None, flow, sweep.to(dev, non_blocking=True), nxt_slot)
+                    self.history_bev = nxt[:, :T]
+                elif self._voxel_major():
                     out, nxt = self._fuse_infer_vm(curr_bev.detach().float(), curr.detach(), flow, sweep.to(dev, non_blocking=True))
                     self.history_bev = nxt[:, :T]                      # (B, T, N, C) view of the buffer just written
                 else:
@@ -220,14 +287,19 @@ class TemporalHistoryFusion(nn.Module):
     def _frame_buffers_vm(self, like, B, N):
         T, C = self.history_cat_num, self.single_bev_num_channels
         shape = (B, T + 1, N, C)
-        if (self._bufs is None or tuple(self._bufs[0].shape) != shape or self._bufs[0].device != like.device
+        device = like if isinstance(like, torch.device) else like.device
+        if (self._bufs is None or tuple(self._bufs[0].shape) != shape or self._bufs[0].device != device
                 or self._bufs[0].dtype != self.history_dtype):
             self._bufs = None                                          # release a planar pair first
-            self._bufs = [torch.empty(shape, dtype=self.history_dtype, device=like.device) for _ in range(2)]
+            self._bufs = [torch.empty(shape, dtype=self.history_dtype, device=device) for _ in range(2)]
         return self._bufs
 
-    def _new_history(self, curr, train_path):
+    def _new_history(self, curr, train_path, rows=None):
         T = self.history_cat_num
+        if rows is not None:                                           # the current frame already sits in the other buffer's slot 0
+            a, _ = self._frame_buffers_vm(rows, rows.shape[0], rows.shape[1])
+            a[:, :T].copy_(rows.unsqueeze(1).expand(-1, T, -1, -1))
+            return a[:, :T]
         if train_path:
             return curr.detach().repeat(1, T, 1, 1, 1)                 # :234
         B, C, Z, Y, X = curr.shape
@@ -290,12 +362,18 @@ class TemporalHistoryFusion(nn.Module):
         out = self.history_keyframe_cat_conv(f.reshape(B, -1, Z, Y, X))                                      # :308-310
         return out, feats_cat
 
-    def _fuse_infer_vm(self, curr_yxz, curr_zyx, flow, sweep):
+    def _fuse_infer_vm(self, curr_yxz, curr_zyx, flow, sweep, nxt_slot=None):
         """_fuse_infer on the voxel-major ring; curr_yxz is the (B, C, Y, X, Z) volume as handed over, curr_zyx the same
         tensor permuted to (B, C, Z, Y, X) (fbocc.py:212) -- whichever of the two is contiguous feeds the slot-0 transpose
-        (the view transformation returns a (Y, X, Z)-shaped VIEW of a (Z, Y, X) buffer: no copy either way)."""
+        (the view transformation returns a (Y, X, Z)-shaped VIEW of a (Z, Y, X) buffer: no copy either way).
+        nxt_slot: the ring buffer whose slot 0 the producer has ALREADY filled with the current frame's rows (begin_frame): no
+        volume, no transpose; everything after it is the same."""
         T, C = self.history_cat_num, self.single_bev_num_channels
-        B, _, Y, X, Z = curr_yxz.shape
+        if nxt_slot is not None:
+            B, (Z, Y, X) = nxt_slot.shape[0], self._grid
+            curr_yxz = nxt_slot                                        # (device / allocation reference below)
+        else:
+            B, _, Y, X, Z = curr_yxz.shape
         n = Z * Y * X
         hist = self.history_bev
         if hist.dim() == 5:                                            # planar history (training path, or the mode changed)
@@ -308,7 +386,9 @@ class TemporalHistoryFusion(nn.Module):
             if hist.dtype != self.history_dtype:                       # the storage type was changed between frames
                 hist = hist.to(self.history_dtype)
             nxt = b if hist.data_ptr() == a.data_ptr() else a
-        if curr_zyx.is_contiguous():                                   # slot 0 = current frame (:286)
+        if nxt_slot is not None:
+            assert nxt is nxt_slot                                     # (_take_pending checked exactly this choice)
+        elif curr_zyx.is_contiguous():                                 # slot 0 = current frame (:286)
             _capi.history_frame_vm(curr_zyx.view(B, C, n), nxt[:, 0])
         else:
             _capi.history_frame_vm(curr_yxz.contiguous().view(B, C, n), nxt[:, 0], inner=Z)

@@ -528,5 +528,23 @@ class LSSViewTransformerFunction3D(nn.Module):
                                     addend=None if addend is None else addend.contiguous().float())
         return out.permute(0, 1, 3, 4, 2)
 
+    def pooled_volume_rows(self, parts, out_rows, addend_rows=None):
+        """The same volume written once as VOXEL ROWS into out_rows (B, Z*Y*X, C) f32 / bf16 / f16 -- rows contiguous, any batch
+        stride: slot 0 of the voxel-major history ring -- rounded once at the store; addend_rows (B, Y*X, C) f32 (the backward
+        projection's rows) is added to every z plane before that rounding (fbbev_bev_pool_v2_dense_fwd_rows).  -> out_rows"""
+        idx, depth, feat, _ = parts
+        B, C = depth.shape[0], feat.shape[-1]
+        Z, Y, X = self.grid_zyx
+        tv = self._wo_tile
+        # the rows kernel tiles the flat (B*Z*Y*X) rank space: a table of its own beside the per-plane one in `parts`
+        tile_ws, gate = self._tile_table(idx, depth.device, B, ('rows', tv))
+        _capi.pool_tile_index(idx.interval_rank, idx.interval_starts, idx.counts, idx.n, B, Z, Y, X, tile_ws, tv,
+                              flags=_capi.POOL_CHANNELS_LAST, cache_state=idx.cache_state, table_gate=gate)
+        if addend_rows is not None and POOL_READ_AHEAD and B * Y * X >= POOL_READ_AHEAD_MIN_QUERIES:      # as pooled_volume
+            _capi.touch(idx.ranks_depth, idx.ranks_feat, idx.interval_rank, idx.interval_starts, idx.interval_lengths, depth, feat, tile_ws)
+        return _capi.bev_pool_v2_dense_fwd_rows(depth, feat, idx.ranks_depth, idx.ranks_feat, idx.interval_rank, idx.interval_starts,
+                                                idx.interval_lengths, B, C, Z, Y, X, out_rows, tile_ws, tv, self.pool_flags,
+                                                addend_rows=addend_rows)
+
     def get_mlp_input(self, rot, tran, intrin, post_rot, post_tran, bda):
         return None

@@ -268,6 +268,32 @@ int fbbev_bev_pool_v2_dense_fwd_add(const float* depth, const float* feat, const
                                     const void* tile_ws, size_t tile_ws_bytes, int tile_voxels, int flags,
                                     const float* addend, fbbev_stream_t stream);
 
+/* fbbev_bev_pool_v2_dense_fwd in the reference op's own (B,Z,Y,X,C) layout (bev_pool.py:24) written as the ROWS of a batch-strided
+ * destination, in f32 / bf16 / f16, with an optional row addend -- what the one consumer of the inference volume, slot 0 of the
+ * voxel-major history ring (B, T+1, Z*Y*X, C), is byte for byte: the view transformation writes its result once, as that slot, instead
+ * of fp32 planes that fbbev_history_frame_vm reads back and re-writes (fbocc.py:365-366 + :212,:286).
+ *   out_rows[b * out_stride_b + v * C + c] = round(pooled[b, c, v] + addend_rows[(b * Y*X + v mod Y*X) * addend_row_stride + c]),
+ *   v = (z*Y + y)*X + x.  Bit contract: `pooled` is the in-order fmaf chain of fbbev_bev_pool_v2_fwd (0.f for an empty voxel); with an
+ *   addend exactly ONE fp32 add per element follows (an empty voxel stores 0.f + addend); the result is rounded ONCE, to nearest even, at
+ *   the store (fbbev_history_frame_vm's rounding; f32: stored as is).  Every row of every sample is written exactly once; nothing
+ *   between the rows of two samples (out_stride_b > Z*Y*X*C) is touched.
+ * FBBEV_POOL_OUT_BF16 / FBBEV_POOL_OUT_F16 in `flags` select the element type of out_rows (neither: f32; both: FBBEV_E_BADARG); the
+ *   layout is channels-last by definition and tile_ws holds the tile index built with FBBEV_POOL_CHANNELS_LAST (same tile_voxels).
+ *   out_stride_b: elements of the output type between two samples, 0 = contiguous Z*Y*X*C (smaller: FBBEV_E_BADARG).  addend_rows:
+ *   (B, Y*X, C) f32 or NULL; addend_row_stride in floats, 0 = C (smaller: FBBEV_E_BADARG).
+ * FBBEV_E_UNSUPPORTED: C % 8 != 0 (16-bit) / C % 4 != 0 (f32), C > 256, out_stride_b not a multiple of 8 / 4 elements,
+ *   addend_row_stride % 4 != 0, feat / out_rows / addend_rows not 16-byte aligned, tile_voxels 8 / 16 / 32 (the small-tile kernel keeps
+ *   its contiguous fp32 form), B*Z*Y*X >= 2^31, or a voxel row that takes more lanes than a workgroup has.
+ *   FBBEV_E_WORKSPACE: tile_ws smaller than the tile table.
+ *   16-bit rows are stored with 8 channels per lane and the `sc1 nt` policy whatever the flags say; XCD swizzle as the dense kernel.
+ * No host sync, graph-capturable. */
+int fbbev_bev_pool_v2_dense_fwd_rows(const float* depth, const float* feat, const int32_t* ranks_depth,
+                                     const int32_t* ranks_feat, const int32_t* interval_rank,
+                                     const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C, int Z,
+                                     int Y, int X, void* out_rows, long long out_stride_b, const float* addend_rows,
+                                     long long addend_row_stride, const void* tile_ws, size_t tile_ws_bytes, int tile_voxels,
+                                     int flags, fbbev_stream_t stream);
+
 /* The forward projection as ONE entry (SURVEY 8b `fbbev_lift_splat_fused`).  Replaces, in
  *   fbbev/view_transformation/forward_projection/view_transformer.py:521-545 (voxel_pooling_v2) + :613-635 (view_transform_core),
  * get_lidar_coor (:458-498) -> voxel_pooling_prepare_v2 (:547-605) -> feat.permute(0,1,3,4,2) (:536) -> bev_pool_v2 (bev_pool.py:83-89:

@@ -3,7 +3,7 @@
 JSON this writes (profiles/rNN_scope_table.json).  fp32, synthetic data, p10 / p50 / p90 of per-iteration GPU time
 (HIP events around each iteration, device synchronised in between).
 
-    python tools/scope_table.py [out.json] [quick]
+    python tools/scope_table.py [out.json] [quick] [only_s6 [s6_direct_only]]
 
   S1  bev_pool_v2 op only (dense fused kernel, indices given)            REF B=16, BL2 B=16
   S2  forward projection: geometry + ranking + tile index + pooling        REF B=16, BL2 B=16   (the bench metric)
@@ -112,7 +112,7 @@ def s3(name, B, levels, n):
         row('S3t training step of the path (forward + backward of FBViewTransform, fused DA backward)', name, B, pct(step, n))
 
 
-def s6(n):
+def s6(n, reps=3, direct_only=False):
     """BASELINE configs[4] as ONE path: forward projection + backward projection + re-add + 16-frame temporal fusion with
     the history ring in fp16, 6x512x1408 input (feat 32x88, D=118), 400x400x16 grid, one sample per GPU."""
     from fb_bev_amd.history_fusion import TemporalHistoryFusion
@@ -133,12 +133,34 @@ def s6(n):
     state = {'first': True}
 
     def frame():
-        bev = m(cam, ctx, depth)
-        out = hist.fuse_history(bev, [dict(sequence_group_idx=0, start_of_sequence=state['first'], curr_to_prev_ego_rt=ego)], cam[5])
+        # direct_slot: the final pooling writes the ring's slot 0 itself (fbbev_bev_pool_v2_dense_fwd_rows); off = fp32 volume + fbbev_history_frame_vm
+        slot = m.history_slot(hist, 1, DEV) if state.get('direct') else None
+        bev = m(cam, ctx, depth, out_slot=slot)
+        out = hist.fuse_history(bev, [dict(sequence_group_idx=0, start_of_sequence=state['first'], curr_to_prev_ego_rt=ego)], cam[5],
+                                in_slot=slot is not None and bev is slot)
         state['first'] = False
         return out
     with torch.no_grad():
         vt_ms = None
+        # direct_slot off / on at the default arithmetic (bf16x3 on the voxel-major fp16 ring), alternated `reps` times: p50 per repeat
+        hist.history_compute, hist.ring_layout = 'bf16x3', 'voxel_major'
+        p50 = {False: [], True: []}
+        for rep in range(reps):
+            for direct in (False, True):
+                state['direct'] = direct
+                hist.reset(); state['first'] = True
+                frame()
+                ms = pct(frame, n, warm=2)
+                p50[direct].append(ms[1])
+                row('S6 BASELINE configs[4] path, direct_slot ' + ('on' if direct else 'off'), 'BL5 (400x400x16, 6x512x1408)', 1, ms,
+                    direct_slot=direct, repeat=rep, history_convs='bf16 MFMA x3 (split operands: fp32-grade)', ring_layout='voxel_major')
+        state['direct'] = False
+        med = {k: sorted(v)[len(v) // 2] for k, v in p50.items()}
+        row('S6 direct_slot summary (median of the per-repeat p50)', 'BL5 (400x400x16, 6x512x1408)', 1, [med[True]] * 3,
+            p50_off=p50[False], p50_on=p50[True], median_off=med[False], median_on=med[True],
+            spread_off=round(max(p50[False]) - min(p50[False]), 4))
+        if direct_only:
+            return
         for comp, lay, label in ((torch.float32, 'planar', 'fp32 MFMA'), (torch.float32, 'voxel_major', 'fp32 MFMA'),
                                  (torch.bfloat16, 'planar', 'bf16 MFMA (fp32 accumulate)'),
                                  ('bf16x3', 'voxel_major', 'bf16 MFMA x3 (split operands: fp32-grade)'),
@@ -205,7 +227,7 @@ def main():
         s3('REF', 1, 1, n); s3('REF', 4, 1, n); s3('BL2', 4, 4, n)
     if 'only_s6' in sys.argv:
         ROWS.clear()
-    s6(8 if quick else 15)
+    s6(8 if quick else 15, direct_only='s6_direct_only' in sys.argv)
     if 'only_s6' not in sys.argv:
         s4_s5(quick)
     json.dump({'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': ROWS}, open(out, 'w'), indent=1)
