@@ -121,6 +121,9 @@ SIGNATURES = {
                                [c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     'fbbev_history_warp_vm': (c_int, [c_void_p, c_int64, c_void_p] + [c_int] * 6 + [c_void_p, c_int64, c_int, c_void_p]),
     'fbbev_history_frame_vm': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    'fbbev_history_stream_prologue': (c_int, [c_void_p] * 7 + [c_float, c_int, c_int, c_int] + [c_void_p] * 6),
+    'fbbev_history_warp_vm_src': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p] + [c_int] * 6 +
+                                  [c_void_p, c_int64, c_int, c_void_p]),
     'fbbev_conv3d_ndhwc': (c_int, [c_void_p] * 4 + [c_int] * 14 + [c_void_p, c_void_p]),
     'fbbev_conv2d_nhwc': (c_int, [c_void_p] * 4 + [c_int] * 11 + [c_void_p, c_void_p]),
     'fbbev_conv3d_ndhwc_bf16': (c_int, [c_void_p] * 4 + [c_int] * 15 + [c_void_p, c_void_p]),
@@ -1024,6 +1027,52 @@ def history_warp_vm(history, rt_flow, out, grid_zyx):
                                            _dev(rt_flow, F32, 'rt_flow'), B, T, C, Z, Y, X,
                                            _dev(out, out.dtype, 'out', contiguous=False), out.stride(0),
                                            ELEM_TYPE[history.dtype], _stream()), 'fbbev_history_warp_vm')
+    return out
+
+
+def history_stream_prologue(flags, curr_to_prev_ego_rt, bda, b1, wt, dx3, lower3, freq, augs_state, sweep_state, flow_augs, rt_flow, bias1):
+    """The device-state stream mode's per-frame prologue (fbbev_history_stream_prologue), all GPU tensors: flags (B) int32 (bit 0 =
+    start_of_sequence, bit 1 = empty history), ego (B,4,4), bda (B,3,3), b1 / wt (C); state updated in place: augs_state (B,4,4),
+    sweep_state (B,T); outputs flow_augs (B,4,4: the augs rt_flow was computed from), rt_flow (B,4,4), bias1 (B*(T+1), C).
+    dx3 / lower3: host (x,y,z)."""
+    B, T = sweep_state.shape
+    C = b1.shape[0]
+    if (tuple(flags.shape) != (B,) or flags.dtype != torch.int32 or tuple(curr_to_prev_ego_rt.shape) != (B, 4, 4) or
+            tuple(bda.shape) != (B, 3, 3) or tuple(wt.shape) != (C,) or tuple(augs_state.shape) != (B, 4, 4) or
+            tuple(flow_augs.shape) != (B, 4, 4) or tuple(rt_flow.shape) != (B, 4, 4) or tuple(bias1.shape) != (B * (T + 1), C)):
+        raise FbbevError('history_stream_prologue: flags (B) int32, ego / augs / flow (B,4,4), bda (B,3,3), b1 / wt (C), '
+                         'sweep (B,T), bias1 (B*(T+1),C)')
+    arr = ctypes.c_float * 3
+    d, lo = arr(*[float(v) for v in dx3]), arr(*[float(v) for v in lower3])
+    with _on(bda):
+        _check(lib().fbbev_history_stream_prologue(
+            _dev(flags, torch.int32, 'flags'), _dev(curr_to_prev_ego_rt, F32, 'curr_to_prev_ego_rt'), _dev(bda, F32, 'bda'),
+            _dev(b1, F32, 'b1'), _dev(wt, F32, 'wt'), ctypes.cast(d, c_void_p), ctypes.cast(lo, c_void_p), float(freq), B, T, C,
+            _dev(augs_state, F32, 'augs_state'), _dev(sweep_state, F32, 'sweep_state'), _dev(flow_augs, F32, 'flow_augs'), _dev(rt_flow, F32, 'rt_flow'),
+            _dev(bias1, F32, 'bias1'), _stream()), 'fbbev_history_stream_prologue')
+    return rt_flow, bias1
+
+
+def history_warp_vm_src(history, curr, flags, rt_flow, out, grid_zyx):
+    """history_warp_vm with a per-sample source: where flags[b] != 0 the T frames of sample b are sampled from curr[b], the (N,C)
+    rows of the current frame (batch stride free), and history[b] is not read.  history, out (B,T,N,C), curr (B,N,C): one type."""
+    B, T, N, C = history.shape
+    Z, Y, X = grid_zyx
+    if tuple(out.shape) != (B, T, N, C) or N != Z * Y * X or tuple(curr.shape) != (B, N, C) or tuple(flags.shape) != (B,):
+        raise FbbevError('history_warp_vm_src: out must have the shape of history, curr (B,N,C), flags (B), N = Z*Y*X')
+    if history.dtype not in ELEM_TYPE or out.dtype != history.dtype or curr.dtype != history.dtype or flags.dtype != torch.int32:
+        raise FbbevError('history / curr / out must all be f32, bf16 or f16; flags int32')
+    for t, n in ((history, 'history'), (out, 'out')):
+        if t.stride()[1:] != (N * C, C, 1):
+            raise FbbevError(f'{n}: the (T,N,C) block of a sample must be contiguous')
+    if curr.stride()[1:] != (C, 1):
+        raise FbbevError('curr: the (N,C) rows of a sample must be contiguous')
+    with _on(history):
+        _check(lib().fbbev_history_warp_vm_src(_dev(history, history.dtype, 'history', contiguous=False), history.stride(0),
+                                               _dev(curr, curr.dtype, 'curr', contiguous=False), curr.stride(0),
+                                               _dev(flags, torch.int32, 'flags'), _dev(rt_flow, F32, 'rt_flow'), B, T, C, Z, Y, X,
+                                               _dev(out, out.dtype, 'out', contiguous=False), out.stride(0),
+                                               ELEM_TYPE[history.dtype], _stream()), 'fbbev_history_warp_vm_src')
     return out
 
 

@@ -2717,6 +2717,29 @@ extern "C" int fbbev_history_flow(const float* history_forward_augs, const float
     return 0;
 }
 
+// the device-state stream mode's per-frame prologue (history_kernels.h): k_history_stream_prologue, then k_history_flow on the
+// augs it selected -- the kernel fbbev_history_flow launches, so rt_flow carries the default route's bits
+extern "C" int fbbev_history_stream_prologue(const int32_t* flags, const float* curr_to_prev_ego_rt, const float* bda,
+                                             const float* b1, const float* wt, const float* dx3, const float* lower3,
+                                             float history_cam_sweep_freq, int B, int T, int C, float* history_forward_augs,
+                                             float* sweep_time, float* flow_augs, float* rt_flow, float* bias1,
+                                             fbbev_stream_t stream_) {
+    if (B < 0 || T < 0 || C <= 0) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    if (!flags || !curr_to_prev_ego_rt || !bda || !b1 || !wt || !dx3 || !lower3 || !history_forward_augs || !flow_augs || !rt_flow ||
+        !bias1 || (T > 0 && !sweep_time)) return FBBEV_E_BADARG;
+    if (!(dx3[0] > 0.f) || !(dx3[1] > 0.f) || !(dx3[2] > 0.f)) return FBBEV_E_BADARG;
+    if (T > 8192) return FBBEV_E_UNSUPPORTED;                      // the new sweep times of a sample sit in LDS
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    FBBEV_LAUNCH(k_history_stream_prologue, B, 256, (size_t)(T + 1) * sizeof(float), stream, flags, bda, b1, wt,
+                 history_cam_sweep_freq, T, C, history_forward_augs, sweep_time, flow_augs, bias1);
+    FBBEV_CHECK_LAUNCH();
+    FBBEV_LAUNCH(k_history_flow, (B + 63) / 64, 64, 0, stream, (const float*)flow_augs, curr_to_prev_ego_rt, bda, dx3[0], dx3[1],
+                 dx3[2], lower3[0], lower3[1], lower3[2], B, rt_flow);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int fbbev_history_warp_e(const void* history, long long history_stride_b, const float* rt_flow, int B, int CH,
                                     int Z, int Y, int X, void* out, long long out_stride_b, int elem_type,
                                     fbbev_stream_t stream_) {
@@ -2851,6 +2874,37 @@ extern "C" int fbbev_history_warp_vm(const void* history, long long history_stri
     if (e || B == 0 || T == 0) return e;
     return history_warp_vm_bands(history, history_stride_b, rt_flow, B, T, C, Z, Y, X, out, out_stride_b, elem_type, pl, 0, pl.nyb,
                                  (fbbev_rt_stream)stream_);
+}
+
+// fbbev_history_warp_vm with a per-sample source: where flags[b] != 0 the T frames of sample b are sampled from curr[b] (the current
+// frame's rows), the old ring of that sample is not read (k_history_warp_vm_src)
+extern "C" int fbbev_history_warp_vm_src(const void* history, long long history_stride_b, const void* curr, long long curr_stride_b,
+                                         const int32_t* flags, const float* rt_flow, int B, int T, int C, int Z, int Y, int X,
+                                         void* out, long long out_stride_b, int elem_type, fbbev_stream_t stream_) {
+    fbbev_warp_vm_plan pl{};
+    const int e = history_warp_vm_plan(history, history_stride_b, rt_flow, B, T, C, Z, Y, X, out, out_stride_b, elem_type, pl);
+    if (e || B == 0 || T == 0) return e;
+    if (!curr || !flags) return FBBEV_E_BADARG;
+    const int VE = elem_type == 0 ? 4 : 8;
+    const long long frame = (long long)Z * Y * X * C;
+    if (curr_stride_b == 0) curr_stride_b = frame;
+    if (curr_stride_b < frame) return FBBEV_E_BADARG;
+    if (curr_stride_b % VE != 0 || !aligned16(curr)) return FBBEV_E_UNSUPPORTED;
+    constexpr int TU = 2;
+    const long long blocks = (long long)B * pl.nyb * pl.n_xc * pl.YB * Z;
+    if (blocks >= (1ll << 31) - 8) return FBBEV_E_UNSUPPORTED;
+    const int per_xcd = (int)((blocks + 7) / 8);
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+#define FBBEV_HWVMS(ET_, TU_)                                                                                                          \
+    FBBEV_LAUNCH((k_history_warp_vm_src<ET_, TU_, 1>), (long long)per_xcd * 8, 256, 0, stream, history, history_stride_b, curr,       \
+                 curr_stride_b, flags, rt_flow, T, C, Z, Y, X, pl.groups, pl.n_xc, pl.YB, pl.nyb, per_xcd, (int)blocks, out, out_stride_b)
+    // the instantiations fbbev_history_warp_vm launches by default: two frames in flight, four for an fp16 ring
+    if (elem_type == 0) FBBEV_HWVMS(0, TU);
+    else if (elem_type == 1) FBBEV_HWVMS(1, TU);
+    else FBBEV_HWVMS(2, 4);
+#undef FBBEV_HWVMS
+    FBBEV_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int fbbev_history_frame_vm(const float* curr, int B, int C, int N, int inner, void* out, long long out_stride_b,

@@ -83,6 +83,55 @@ k_history_flow(const float* __restrict__ hist_augs, const float* __restrict__ eg
     for (int k = 0; k < 16; ++k) flow[b * 16 + k] = c[k];
 }
 
+// ---------------------------------------------------------------- device-resident sequence state (stream mode)
+// Everything FBOCC.fuse_history computes between reading img_metas and the warp (fbocc.py:220-261, 279-281, 313-314), for a history
+// whose state lives on the device: no host dependence, so a streaming frame can be replayed as a hipGraph.
+//   flags[b] bit 0 = start_of_sequence, bit 1 = the history is empty (first frame after a reset).
+// Per sample, in the reference's order: an empty history takes forward_augs = fwd and sweep 0 (:227-238); sweep += 1 (:252); a
+// started sample takes sweep 0 and forward_augs = fwd (:253-261); the resulting augs go to flow_augs, from which k_history_flow --
+// the SAME kernel the default route launches, hence the same bits: inlined into this kernel its products and sums were contracted
+// differently (127 against 125 fused multiply-adds in the compiled code) -- computes rt_flow right behind this launch (:197-203);
+// sweep' = [0, sweep] (:279-281); bias1[b, t] = b1 + (sweep'[t] * freq) * wt (the time channel of the 81 -> 80 convolution folded
+// into a bias: two single-rounded multiplies and one add, what the eager route's element-wise launches compute); the state
+// becomes sweep'[:, :T] (:313) and fwd (:314).  A first frame whose bit 0 is clear therefore ends with sweep 1, like the reference.
+// A workgroup per sample: thread 0 walks the T sweep entries (new values parked in LDS, T + 1 floats), the first thread of the
+// second wave moves the matrices, then all threads write the (T+1) x C bias rows.  Not a hot kernel: one launch of B workgroups.
+__global__ void __launch_bounds__(256)
+k_history_stream_prologue(const int* __restrict__ flags, const float* __restrict__ bda, const float* __restrict__ b1,
+                          const float* __restrict__ wt, float freq, int T, int C, float* __restrict__ augs_state,
+                          float* __restrict__ sweep_state, float* __restrict__ flow_augs, float* __restrict__ bias1) {
+    float* sw = fbbev_dyn_lds_f32();                                   // sweep' of this sample: T + 1 entries
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int fl = flags[b];
+    if (tid == 0) {
+        float* st = sweep_state + (long long)b * T;
+        sw[0] = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const float s = (fl & 1) ? 0.f : fbbev_add((fl & 2) ? 0.f : st[t], 1.f);
+            sw[t + 1] = s;
+        }
+        for (int t = 0; t < T; ++t) st[t] = sw[t];
+    }
+    if (tid == 64) {
+        const float* m = bda + b * 9;
+        float* as = augs_state + b * 16;
+        float* used = flow_augs + b * 16;
+        for (int k = 0; k < 16; ++k) {                                 // generate_forward_transformation_matrix (fbocc.py:36-41)
+            const int r = k >> 2, c = k & 3;
+            const float fwd = (r < 3 && c < 3) ? m[r * 3 + c] : (k == 15 ? 1.f : 0.f);
+            used[k] = fl ? fwd : as[k];
+            as[k] = fwd;
+        }
+    }
+    __syncthreads();
+    const int n = (T + 1) * C;
+    float* out = bias1 + (long long)b * n;
+    for (int i = tid; i < n; i += (int)blockDim.x) {
+        const int t = i / C, c = i - t * C;
+        out[i] = fbbev_add(b1[c], fbbev_mul(fbbev_mul(sw[t], freq), wt[c]));
+    }
+}
+
 // work item = ((b * n_groups) + group) * n_chunks + chunk
 // The 8 trilinear taps of output voxel (x, y, z) under the sample's rt_flow `m` (4x4 row-major): voxel index of each tap in
 // the source frame (0 for a tap outside the grid) and its weight (0 outside).  fbocc.py:205 rt_flow @ (x,y,z,1); :208-209
@@ -261,6 +310,83 @@ k_history_warp_vm(const void* __restrict__ hist, long long hist_stride_b, const 
             fo[u] = (size_t)(t0 + u < T ? t0 + u : T - 1) * frame_bytes;   // uniform
 #pragma unroll
             for (int k = 0; k < 8; ++k) raw[u][k] = *reinterpret_cast<const fbbev_v4u*>(src + fo[u] + ob[k]);
+        }
+        fbbev_sched_fence();
+#pragma unroll
+        for (int u = 0; u < TU; ++u) {
+            float acc[VE];
+#pragma unroll
+            for (int e = 0; e < VE; ++e) acc[e] = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if constexpr (ET == 2) {                 // the half is widened by the multiply itself (same value, half the issue slots)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        acc[2 * e] = fbbev_fma_f16<0>(raw[u][k][e], w[k], acc[2 * e]);
+                        acc[2 * e + 1] = fbbev_fma_f16<1>(raw[u][k][e], w[k], acc[2 * e + 1]);
+                    }
+                } else {
+                    float a[VE];
+                    fbbev_widen_vec<ET>(raw[u][k], a);
+#pragma unroll
+                    for (int e = 0; e < VE; ++e) acc[e] = fmaf(a[e], w[k], acc[e]);
+                }
+            }
+            // write-once stream: non-temporal, so the new frames do not push the tap rows of the neighbouring workgroups out of L2
+            const fbbev_v4u pk = fbbev_narrow_vec<ET>(acc);
+            fbbev_v4f pf;
+            __builtin_memcpy(&pf, &pk, 16);
+            fbbev_store4<ST>(reinterpret_cast<float*>(dst + fo[u]), pf);
+        }
+    }
+}
+
+// k_history_warp_vm with a per-sample source select (the device-state stream mode, fbocc.py:253-258): where flags[b] != 0 (the sample
+// starts a sequence, or the history is empty) every one of its T output frames is sampled from `curr`, the current frame's rows
+// (slot 0 of the next ring, batch stride curr_stride_b elements) -- what the warp computes after the current frame was copied T times
+// into the ring, without that fill and without reading the old ring.  The select is two wave-uniform scalars chosen before the frame
+// loop (source base, source frame stride 0): no select behind a load.  A kernel of its own name with a copy of the frame loop:
+// shared through a device function the loop compiled to other registers in k_history_warp_vm, which stays exactly as tuned.
+template <int ET, int TU, int ST>
+__global__ void __launch_bounds__(256)
+k_history_warp_vm_src(const void* __restrict__ hist, long long hist_stride_b, const void* __restrict__ curr, long long curr_stride_b,
+                      const int* __restrict__ flags, const float* __restrict__ flow, int T, int C, int Z, int Y, int X, int groups,
+                      int n_xc, int YB, int nyb, int per_xcd, int n_work, void* __restrict__ out, long long out_stride_b) {
+    constexpr int VE = ET == 0 ? 4 : 8;
+    constexpr int ESZ = ET == 0 ? 4 : 2;
+    int work = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);            // one contiguous eighth per XCD
+    if ((int)(blockIdx.x >> 3) >= per_xcd || work >= n_work) return;
+    const int z = work % Z; work /= Z;
+    const int yl = work % YB; work /= YB;
+    const int xc = work % n_xc; work /= n_xc;
+    const int yb = work % nyb, b = work / nyb;
+    const int y = yb * YB + yl;
+    const int item = xc * 256 + (int)threadIdx.x;
+    const int x = item / groups, gq = item - x * groups;
+    if (y >= Y || x >= X) return;
+    const int YX = Y * X, ZYX = Z * YX;
+    const int v = (z * Y + y) * X + x;
+    unsigned int ob[8];
+    float w[8];
+    fbbev_warp_taps_vm(flow + b * 16, x, y, z, X, Y, Z, C, gq * VE, ESZ, ob, w);
+    const size_t frame_bytes = (size_t)ZYX * C * ESZ;
+    const bool fresh = flags[b] != 0;                    // uniform: b comes from the workgroup index
+    const char* src = fresh ? static_cast<const char*>(curr) + (size_t)b * curr_stride_b * ESZ
+                            : static_cast<const char*>(hist) + (size_t)b * hist_stride_b * ESZ;
+    char* dst = static_cast<char*>(out) + (size_t)b * out_stride_b * ESZ + ((size_t)v * C + gq * VE) * ESZ;
+    const size_t src_frame_bytes = fresh ? (size_t)0 : frame_bytes;
+    for (int t0 = 0; t0 < T; t0 += TU) {
+        // k_history_warp_vm's frame loop with a source stride of its own (so).  straight-line body: the frame index is clamped for the loads AND the stores (an odd tail computes and stores frame
+        // T-1 twice, the same bits) -- with a break in the store loop the compiler split the batch into one frame at a time
+        fbbev_v4u raw[TU][8];
+        size_t fo[TU], so[TU];
+#pragma unroll
+        for (int u = 0; u < TU; ++u) {
+            const size_t tt = (size_t)(t0 + u < T ? t0 + u : T - 1);          // uniform
+            fo[u] = tt * frame_bytes;
+            so[u] = tt * src_frame_bytes;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) raw[u][k] = *reinterpret_cast<const fbbev_v4u*>(src + so[u] + ob[k]);
         }
         fbbev_sched_fence();
 #pragma unroll

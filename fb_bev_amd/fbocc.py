@@ -74,6 +74,9 @@ class FBOCC(nn.Module):
         da_value_dtype='bf16' | 'f16' keeps the cross-attention's camera tokens in 16 bits at inference (fp32 accumulate);
         history_direct_slot=True|False: inference on the voxel-major ring, the view transformation writes its volume once, as the
         ring's slot 0 (fbbev_bev_pool_v2_dense_fwd_rows: no fp32 volume, no fbbev_history_frame_vm; bit-identical results);
+        stream_graph=True: eval mode without gradients (and history_direct_slot off), the view transformation + history step of a
+        frame run through graphed.GraphedStream -- the sequence state on the device, the pair replayed as a hipGraph from the fifth
+        frame of a stream on (bit-identical results; the convolution stacks stay outside the graph);
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -107,6 +110,8 @@ class FBOCC(nn.Module):
         self.history_keyframe_cat_conv = hist.history_keyframe_cat_conv
         self._path = [fvt, hist]                  # plain list: holders stay out of the parameter tree (names above)
         self.history_direct_slot = bool(ex.get('history_direct_slot', HISTORY_DIRECT_SLOT_DEFAULT))
+        self.stream_graph = bool(ex.get('stream_graph', False))
+        self._stream = None                       # the GraphedStream of the pair, built on first use
         self.img_bev_encoder_backbone = _build(img_bev_encoder_backbone, **cp, compute_dtype=_dtype(ex.get('voxel_dtype')))
         self.img_bev_encoder_neck = _build(img_bev_encoder_neck, **cp, compute_dtype=_dtype(ex.get('voxel_dtype')))
         self.occupancy_head = _build(occupancy_head, **cp, compute_dtype=_dtype(ex.get('head_dtype')))
@@ -235,6 +240,13 @@ class FBOCC(nn.Module):
             mlp_input = self.depth_net.get_mlp_input(*cam_params)
             context, depth = self.depth_net(context, mlp_input)
             ret['depth'], ret['context'] = depth, context
+        if self.stream_graph and not self.history_direct_slot and not self.training and not torch.is_grad_enabled():
+            if self._stream is None:
+                from .graphed import GraphedStream
+                self._stream = GraphedStream(self.view_transform, self.history)
+            bev_feat = self._stream(cam_params, context.float(), depth.float(), img_metas, img[6])        # :344-371, replayed
+            ret['cam_params'] = cam_params
+            return self._encode_bev(bev_feat, ret)
         # inference on the voxel-major ring: the view transformation writes its result ONCE, as slot 0 of the ring buffer the
         # history step assembles (execution=dict(history_direct_slot=...)); None on every other route
         slot = self.view_transform.history_slot(self.history, context.shape[0], context.device) if self.history_direct_slot else None
@@ -244,6 +256,9 @@ class FBOCC(nn.Module):
             bev_feat = self.history.fuse_history(bev_feat, img_metas, img[6], in_slot=True)               # :371
         else:
             bev_feat = self.history.fuse_history(bev_feat, img_metas, img[6])                             # :371
+        return self._encode_bev(bev_feat, ret)
+
+    def _encode_bev(self, bev_feat, ret):
         if self._use_mfma(bev_feat):
             from .mfma_conv3d import to_ndhwc
             backbone, neck = self._mfma_stacks()[:2]

@@ -18,6 +18,10 @@ What runs where:
     16 fall back to two batched library GEMMs with a bias epilogue;
   * training (grad enabled): the reference's own op sequence on the module's layers (batch-norm statistics intact),
     only the warp is the HIP kernel -- `history_bev` is detached (:241), so the warp needs no backward.
+  * stream_state=True (opt-in): inference on the voxel-major ring keeps the sequence state -- history_forward_augs, the sweep
+    times, rt_flow, the folded bias rows -- ON THE DEVICE (`fbbev_history_stream_prologue`, `fbbev_history_warp_vm_src`): a frame
+    is one small pinned upload (flags + ego matrices) and a handful of launches with no host dependence, so that
+    `graphed.GraphedStream` can replay it as a hipGraph.  Same bits as the default route.
 No CPU fallback: the HIP extension must be present and the tensors on the GPU.
 """
 import torch
@@ -31,7 +35,7 @@ from .mfma_conv3d import MConv3d      # nn.Conv3d (same parameters / state dict)
 class TemporalHistoryFusion(nn.Module):
     def __init__(self, dx, bx, single_bev_num_channels=80, history_cat_num=16, history_cat_conv_out_channels=None,
                  do_history=True, interpolation_mode='bilinear', history_cam_sweep_freq=0.5, history_dtype=torch.float32,
-                 history_compute='auto', ring_layout='voxel_major'):
+                 history_compute='auto', ring_layout='voxel_major', stream_state=False):
         super().__init__()
         if interpolation_mode != 'bilinear':
             raise NotImplementedError("only interpolation_mode='bilinear' (trilinear on the voxel grid) is built")
@@ -87,6 +91,12 @@ class TemporalHistoryFusion(nn.Module):
         if ring_layout not in ('planar', 'voxel_major'):
             raise ValueError("ring_layout is 'planar' or 'voxel_major'")
         self.ring_layout = ring_layout
+        # Device-resident sequence state (opt-in): eval mode, gradients off, the voxel-major ring and the default two-kernel step
+        # (warp + history_conv).  The per-frame host work shrinks to the sequence-id assertion, the CPU mirrors of the state and
+        # ONE pinned upload of the flags and ego matrices; everything else is a handful of launches on buffers allocated once
+        # (_fuse_stream).  Every other situation -- training, gradients, a planar ring, a history that is not in the ring yet --
+        # runs the default route for that frame and the device state is refreshed from the mirrors afterwards.
+        self.stream_state = bool(stream_state)
         self.reset()
 
     def reset(self):
@@ -98,6 +108,9 @@ class TemporalHistoryFusion(nn.Module):
         self._grid = None                     # (Z,Y,X) of the last frame
         self._fold = None                     # cached folded weights (_folded_pair)
         self._pending = None                  # begin_frame's promise: (slot view, its ring buffer, B, (Z, Y, X))
+        self._st = None                       # stream_state: the device buffers of the sequence state (_stream_bufs)
+        self._st_ok = False                   # ... and whether they hold what the mirrors above say (False after a default-route frame)
+        self._epoch = getattr(self, '_epoch', 0) + 1      # counts resets: graphed.GraphedStream drops its graphs when it moves
 
     def _voxel_major(self):
         C = self.single_bev_num_channels
@@ -133,14 +146,18 @@ class TemporalHistoryFusion(nn.Module):
         b = (conv.bias - bn.running_mean) * scale + bn.bias
         return w, b
 
+    def _fold_key(self):
+        """(storage pointer, in-place version) of every tensor the folded maps are made of: what the _folded_pair cache is keyed on."""
+        ts = [t for seq in (self.history_keyframe_time_conv, self.history_keyframe_cat_conv)
+              for t in (seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias, seq[1].running_mean, seq[1].running_var)]
+        return tuple((t.data_ptr(), t._version) for t in ts)
+
     def _folded_pair(self):
         """Both folded maps, split the way the kernels take them -- (w1 (C,C), time column (C), b1 (C), w2 (Cout,(T+1)C), b2) --
         and cached while no parameter / running statistic changes (storage pointer + in-place version counter of each): the
         dozen small element-wise launches of the folding are a third of the inference step at 100x100x8, B=1."""
         C = self.single_bev_num_channels
-        ts = [t for seq in (self.history_keyframe_time_conv, self.history_keyframe_cat_conv)
-              for t in (seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias, seq[1].running_mean, seq[1].running_var)]
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = self._fold_key()
         if self._fold is None or self._fold[0] != key:
             with torch.no_grad():
                 w1, b1 = self._folded(self.history_keyframe_time_conv)
@@ -166,10 +183,11 @@ class TemporalHistoryFusion(nn.Module):
         fuse_history(slot, ..., in_slot=True): the fp32 volume and its transposing copy (fbbev_history_frame_vm) are never made.
         Only when that call will take the voxel-major inference route -- eval mode, gradients off, ring_layout='voxel_major' with
         channel counts the row kernels take -- and the producer's volume is fp32 (the slot holds ONE rounding of the fp32 sums; a
-        16-bit volume would be rounded twice on today's route).  None otherwise: the caller hands over the volume as before."""
+        16-bit volume would be rounded twice on today's route).  None otherwise: the caller hands over the volume as before.
+        None as well while stream_state is on: the device-state route takes the volume (the direct slot is not part of it)."""
         self._pending = None
         device = torch.device(device)
-        if (self.training or torch.is_grad_enabled() or not self._voxel_major() or device.type != 'cuda' or
+        if (self.stream_state or self.training or torch.is_grad_enabled() or not self._voxel_major() or device.type != 'cuda' or
                 volume_dtype != torch.float32 or self.history_dtype not in (torch.float32, torch.bfloat16, torch.float16)):
             return None
         Z, Y, X = (int(v) for v in grid_zyx)
@@ -195,6 +213,8 @@ class TemporalHistoryFusion(nn.Module):
     # ------------------------------------------------------------------ fuse_history (fbocc.py:207-319)
     def fuse_history(self, curr_bev, img_metas, bda, in_slot=False):
         """in_slot=True: curr_bev is the (B, N, C) view begin_frame returned and already holds the current frame as voxel rows."""
+        if self.stream_state and not in_slot and self._stream_route(curr_bev, len(img_metas)):
+            return self._fuse_stream(curr_bev, img_metas, bda)
         rows = nxt_slot = None
         if in_slot:
             if self._pending is None or curr_bev.dim() != 3:
@@ -271,9 +291,139 @@ class TemporalHistoryFusion(nn.Module):
         self.history_forward_augs = fwd.clone()                        # :314
         if not self.do_history:                                        # :317-318
             self.history_bev = None
+        self._st_ok = False                                            # the device copy of the state (stream_state) is behind now
         return out.permute(0, 1, 3, 4, 2)                              # (B,Cout,Y,X,Z) view, as :315-319
 
     forward = fuse_history
+
+    # ------------------------------------------------------------------ stream_state: the sequence state on the device
+    def _stream_check(self):
+        if self.fused_x3 or self.pipelined_step or self.fused_warp_conv:
+            raise ValueError('stream_state covers the default two-kernel history step (fbbev_history_warp_vm_src + fbbev_history_conv): '
+                             'switch fused_x3 / pipelined_step (it runs on two streams) / fused_warp_conv off, or stream_state')
+
+    def _stream_route(self, curr_bev, B):
+        """True when this frame runs on the device-state route: eval mode, gradients off, the voxel-major ring, and a history that
+        is either empty or already lives in the ring buffers of this shape and type (a planar / re-typed / foreign history takes
+        one default-route frame first, which puts it there)."""
+        self._stream_check()
+        if (self.training or torch.is_grad_enabled() or not self._voxel_major() or not self.do_history or curr_bev.dim() != 5
+                or self.history_dtype not in _capi.ELEM_TYPE):
+            return False
+        h = self.history_bev
+        if h is None:
+            return True
+        T, C = self.history_cat_num, self.single_bev_num_channels
+        _, _, Y, X, Z = curr_bev.shape
+        bufs = self._bufs
+        return (h.dim() == 4 and h.dtype == self.history_dtype and bufs is not None and bufs[0].dtype == self.history_dtype and
+                tuple(bufs[0].shape) == (B, T + 1, Z * Y * X, C) and bufs[0].device == curr_bev.device and
+                h.data_ptr() in (bufs[0].data_ptr(), bufs[1].data_ptr()) and tuple(self.history_sweep_time.shape) == (B, T))
+
+    def _stream_bufs(self, B, device):
+        """Everything the device-state route reads or writes per frame besides the two ring buffers, allocated once per (B, device):
+        `up` = [flags (B) int32 | ego (B,4,4)] -- the target of the one upload; the state (`augs`, `sweep`); the prologue's outputs
+        (`used` = the augs of this frame's flow, `flow`, `bias1`); a few pinned staging buffers that take turns, each guarded by the event of its last copy."""
+        T, C = self.history_cat_num, self.single_bev_num_channels
+        st = self._st
+        if st is None or st['key'] != (B, T, C, device):
+            f32 = dict(dtype=torch.float32, device=device)
+            up = torch.zeros(B * 17, **f32)
+            st = dict(key=(B, T, C, device), up=up, flags=up[:B].view(torch.int32), ego=up[B:].view(B, 4, 4),
+                      augs=torch.zeros(B, 4, 4, **f32), sweep=torch.zeros(B, T, **f32), used=torch.zeros(B, 4, 4, **f32),
+                      flow=torch.zeros(B, 4, 4, **f32),
+                      bias1=torch.zeros(B * (T + 1), C, **f32),
+                      pins=[torch.zeros(B * 17, dtype=torch.float32).pin_memory() for _ in range(4)], events=[None] * 4, turn=0)
+            self._st, self._st_ok = st, False
+        return st
+
+    def _stream_host(self, img_metas, device):
+        """The host's share of a device-state frame: the sequence-id assertion (fbocc.py:248-249), history_seq_ids, the CPU mirror
+        of the sweep times (:252-261, :279-281, :313) -- none of it reads the device -- and ONE upload: flags (bit 0 =
+        start_of_sequence, bit 1 = empty history) and the ego matrices, from a pinned buffer into their fixed device buffer."""
+        T = self.history_cat_num
+        B = len(img_metas)
+        st = self._stream_bufs(B, device)
+        seq_ids = torch.LongTensor([m['sequence_group_idx'] for m in img_metas])
+        start = torch.BoolTensor([bool(m['start_of_sequence']) for m in img_metas])
+        empty = self.history_bev is None
+        if empty:                                                      # first batch (:227-238): bit 1, the old state is not read
+            self.history_seq_ids = seq_ids.clone()
+            self.history_sweep_time = torch.zeros(B, T)
+        elif not self._st_ok:                                          # default-route frames ran in between: the mirrors are the truth
+            st['sweep'].copy_(self.history_sweep_time)
+            st['augs'].copy_(self.history_forward_augs)
+        bad = (self.history_seq_ids != seq_ids)[~start]
+        assert int(bad.sum()) == 0, '{}, {}, {}'.format(self.history_seq_ids, seq_ids, start)   # :248-249
+        sweep = self.history_sweep_time + 1                            # :252
+        if bool(start.any()):                                          # :253-261
+            sweep[start] = 0
+            self.history_seq_ids[start] = seq_ids[start]
+        self.history_sweep_time = torch.cat([torch.zeros(B, 1), sweep], dim=1)[:, :-1]      # :279-281, :313
+        i = st['turn']
+        st['turn'] = (i + 1) % len(st['pins'])
+        ev, pin = st['events'][i], st['pins'][i]
+        if ev is not None and not ev.query():                          # its copy of four frames ago is still in flight
+            ev.synchronize()
+        pin[:B].view(torch.int32).copy_(torch.tensor([int(s) | (2 if empty else 0) for s in start.tolist()], dtype=torch.int32))
+        ego = pin[B:].view(B, 4, 4)
+        for b, m in enumerate(img_metas):                              # :222-224
+            ego[b].copy_(torch.as_tensor(m['curr_to_prev_ego_rt'], dtype=torch.float32))
+        st['up'].copy_(pin, non_blocking=True)
+        if ev is None:
+            ev = st['events'][i] = torch.cuda.Event()
+        ev.record()
+        self._st_ok = True
+
+    def _stream_device(self, curr_bev, bda):
+        """The device's share: fbbev_history_frame_vm into slot 0 of the ring buffer the history does not live in, the prologue,
+        fbbev_history_warp_vm_src into slots 1..T, fbbev_history_conv.  Reads no host data and changes none: -> (fused (B, Cout, Z,
+        Y, X), that ring buffer); the caller moves the history there (_stream_commit).  This is what GraphedStream captures."""
+        st = self._st
+        T, C = self.history_cat_num, self.single_bev_num_channels
+        curr_yxz = curr_bev.detach().float()
+        B, _, Y, X, Z = curr_yxz.shape
+        n = Z * Y * X
+        a, b = self._frame_buffers_vm(curr_yxz, B, n)
+        hist = self.history_bev
+        if hist is None:                                               # empty: bit 1 is set for every sample, `a` is never read
+            hist, nxt = a[:, :T], b
+        else:
+            nxt = b if hist.data_ptr() == a.data_ptr() else a
+        curr_zyx = curr_yxz.permute(0, 1, 4, 2, 3)                     # :212
+        if curr_zyx.is_contiguous():                                   # slot 0 = current frame (:286), as _fuse_infer_vm
+            _capi.history_frame_vm(curr_zyx.view(B, C, n), nxt[:, 0])
+        else:
+            _capi.history_frame_vm(curr_yxz.contiguous().view(B, C, n), nxt[:, 0], inner=Z)
+        w1, wt, b1, w2, b2 = self._folded_pair()
+        _capi.history_stream_prologue(st['flags'], st['ego'], bda.float().contiguous(), b1, wt, self.dx, self.lower,
+                                      self.history_cam_sweep_freq, st['augs'], st['sweep'], st['used'], st['flow'], st['bias1'])
+        _capi.history_warp_vm_src(hist, nxt[:, 0], st['flags'], st['flow'], nxt[:, 1:], (Z, Y, X))      # slots 1..T (:253-258, :275)
+        compute = self.history_compute
+        if compute == 'auto':
+            compute = 'bf16x3' if nxt.dtype in (torch.bfloat16, torch.float16) else torch.float32
+        if compute == 'bf16x3' and not (nxt.dtype in (torch.bfloat16, torch.float16) and C == w2.shape[0] and C in (16, 80)):
+            compute = torch.float32
+        out = _capi.history_conv(nxt, w1, st['bias1'], w2, b2,
+                                 torch.empty((B, w2.shape[0], n), dtype=torch.float32, device=curr_yxz.device),
+                                 compute=compute, voxel_major=True)
+        return out.view(B, -1, Z, Y, X), nxt
+
+    def _stream_commit(self, nxt, grid_zyx):
+        """The history now lives in `nxt` (:312) and history_forward_augs is the device state itself (:314: the prologue left fwd there)."""
+        self._grid = tuple(grid_zyx)
+        self.history_bev = nxt[:, :self.history_cat_num]
+        self.history_forward_augs = self._st['augs']
+
+    def _fuse_stream(self, curr_bev, img_metas, bda):
+        _capi.require_gpu(curr_bev, 'curr_bev')
+        self._pending = None
+        _, _, Y, X, Z = curr_bev.shape
+        self._stream_host(img_metas, curr_bev.device)
+        with torch.no_grad():
+            out, nxt = self._stream_device(curr_bev, bda)
+        self._stream_commit(nxt, (Z, Y, X))
+        return out.permute(0, 1, 3, 4, 2)                              # (B,Cout,Y,X,Z) view, as :315-319
 
     # ------------------------------------------------------------------ internals
     def _frame_buffers(self, like, B, Z, Y, X):

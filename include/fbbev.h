@@ -1026,6 +1026,32 @@ int fbbev_history_warp_vm(const void* history, long long history_stride_b, const
 int fbbev_history_frame_vm(const float* curr, int B, int C, int N, int inner, void* out, long long out_stride_b,
                            int elem_type, fbbev_stream_t stream);
 
+/* ---- device-resident sequence state of the history fusion (TemporalHistoryFusion(stream_state=True)): one frame of a camera
+ * stream without host dependence, so that it can be captured and replayed as a hipGraph.
+ * fbbev_history_stream_prologue: everything FBOCC.fuse_history computes between reading img_metas and the warp, on a state that
+ *   lives on the device (two small launches: the state / bias kernel, then the kernel of fbbev_history_flow).  flags[b] (int32, device): bit 0 = start_of_sequence, bit 1 = the history is empty (the
+ *   first frame after a reset).  State, updated in place: history_forward_augs (B,4,4), sweep_time (B,T).  Per sample, in the
+ *   reference's order: an empty history takes forward_augs = fwd, the homogeneous embedding of bda[b] (fbocc.py:36-41), and
+ *   sweep 0 (:227-238); sweep += 1 (:252); a started sample takes sweep 0 and forward_augs = fwd (:253-261); the resulting augs
+ *   are left in flow_augs (B,4,4) and rt_flow[b] is what fbbev_history_flow computes from them (:197-203; the same kernel: the same bits);
+ *   sweep' = [0, sweep] (:279-281); bias1[b*(T+1) + t, :] = b1 + (sweep'[t] * history_cam_sweep_freq) * wt, each operation rounded
+ *   once -- the time channel of the 81 -> 80 convolution (:292-305) folded into the bias rows fbbev_history_conv_* take (b1 (C):
+ *   folded bias, wt (C): folded time column); then the state becomes sweep'[:, :T] (:313) and fwd (:314).  A first frame whose bit
+ *   0 is clear therefore ends with sweep 1, as in the reference.  dx3 / lower3 are HOST pointers (x,y,z); every other pointer is
+ *   device memory.  B == 0: no-op.
+ * fbbev_history_warp_vm_src: fbbev_history_warp_vm with a per-sample source.  Where flags[b] != 0, all T output frames of sample b
+ *   are sampled from curr[b] -- the current frame's rows (N, C), i.e. slot 0 of the next ring; curr_stride_b elements between
+ *   samples, 0 = dense -- which is what :253-258 + :264-275 compute after copying the current frame T times into the history; the
+ *   old ring of that sample is never read.  Where flags[b] == 0: fbbev_history_warp_vm.  Same element bits, argument checks and
+ *   error codes as fbbev_history_warp_vm (curr: 16-byte aligned, stride as history's); B == 0 or T == 0: no-op. */
+int fbbev_history_stream_prologue(const int32_t* flags, const float* curr_to_prev_ego_rt, const float* bda, const float* b1,
+                                  const float* wt, const float* dx3, const float* lower3, float history_cam_sweep_freq, int B,
+                                  int T, int C, float* history_forward_augs, float* sweep_time, float* flow_augs, float* rt_flow,
+                                  float* bias1, fbbev_stream_t stream);
+int fbbev_history_warp_vm_src(const void* history, long long history_stride_b, const void* curr, long long curr_stride_b,
+                              const int32_t* flags, const float* rt_flow, int B, int T, int C, int Z, int Y, int X, void* out,
+                              long long out_stride_b, int elem_type, fbbev_stream_t stream);
+
 /* Dense 3-D convolution on NDHWC (torch channels_last_3d) f32 activations as an fp32-MFMA implicit GEMM, inference:
  * replaces the eval-mode Conv3d (+ folded BatchNorm) (+ residual) (+ ReLU) groups of CustomResNet3D (resnet3d.py:19-43,
  * 78-102), FPN3D (fpn3d.py:50-70) and OccHead (occupancy_head.py:82-141), which the reference runs in fp32 through the

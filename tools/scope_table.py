@@ -3,7 +3,7 @@
 JSON this writes (profiles/rNN_scope_table.json).  fp32, synthetic data, p10 / p50 / p90 of per-iteration GPU time
 (HIP events around each iteration, device synchronised in between).
 
-    python tools/scope_table.py [out.json] [quick] [only_s6 [s6_direct_only]]
+    python tools/scope_table.py [out.json] [quick] [only_s6 [s6_direct_only]] [only_s6_stream]
 
   S1  bev_pool_v2 op only (dense fused kernel, indices given)            REF B=16, BL2 B=16
   S2  forward projection: geometry + ranking + tile index + pooling        REF B=16, BL2 B=16   (the bench metric)
@@ -11,6 +11,9 @@ JSON this writes (profiles/rNN_scope_table.json).  fp32, synthetic data, p10 / p
   S3  S2 + backward projection + re-add (FBViewTransform)                  REF B=1 / B=4 (1 level), BL2 grid B=4 (4 levels = BASELINE configs[2])
   S4  full detector, images -> occupancy ids (shipped config)              B=1: fp32-MFMA convolution route (default), bf16_tiled route
   S5  full training step (forward_train + backward + clip + AdamW)         B=2, B=4 (= BASELINE configs[3] per-GPU batch)
+  S6-stream  one frame of a B=1 camera stream, view transformation + history step, three routes alternated in one process:
+      default eager | device-state eager (stream_state) | replayed (graphed.GraphedStream)
+                                                                           REF grid fp32 / fp16 ring, BL5 (configs[4]) fp16 ring
 """
 import json, os, sys
 import torch
@@ -178,6 +181,55 @@ def s6(n, reps=3, direct_only=False):
     torch.cuda.empty_cache()
 
 
+def s6_stream(n, reps=3):
+    """One frame of a B = 1 stream -- FBViewTransform + TemporalHistoryFusion, 16-frame history -- on the default eager route, the
+    device-state eager route (stream_state=True) and replayed from the two hipGraphs of graphed.GraphedStream: three history modules
+    on one view transformation, alternated `reps` times in this process; p50 of the per-iteration HIP-event time per repeat, and the
+    median / spread over the repeats."""
+    from fb_bev_amd.graphed import GraphedStream
+    from fb_bev_amd.history_fusion import TemporalHistoryFusion
+    for name, dt, label, n_it in (('REF', torch.float32, 'REF (100x100x8), fp32 ring', n), ('REF', torch.float16, 'REF (100x100x8), fp16 ring', n),
+                                  ('BL5', torch.float16, 'BL5 (400x400x16, 6x512x1408), fp16 ring', max(8, n // 5))):
+        pc = S.CONFIGS[name]
+        X, Y, Z = pc.grid_xyz
+        gcb = {'x': pc.grid_config['x'], 'y': pc.grid_config['y'], 'z': [-1, 5.4, 1.6]}
+        cfg = configs.fbocc_r50(bev_h=Y, bev_w=X, numC_Trans=pc.channels, input_size=pc.input_size, grid_config=pc.grid_config,
+                                grid_config_bevformer=gcb, depth_bound=tuple(pc.grid_config['depth']), downsample=pc.downsample)
+        m = FBViewTransform(cfg['forward_projection'], cfg['backward_projection']).to(DEV).eval()
+        dx = [pc.grid_config[a][2] for a in 'xyz']
+        bx = [pc.grid_config[a][0] + pc.grid_config[a][2] / 2 for a in 'xyz']
+        hists = [TemporalHistoryFusion(dx, bx, single_bev_num_channels=pc.channels, history_cat_num=16, history_dtype=dt).to(DEV).eval()
+                 for _ in range(3)]
+        for h in hists[1:]:
+            h.load_state_dict(hists[0].state_dict())
+        hists[1].stream_state = True
+        g = GraphedStream(m, hists[2])
+        cam = [t.to(DEV) for t in S.camera_rig(pc, 1, seed=0, bda_aug=False)]
+        depth, ctx = (t.to(DEV) for t in S.depth_and_context(pc, 1, seed=0))
+        ego = torch.eye(4); ego[0, 3] = 0.8
+
+        def metas(first=False):
+            return [dict(sequence_group_idx=0, start_of_sequence=first, curr_to_prev_ego_rt=ego)]
+        routes = (('default eager', lambda first=False: hists[0].fuse_history(m(cam, ctx, depth), metas(first), cam[5])),
+                  ('device-state eager', lambda first=False: hists[1].fuse_history(m(cam, ctx, depth), metas(first), cam[5])),
+                  ('replayed', lambda first=False: g(cam, ctx, depth, metas(first), cam[5])))
+        with torch.no_grad():
+            p50 = {k: [] for k, _ in routes}
+            for k, fn in routes:
+                fn(True)
+            for rep in range(reps):
+                for k, fn in routes:
+                    ms = pct(fn, n_it, warm=5)           # (the replayed route needs four frames before it only replays)
+                    p50[k].append(ms[1])
+                    row('S6-stream view transformation + history step, ' + k, label, 1, ms, route=k, repeat=rep)
+            assert all(gr is not None for gr in g._graphs)
+            med = {k: sorted(v)[len(v) // 2] for k, v in p50.items()}
+            row('S6-stream summary (median of the per-repeat p50)', label, 1, [med['replayed']] * 3, p50=p50, median=med,
+                spread_default_eager=round(max(p50['default eager']) - min(p50['default eager']), 4))
+        del m, hists, g
+        torch.cuda.empty_cache()
+
+
 def s4_s5(quick):
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import time_full as T
@@ -221,6 +273,10 @@ def main():
     quick = 'quick' in sys.argv
     n = 20 if quick else 100                 # at least 100 timed iterations (round-2 tables were taken with 50)
     only6 = 'only_s6' in sys.argv
+    if 'only_s6_stream' in sys.argv:
+        s6_stream(n)
+        json.dump({'device': torch.cuda.get_device_name(0), 'torch': torch.__version__, 'rows': ROWS}, open(out, 'w'), indent=1)
+        return
     for name in (() if only6 else ('REF', 'BL2')):
         s1_s2(name, 16, n)
     if not only6:
