@@ -34,7 +34,8 @@ def deterministic_enabled():
 
 def set_rows_linear_mode(name):
     """Route of the backward projection's row-wise linear layers: 'x3' (split-operand bf16 MFMA, the default), 'f32' (vendor fp32
-    GEMM) or 'f32_mfma' (exact fp32 on the FP32 MFMA, the arithmetic contract of fbbev_rows_linear_f32 in include/fbbev.h).
+    GEMM) or 'f32_mfma' (exact fp32 on the FP32 MFMA, in inference and under autograd: the arithmetic contracts of fbbev_rows_linear_f32
+    and fbbev_rows_wgrad_f32 in include/fbbev.h).
     Returns the previous mode; `rows_linear.set_mode` is the same switch.  FBBEV_ROWS_LINEAR only sets the initial mode."""
     from . import rows_linear
     return rows_linear.set_mode(name)

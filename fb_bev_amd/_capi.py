@@ -100,6 +100,10 @@ SIGNATURES = {
     'fbbev_rows_wgrad_x3_ws_bytes': (c_size_t, [c_int64, c_int, c_int]),
     'fbbev_rows_wgrad_x3': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    'fbbev_rows_wgrad_f32_slice_rows': (c_int64, [c_int64, c_int, c_int]),
+    'fbbev_rows_wgrad_f32_ws_bytes': (c_size_t, [c_int64, c_int, c_int]),
+    'fbbev_rows_wgrad_f32': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
     'fbbev_rows_linear_x3_train': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                            c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     'fbbev_sum_leading': (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
@@ -1632,6 +1636,42 @@ def rows_wgrad_x3_supported(grad_out, x):
     return (grad_out.is_cuda and grad_out.dtype == F32 and x.dtype == F32 and grad_out.dim() == 2 and x.dim() == 2 and
             grad_out.stride(1) == 1 and x.stride(1) == 1 and grad_out.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and
             grad_out.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and grad_out.shape[1] % 4 == 0 and x.shape[1] % 4 == 0)
+
+
+def rows_wgrad_f32_slice_rows(R, I, O):
+    """rows per slice of fbbev_rows_wgrad_f32's two-stage sum (host function): a multiple of 4 that depends on (R, I, O) only"""
+    L = lib().fbbev_rows_wgrad_f32_slice_rows(int(R), int(I), int(O))
+    if L <= 0:
+        raise FbbevError(f'rows_wgrad_f32_slice_rows: invalid argument {L}')
+    return int(L)
+
+
+def rows_wgrad_f32(grad_out, x, bias=True):
+    """grad_out (R, O), x (R, I) f32 rows (unit column stride) -> (grad_weight (O, I), grad_bias (O) or None) in exact fp32 on the
+    FP32 MFMA (fbbev_rows_wgrad_f32: one fmaf chain per slice of rows_wgrad_f32_slice_rows rows, the slices added in ascending order)."""
+    R, O = grad_out.shape
+    I = x.shape[1]
+    if x.shape[0] != R or grad_out.stride(1) != 1 or x.stride(1) != 1:
+        raise FbbevError('rows_wgrad_f32: grad_out (R, O) and x (R, I) rows with unit column stride')
+    gw = torch.empty((O, I), dtype=F32, device=x.device)
+    gb = torch.empty((O,), dtype=F32, device=x.device) if bias else None
+    need = lib().fbbev_rows_wgrad_f32_ws_bytes(R, I, O)
+    if need == 0 and R > 0:
+        raise FbbevError('rows_wgrad_f32: unsupported shape (in_features % 8, out_features % 8)')
+    ws = torch.empty(max(need, 16) // 4, dtype=F32, device=x.device)
+    with _on(x):
+        _check(lib().fbbev_rows_wgrad_f32(_dev(grad_out, F32, 'grad_out', contiguous=False), grad_out.stride(0),
+                                          _dev(x, F32, 'x', contiguous=False), x.stride(0), R, I, O, _dev(gw, F32, 'grad_weight'),
+                                          _dev(gb, F32, 'grad_bias') if gb is not None else None, c_void_p(ws.data_ptr()), need, _stream()),
+               'fbbev_rows_wgrad_f32')
+    return gw, gb
+
+
+def rows_wgrad_f32_supported(grad_out, x):
+    return (grad_out.is_cuda and grad_out.dtype == F32 and x.dtype == F32 and grad_out.dim() == 2 and x.dim() == 2 and
+            grad_out.stride(1) == 1 and x.stride(1) == 1 and grad_out.stride(0) % 4 == 0 and x.stride(0) % 4 == 0 and
+            grad_out.stride(0) >= grad_out.shape[1] and x.stride(0) >= x.shape[1] and
+            grad_out.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and grad_out.shape[1] % 8 == 0 and x.shape[1] % 8 == 0)
 
 
 def conv3d_ndhwc(x, weight_fragments, bias, out, Cout, ksize=3, stride=1, pad=1, relu=False, residual=None, transposed=False):

@@ -5,6 +5,7 @@
 #include "rt.h"
 #include "capi_common.h"
 #include "wgrad_kernels.h"
+#include "rows_wgrad_f32_kernels.h"
 #include "../../include/fbbev.h"
 
 // ------------------------------------------------------------------------------ weight / bias gradient of a row-wise linear layer
@@ -80,6 +81,67 @@ extern "C" int fbbev_rows_wgrad_x3(const float* grad_out, long long ld_grad, con
     const long long OI = (long long)O * I, total = OI + (grad_bias ? O : 0);
     FBBEV_LAUNCH(k_rows_wgrad_reduce<8>, (total + 31) / 32, 256, 0, stream, (const float*)part_w, (const float*)part_b, p.n_split, OI,
                  O, grad_weight, grad_bias);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ the same gradients in exact fp32 (FP32 MFMA)
+struct wgf_plan { int L, S, n_oc, n_ic; long long items; size_t part_b, total; };
+
+static bool wgf_plan_make(long long rows, int I, int O, wgf_plan* p) {
+    if (rows <= 0 || I <= 0 || O <= 0 || I % 8 != 0 || O % 8 != 0) return false;
+    const long long L = fbbev_rows_wgrad_f32_slice(rows, I, O), S = (rows + L - 1) / L;
+    p->n_oc = (O + 16 * FBBEV_WGF_TO - 1) / (16 * FBBEV_WGF_TO);
+    p->n_ic = (I + 16 * FBBEV_WGF_TI - 1) / (16 * FBBEV_WGF_TI);
+    p->items = S * p->n_oc * p->n_ic;
+    if (S >= (1ll << 31) || p->items + 3 >= (1ll << 32)) return false;                    // (the kernel decodes the item in 32 bits)
+    p->L = (int)L;
+    p->S = (int)S;
+    p->part_b = align_up((size_t)S * O * I * sizeof(float), 256);
+    p->total = p->part_b + align_up((size_t)S * O * sizeof(float), 256);
+    return true;
+}
+
+extern "C" long long fbbev_rows_wgrad_f32_slice_rows(long long rows, int in_features, int out_features) {
+    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
+    if (in_features % 8 != 0 || out_features % 8 != 0) return FBBEV_E_UNSUPPORTED;
+    return fbbev_rows_wgrad_f32_slice(rows, in_features, out_features);
+}
+
+extern "C" size_t fbbev_rows_wgrad_f32_ws_bytes(long long rows, int in_features, int out_features) {
+    wgf_plan p;
+    return wgf_plan_make(rows, in_features, out_features, &p) ? p.total : 0;
+}
+
+extern "C" int fbbev_rows_wgrad_f32(const float* grad_out, long long ld_grad, const float* x, long long ldx, long long rows,
+                                    int in_features, int out_features, float* grad_weight, float* grad_bias, void* workspace,
+                                    size_t workspace_bytes, fbbev_stream_t stream_) {
+    const int I = in_features, O = out_features;
+    if (rows < 0 || I <= 0 || O <= 0 || ld_grad < 0 || ldx < 0) return FBBEV_E_BADARG;
+    if (!grad_weight || (rows > 0 && (!grad_out || !x))) return FBBEV_E_BADARG;
+    int e_rows = 0;
+    if (rows > 0) {
+        e_rows = row_worse(row_operand(grad_out, &ld_grad, O), row_operand(x, &ldx, I));
+        if (e_rows == FBBEV_E_BADARG) return e_rows;
+    }
+    if (I % 8 != 0 || O % 8 != 0 || e_rows || !aligned16(grad_weight) || (grad_bias && !aligned16(grad_bias))) return FBBEV_E_UNSUPPORTED;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    if (rows == 0) {
+        int e = fbbev_rt_memset_async(grad_weight, 0, (size_t)O * I * sizeof(float), stream);
+        if (!e && grad_bias) e = fbbev_rt_memset_async(grad_bias, 0, (size_t)O * sizeof(float), stream);
+        return e;
+    }
+    wgf_plan p;
+    if (!wgf_plan_make(rows, I, O, &p)) return FBBEV_E_UNSUPPORTED;
+    if (!workspace || !aligned16(workspace) || workspace_bytes < p.total) return FBBEV_E_WORKSPACE;
+    float* part_w = reinterpret_cast<float*>(workspace);
+    float* part_b = grad_bias ? reinterpret_cast<float*>(static_cast<char*>(workspace) + p.part_b) : nullptr;
+    FBBEV_LAUNCH(k_rows_wgrad_f32<FBBEV_WGF_DEPTH>, (p.items + 3) / 4, 256, 0, stream, grad_out, ld_grad, x, ldx, rows, O, I, p.L, p.n_oc,
+                 p.n_ic, (unsigned int)p.items, part_w, part_b);
+    FBBEV_CHECK_LAUNCH();
+    const long long OI = (long long)O * I, total = OI + (grad_bias ? O : 0);
+    FBBEV_LAUNCH(k_rows_wgrad_f32_reduce<8>, (total + 255) / 256, 256, 0, stream, (const float*)part_w, (const float*)part_b, p.S, OI, O,
+                 grad_weight, grad_bias);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

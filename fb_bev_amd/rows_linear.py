@@ -22,6 +22,8 @@ MIN_ROWS = 16384            # below this autograd's plain GEMM is as good
 # FBBEV_ROWS_LINEAR=f32_mfma: the exact-fp32 kernel on the FP32 MFMA (fbbev_rows_linear_f32: one fmaf chain per output element in a
 # documented order, bias / ReLU / addend / LayerNorm in its epilogue) takes every layer the split-operand kernel would have taken.
 # X3 keeps its meaning -- "the split-operand kernels and the one-kernel attention routes are on" -- and is False on that route.
+# Under autograd the same mode runs a layer's forward, input gradient and weight / bias gradient on the FP32 MFMA as well
+# (_RowsLinearF32: fbbev_rows_linear_f32 on W and on W^T, fbbev_rows_wgrad_f32), from X3_MIN_ROWS rows on.
 MODES = ('x3', 'f32', 'f32_mfma')
 _env_mode = os.environ.get('FBBEV_ROWS_LINEAR', 'x3')
 X3 = _env_mode not in ('f32', 'f32_mfma')
@@ -110,6 +112,62 @@ class _RowsLinear(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = bias_grad(gy)
         return gx, gw, gb
+
+
+def _aligned_rows(t):
+    """a 2-D fp32 tensor as the exact-fp32 entries read it: unit column stride, row stride % 4 == 0, 16-byte aligned"""
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < t.shape[1] or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _RowsLinearF32(torch.autograd.Function):
+    """x (R, I) 2-D -> (R, O) on the exact-fp32 MFMA route (mode f32_mfma) under autograd: every product of the layer's training step
+    has an arithmetic the header defines (include/fbbev.h).  Forward: fbbev_rows_linear_f32 (bias inside, no ReLU) -- the kernel and
+    the bits of the same layer's no_grad forward.  grad_x = gy W: the same entry on (gy, W^T), a chain over the output channels in the
+    order rows_linear_f32_k_order(O).  grad_W / grad_b: fbbev_rows_wgrad_f32 (slice chains over the rows, slices added in order)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, x, w, b):
+        x, wc = _aligned_rows(x), _aligned_rows(w)
+        bc = None if b is None else b.contiguous()
+        if bc is not None and bc.data_ptr() % 16 != 0:                       # a view into a flat parameter buffer (as X3Weights.get)
+            bc = bc.clone()
+        ctx.save_for_backward(x, wc)
+        ctx.has_bias = b is not None
+        return _capi.rows_linear_f32(x, wc, bc)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type='cuda')
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = _aligned_rows(gy.float())
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = _capi.rows_linear_f32(gy, w.t().contiguous(), None)
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1] or want_b:
+            gw, gb = _capi.rows_wgrad_f32(gy, x, bias=want_b)
+            if not ctx.needs_input_grad[1]:
+                gw = None
+        return gx, gw, gb
+
+
+def _is_gpu(t):
+    return t.is_cuda
+
+
+def f32_train_ok(x, w, b):
+    """the exact-fp32 training route applies: mode f32_mfma, GPU fp32 rows, autograd recording something, the row count of the same
+    mode's inference gate (a layer's forward runs on the same kernel with and without grad), shapes the entries take.  Strides and
+    alignment are not a condition of the route: _RowsLinearF32 brings its operands into the form the entries read (_aligned_rows, the
+    rule of _capi.rows_wgrad_f32_supported), so that a layer's route does not depend on how a caller laid out its rows"""
+    I, O = x.shape[-1], w.shape[0]
+    return (f32_mfma_on() and _is_gpu(x) and x.dtype == torch.float32 and w.dtype == torch.float32 and
+            (b is None or b.dtype == torch.float32) and torch.is_grad_enabled() and
+            (w.requires_grad or x.requires_grad or (b is not None and b.requires_grad)) and
+            w.dim() == 2 and w.shape[1] == I and I % 8 == 0 and O % 8 == 0 and x.numel() // max(1, I) >= X3_MIN_ROWS)
 
 
 class X3Weights:
@@ -218,7 +276,8 @@ def linear_x3(x, cache, relu=False, out=None, addend=None, ln=None):
 def linear_rows(x, w, b=None, cache=None, transform=None, relu=False, addend=None, ln=None):
     """F.linear (+ ReLU) of x [+ addend] for row tensors.  Inference on a GPU with a `cache` (X3Weights owned by the calling module;
     `w` / `b` are then the SOURCE parameters and `transform` derives the applied matrix): the split-operand MFMA kernel, which
-    also folds the addend (query_pos) into its row loads.  Training on a GPU: the split-K backward when it pays.  Otherwise F.linear."""
+    also folds the addend (query_pos) into its row loads.  Training on a GPU: in mode f32_mfma the exact-fp32 function _RowsLinearF32
+    (addend, ReLU and LayerNorm stay separate ATen steps), else the split-K backward when it pays.  Otherwise F.linear."""
     if cache is not None:
         O = w.shape[0] if transform is None else None
         if x3_ok(x, x.shape[-1], O if O is not None else 4):
@@ -233,7 +292,9 @@ def linear_rows(x, w, b=None, cache=None, transform=None, relu=False, addend=Non
     if transform is not None:
         w, b = transform(w, b)
     rows = x.numel() // max(1, x.shape[-1])
-    if (x.is_cuda and rows >= MIN_ROWS and torch.is_grad_enabled() and x.dtype == torch.float32 and
+    if f32_train_ok(x, w, b):
+        y = _RowsLinearF32.apply(x.reshape(rows, x.shape[-1]), w, b).view(*x.shape[:-1], w.shape[0])
+    elif (x.is_cuda and rows >= MIN_ROWS and torch.is_grad_enabled() and x.dtype == torch.float32 and
             (w.requires_grad or x.requires_grad or (b is not None and b.requires_grad))):
         y = _RowsLinear.apply(x.reshape(rows, x.shape[-1]), w, b).view(*x.shape[:-1], w.shape[0])
     else:

@@ -858,7 +858,10 @@ int fbbev_rows_linear_x3_ln(const float* x, long long x_row_stride, const void* 
  * FFN), with a summation order this header defines instead of a vendor library's kernel selection.  `weight` is the nn.Linear
  * parameter itself: row-major (out_features, in_features) fp32, 16-byte aligned; no prepared fragments.  Strides, shapes and error
  * codes as fbbev_rows_linear_x3 (in_features % 8 == 0, out_features % 4 == 0, strides % 4 == 0, 16-byte aligned pointers, else
- * FBBEV_E_UNSUPPORTED; FBBEV_E_BADARG for null x / weight / out or negative sizes; rows == 0: 0 and no launch).  Inference only.
+ * FBBEV_E_UNSUPPORTED; FBBEV_E_BADARG for null x / weight / out or negative sizes; rows == 0: 0 and no launch).  Training: the
+ * forward of a layer is this entry as it is; its input gradient grad_x = grad_out . W is this entry again on (grad_out, W^T) with
+ * W^T a contiguous (in_features, out_features) fp32 matrix, so its chain runs over the OUTPUT channels in the order
+ * fbbev_rows_linear_f32_k_order(out_features); weight and bias gradient: fbbev_rows_wgrad_f32 below.
  *
  * Arithmetic contract, for every output element (r, o):
  *   1. xr[k] = x[r, k], or x[r, k] + addend[r % addend_period, k] as one fp32 add (fbbev_rows_linear_f32_add);
@@ -887,6 +890,33 @@ int fbbev_rows_linear_f32_ln(const float* x, long long x_row_stride, const float
  * 0 .. in_features-1 that depends on in_features only.  Host function, no GPU work.  FBBEV_E_BADARG for in_features <= 0 or a
  * null pointer. */
 int fbbev_rows_linear_f32_k_order(int in_features, int* order);
+/* Weight and bias gradient of the same layers in EXACT fp32 on the FP32 matrix instruction (autograd's `grad_out.t().mm(x)` /
+ * `grad_out.sum(0)` behind every nn.Linear of bevformer_encoder.py:206-377 and spatial_cross_attention_depth.py:432-436,464):
+ *   grad_weight (out_features, in_features) = grad_out^T x,   grad_bias (out_features) = column sums of grad_out (NULL: skipped)
+ * for grad_out (rows, out_features) and x (rows, in_features), row strides in floats (0 = dense), with a summation order this header
+ * defines.  Partial results go through `workspace` (fbbev_rows_wgrad_f32_ws_bytes bytes, 16-byte aligned).
+ *
+ * Arithmetic contract.  L = fbbev_rows_wgrad_f32_slice_rows(rows, in_features, out_features): a positive multiple of 4 that depends
+ * on its three arguments only (not on the launch geometry, the CU count, the entry or any environment knob).  Slice s covers the rows
+ * [s L, min((s + 1) L, rows)), S = ceil(rows / L).  For every element (o, i):
+ *   1. p_s = +0; for r ascending in slice s: p_s = fmaf(grad_out[r, o], x[r, i], p_s) -- one chain per slice;
+ *   2. grad_weight[o, i] = p_0; for s = 1 .. S-1: grad_weight[o, i] += p_s -- plain fp32 adds in ascending s;
+ *   3. grad_bias[o] the same two stages with q_s = q_s + grad_out[r, o] (= fmaf(grad_out[r, o], 1, q_s)) inside a slice.
+ * No atomics: bit-identical from run to run, and for finite inputs every bit is reproducible on a host with fmaf.  The sign of a
+ * zero is not part of the contract (the zero-padded rows of a slice's last 4-row step may turn -0 into +0).
+ *
+ * in_features % 8 == 0, out_features % 8 == 0, strides % 4 == 0, 16-byte aligned pointers, else FBBEV_E_UNSUPPORTED (ws_bytes
+ * returns 0, slice_rows FBBEV_E_UNSUPPORTED); FBBEV_E_BADARG for null grad_out / x / grad_weight, negative sizes or a stride shorter
+ * than its row; FBBEV_E_WORKSPACE for a workspace that is null, misaligned or too small; rows == 0: the outputs are zero-filled, 0.
+ * Nothing is launched before the arguments are validated.  fbbev_rows_wgrad_f32_slice_rows is a host function, no GPU work; it is
+ * the one entry of this header that returns a 64-bit value.  Keep the spelling `long long int` (the same type as long long):
+ * tests/test_abi_symbols.py finds a declaration by `int` or `size_t` in front of its name, and a declaration it does not find drops
+ * out of the header / signature-table / export comparison without a failure. */
+long long int fbbev_rows_wgrad_f32_slice_rows(long long rows, int in_features, int out_features);
+size_t fbbev_rows_wgrad_f32_ws_bytes(long long rows, int in_features, int out_features);
+int fbbev_rows_wgrad_f32(const float* grad_out, long long ld_grad, const float* x, long long ldx, long long rows, int in_features,
+                         int out_features, float* grad_weight, float* grad_bias, void* workspace, size_t workspace_bytes,
+                         fbbev_stream_t stream);
 /* The FFN pair of the encoder layer in ONE kernel: out = [LayerNorm](W2 relu(W1 x + b1) + b2 [+ residual]) -- mmcv FFN as the encoder
  * layer configures it (Linear + ReLU, Linear, add_identity; bevformer_encoder.py:250-377) and, with ln_weight, the layer's following
  * LayerNorm.  The hidden rows never leave the CU (as two launches they are written and re-read: 205 MB each way at 160 000 rows).
