@@ -23,7 +23,8 @@ static bool wgrad_plan_make(long long rows, int I, int O, wgrad_plan* p) {
     p->amt = O >= 128 ? 8 : (O + 15) / 16;
     // (768 workgroups for the narrow layers -- three per CU at their 41 KB of LDS -- measured slower than 256: 48.8 -> 54.8 us at 80 x 80)
     long long want = 512 / ((long long)p->n_oc * p->n_ic);
-    static const int env_split = fbbev_env_int("FBBEV_WGRAD_SPLITS", 0);   // tuning knob
+    // tuning knob (FBBEV_KNOB_ONCE: the emulator's tests switch it inside one process)
+    FBBEV_KNOB_ONCE(int, env_split, fbbev_env_int("FBBEV_WGRAD_SPLITS", 0));
     if (env_split > 0) want = env_split;
     if (want < 8) want = 8;
     if (want > 256) want = 256;

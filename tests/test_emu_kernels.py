@@ -794,8 +794,9 @@ def test_rows_linear_with_periodic_addend_emulated():
 def test_rows_wgrad_split_operand_emulated(R, I, O, monkeypatch):
     """fbbev_rows_wgrad_x3 (grad_weight = grad_out^T x, grad_bias = column sums: autograd's backward of nn.Linear) against float64 for
     the backward projection's layer shapes (80 x 80, 512 x 80, 96 x 80, the FFN's 80 x 320 with three input chunks), row counts that
-    are not multiples of the 32-row step, widths that are not multiples of a 16-column tile, strided rows, three K splits (the last one
-    partial); a second run is bit-identical, and the bias gradient can be skipped."""
+    are not multiples of the 32-row step, widths that are not multiples of a 16-column tile, strided rows, few K splits (the knob asks
+    for three, the plan takes eight at the least: splits of several steps, the last one partial); a second run is bit-identical, and
+    the bias gradient can be skipped."""
     g = torch.Generator().manual_seed(R * 7 + I + O)
     gys = torch.randn(R, O + 4, generator=g)
     xs = torch.randn(R, I + 8, generator=g) * 2

@@ -700,7 +700,10 @@ def test_write_once_volume_path_equals_reference_composition(dev, name, B):
 @pytest.mark.gpu
 def test_rows_linear_split_k_backward_on_the_gpu():
     """rows_linear at the configs[2] row count (160 000 x 80 -> 128): the GPU route is taken (custom backward node) and its
-    weight / bias / input gradients equal autograd's plain GEMMs to fp32 rounding."""
+    weight / bias / input gradients equal autograd's plain GEMMs to fp32 rounding.  One shape, every size a multiple of every tile,
+    a normwise bar: shapes other than 160 000 x 80 -> 128 (row tails, partial output chunks and column tiles, several input chunks,
+    shorter last K splits, the periodic addend, strided and in-place operands) are pinned element by element in
+    tests/test_gpu_rows_train_kernels.py."""
     from fb_bev_amd import rows_linear as RL
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(3)
