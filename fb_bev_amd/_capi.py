@@ -1674,9 +1674,19 @@ def rows_wgrad_f32_supported(grad_out, x):
             grad_out.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0 and grad_out.shape[1] % 8 == 0 and x.shape[1] % 8 == 0)
 
 
+def _padded_bias(bias, Cout, what):
+    """The convolution kernels read `bias + c0` as one float4 for every live 4-channel group of a 16-channel output tile, so the bias
+    must hold ceil(Cout / 16) * 16 floats (include/fbbev.h); a shorter one is refused here, before any launch."""
+    need = (int(Cout) + 15) // 16 * 16
+    if not isinstance(bias, torch.Tensor) or bias.numel() < need:
+        have = bias.numel() if isinstance(bias, torch.Tensor) else None
+        raise FbbevError(f'{what}: bias must be zero-padded to {need} floats (16 * ceil(Cout / 16), Cout = {int(Cout)}), got {have}')
+
+
 def conv3d_ndhwc(x, weight_fragments, bias, out, Cout, ksize=3, stride=1, pad=1, relu=False, residual=None, transposed=False):
     """x (B,Di,Hi,Wi,Cin) f32 contiguous (NDHWC); out (B,Do,Ho,Wo,Cout) [transposed: (B,2Di,2Hi,2Wi,Cout)] contiguous;
     weight_fragments / bias as built by fb_bev_amd.mfma_conv3d (batch norm folded, MFMA A-fragment order)."""
+    _padded_bias(bias, Cout, 'conv3d_ndhwc')
     B, Di, Hi, Wi, Cin = x.shape
     if transposed:
         Do, Ho, Wo = Di, Hi, Wi
@@ -1697,6 +1707,7 @@ def conv3d_ndhwc(x, weight_fragments, bias, out, Cout, ksize=3, stride=1, pad=1,
 
 def conv2d_nhwc(x, weight_fragments, bias, out, Cout, ksize=3, stride=1, pad=1, relu=False, residual=None):
     """x (B,H,W,Cin) f32 contiguous (NHWC); out (B,Ho,Wo,Cout); weights as mfma_conv3d.weight_fragments(w[:, :, None])."""
+    _padded_bias(bias, Cout, 'conv2d_nhwc')
     B, Hi, Wi, Cin = x.shape
     Ho, Wo = [(n + 2 * pad - ksize) // stride + 1 for n in (Hi, Wi)]
     if tuple(out.shape) != (B, Ho, Wo, Cout) or (residual is not None and tuple(residual.shape) != (B, Ho, Wo, Cout)):
@@ -1713,6 +1724,7 @@ def conv3d_ndhwc_bf16(x, weight_fragments_bf16, bias, out, Cout, ksize=3, stride
                       transposed=False, planar=False):
     """bf16-MFMA variant of conv3d_ndhwc (planar=True: x (B,1,H,W,Cin), the 2-D case); weights from
     mfma_conv3d.weight_fragments_bf16 (torch.bfloat16 tensor)."""
+    _padded_bias(bias, Cout, 'conv3d_ndhwc_bf16')
     B, Di, Hi, Wi, Cin = x.shape
     Do, Ho, Wo = out.shape[1:4]
     if transposed:
@@ -1730,6 +1742,7 @@ def conv3d_ndhwc_bf16(x, weight_fragments_bf16, bias, out, Cout, ksize=3, stride
 
 def conv3d_k3s1_tiled_bf16(x, weight_fragments_bf16, bias, out, Cout, relu=False, residual=None):
     """3x3x3 / stride 1 / padding 1 on (B,D,H,W,Cin) f32 with the LDS-staged halo tile (bf16 MFMA)."""
+    _padded_bias(bias, Cout, 'conv3d_k3s1_tiled_bf16')
     B, D, H, W, Cin = x.shape
     if tuple(out.shape) != (B, D, H, W, Cout) or weight_fragments_bf16.dtype != torch.bfloat16:
         raise FbbevError('conv3d_k3s1_tiled_bf16: bad out shape / weight dtype')

@@ -645,6 +645,22 @@ def conv3d_wgrad_ndhwc(x, dy, ksize=3, stride=1, pad=1):
     return code, dw
 
 
+def conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, ksize, flags=_capi.FLAG_DETERMINISTIC):
+    return lib().fbbev_conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, ksize, flags)
+
+
+def conv3d_wgrad_ndhwc_ex(x, dy, ksize=3, stride=1, pad=1, flags=_capi.FLAG_DETERMINISTIC):
+    """fbbev_conv3d_wgrad_ndhwc_ex -> (code, dw); the chunk workspace starts as NaN (the kernel must store every word it later adds)"""
+    B, Di, Hi, Wi, Cin = x.shape
+    _, Do, Ho, Wo, Cout = dy.shape
+    need = conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, ksize, flags)
+    ws = torch.full((max(need, 4) // 4,), float('nan'))
+    dw = torch.zeros(ksize ** 3, Cout, Cin)
+    code = lib().fbbev_conv3d_wgrad_ndhwc_ex(p(x), p(dy), B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, p(dw), flags,
+                                             p(ws) if need else None, need, None)
+    return code, dw
+
+
 def conv2d_nhwc(x, wf, bias, Cout, ksize=3, stride=1, pad=1, relu=False, residual=None):
     B, Hi, Wi, Cin = x.shape
     Ho, Wo = [(n + 2 * pad - ksize) // stride + 1 for n in (Hi, Wi)]
