@@ -175,6 +175,7 @@ SIGNATURES = {
     'fbbev_value_rows_to_head_planes': (c_int, [c_void_p, c_int64] + [c_int] * 5 + [c_void_p, c_void_p]),
     'fbbev_da_cross_attn_fwd_planes_supported': (c_int, [c_int] * 9),
     'fbbev_da_cross_attn_fwd_planes': (c_int, [c_void_p] * 9 + [c_int] * 10 + [c_float, c_float, c_int, c_int, c_int] + [c_void_p, c_void_p]),
+    'fbbev_occ_classes': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 6 + [c_void_p] * 6),
 }
 
 _lib = None
@@ -1888,4 +1889,35 @@ def history_conv(feats, w1, bias1, w2, bias2, out, compute=torch.float32, voxel_
             _check(lib().fbbev_history_conv_vm(*args, ELEM_TYPE[feats.dtype], _stream()), 'fbbev_history_conv_vm')
         else:
             _check(lib().fbbev_history_conv_e(*args, ELEM_TYPE[feats.dtype], _stream()), 'fbbev_history_conv_e')
+    return out
+
+
+U8 = torch.uint8
+
+
+def occ_classes(logits, c0=0, gt=None, mask=None, column_mask=None, hist=None, out=None):
+    """fbbev_occ_classes: class ids uint8 (B, W, H, D) -- the CVPR-2023 axis order of fbocc.py:546-549 -- from logits (B, C, H, W, D)
+    f32 with ANY strides (the channels-last view of the MFMA head runner and the vendor route's class planes are the fast ones; no
+    copy is made).  The class is softmax(logits[:, c0:]).argmax(1), taken from the logits.  With gt (B, W, H, D) uint8 and hist
+    (n, n) int32, n = C - c0, the same launch adds the confusion counts hist[gt][class] of the voxels with gt < n whose mask
+    (B, W, H, D) and column_mask (W, H) bytes (where given) are non-zero."""
+    require_gpu(logits, 'logits')
+    if logits.dtype != F32 or logits.dim() != 5:
+        raise FbbevError(f'logits must be a 5-D float32 tensor (B, C, H, W, D), got {logits.dtype} {tuple(logits.shape)}')
+    B, C, H, W, D = logits.shape
+    if out is None:
+        out = torch.empty((B, W, H, D), dtype=U8, device=logits.device)
+    elif tuple(out.shape) != (B, W, H, D):
+        raise FbbevError(f'out must be {(B, W, H, D)}, got {tuple(out.shape)}')
+    n = C - int(c0)
+    for t, name, shape in ((gt, 'gt', (B, W, H, D)), (mask, 'mask', (B, W, H, D)), (column_mask, 'column_mask', (W, H))):
+        if t is not None and tuple(t.shape) != shape:
+            raise FbbevError(f'{name} must be {shape}, got {tuple(t.shape)}')
+    if hist is not None and tuple(hist.shape) != (n, n):
+        raise FbbevError(f'hist must be {(n, n)}, got {tuple(hist.shape)}')
+    opt = lambda t, dt, name: None if t is None else _dev(t, dt, name)  # noqa: E731
+    with _on(logits):
+        _check(lib().fbbev_occ_classes(c_void_p(logits.data_ptr()), *[int(s) for s in logits.stride()], B, C, int(c0), H, W, D,
+                                       _dev(out, U8, 'out'), opt(gt, U8, 'gt'), opt(mask, U8, 'mask'),
+                                       opt(column_mask, U8, 'column_mask'), opt(hist, I32, 'hist'), _stream()), 'fbbev_occ_classes')
     return out

@@ -24,6 +24,7 @@
 #include "msda_bwd_kernels.h"
 #include "conv3d_kernels.h"
 #include "det_kernels.h"
+#include "occ_kernels.h"
 #include "../../include/fbbev.h"
 
 #include "capi_common.h"
@@ -3929,6 +3930,38 @@ extern "C" int fbbev_blend_levels_ndhwc(const float* level0, const float* const*
     if (blocks > 262144) blocks = 262144;
     FBBEV_LAUNCH(k_blend_levels_ndhwc, blocks, 256, 0, (fbbev_rt_stream)stream_, level0, lv[0], lv[1], lv[2], n_coarse, wsoft, K,
                  B, D, H, W, C, out);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ occupancy classes + mIoU confusion matrix
+extern "C" int fbbev_occ_classes(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                                 long long stride_d, int B, int C, int c0, int H, int W, int D, uint8_t* classes, const uint8_t* gt,
+                                 const uint8_t* mask, const uint8_t* column_mask, int32_t* hist, fbbev_stream_t stream_) {
+    if (!logits || !classes || B < 0 || C <= 0 || H <= 0 || W <= 0 || D <= 0 || c0 < 0) return FBBEV_E_BADARG;
+    if (!gt && (mask || column_mask || hist)) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    const int n = C - c0;
+    if (n < 2 || n > 32 || (long long)B * H * W * D >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    // tile: TD depth cells (the whole depth up to 64) x T x T columns, <= FBBEV_OCC_TILE_VOXELS voxels
+    const int TD = D < 64 ? D : 64, T = TD >= 16 ? 8 : 16;
+    const int nth = (H + T - 1) / T, ntw = (W + T - 1) / T, ntd = (D + TD - 1) / TD;
+    const long long ntiles = (long long)B * nth * ntw * ntd;
+    // channels-last (a voxel's logits contiguous, voxels C apart along d) goes through LDS while 256 rows fit in 40 KiB
+    const int staged = (stride_c == 1 && stride_d == C && C <= 40) ? 1 : 0;
+    const int row_runs = (staged && TD == D && stride_w == (long long)D * C) ? 1 : 0;
+    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
+    const int vec4 = (D % 4 == 0 && aligned4(classes) && aligned4(gt) && aligned4(mask)) ? 1 : 0;
+    const size_t lds = (staged ? (size_t)FBBEV_OCC_THREADS * C * 4 : 0) + (size_t)n * n * 4 + FBBEV_OCC_TILE_VOXELS;
+    const long long blocks = ntiles < 1536 ? ntiles : 1536;          // six workgroups per CU resident: one wave of workgroups
+#define FBBEV_OCC_LAUNCH(S, V)                                                                                                          \
+    FBBEV_LAUNCH((k_occ_classes<S, V>), blocks, FBBEV_OCC_THREADS, lds, (fbbev_rt_stream)stream_, logits, stride_b, stride_c, stride_h, \
+                 stride_w, stride_d, C, c0, H, W, D, T, TD, nth, ntw, ntd, (int)ntiles, row_runs, classes, gt, mask, column_mask, hist)
+    if (staged && vec4) FBBEV_OCC_LAUNCH(true, true);
+    else if (staged) FBBEV_OCC_LAUNCH(true, false);
+    else if (vec4) FBBEV_OCC_LAUNCH(false, true);
+    else FBBEV_OCC_LAUNCH(false, false);
+#undef FBBEV_OCC_LAUNCH
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

@@ -1153,6 +1153,22 @@ int fbbev_blend_levels_ndhwc(const float* level0, const float* const* coarse, co
                              const float* wsoft, int K, int B, int D, int H, int W, int C, float* out,
                              fbbev_stream_t stream);
 
+/* Occupancy class map and mIoU confusion matrix in ONE pass over the head's logits: replaces the inference tail of the reference
+ * (fbocc.py:539-554: fix_void slice, softmax, argmax, permute / flip / rot90 / permute) and the scoring of a frame
+ * (occ_metrics.py:80-105 hist_info, :122-164 add_batch with mask_camera and the range ring).
+ *   logits (B, C, H, W, D) f32 with the given strides in elements (any pattern; fast for channels-last -- stride_c == 1,
+ *   stride_d == C -- and for class planes, stride_d == 1).  n = C - c0 classes are scored (c0 = 1: fix_void).
+ *   classes[b, w, h, d] = lowest index among the maxima of logits[b, c0:, h, w, d]; 0 when one of them is NaN or +inf (what
+ *   softmax(...).argmax() returns).  (B, W, H, D) contiguous: the CVPR-2023 axis order, an H <-> W transpose of the input.
+ *   gt, mask (B, W, H, D) and column_mask (W, H) bytes or NULL; hist (n, n) int32 or NULL, row = gt, column = prediction,
+ *   ADDED to: a voxel counts iff gt < n and its mask byte and its column's column_mask byte (where given) are non-zero.
+ *   Integer adds only: exact and identical run to run.
+ * FBBEV_E_BADARG: null logits / classes, B < 0, a non-positive C / H / W / D, c0 < 0, or mask / column_mask / hist without gt.
+ * B == 0: 0 and no launch.  FBBEV_E_UNSUPPORTED: n outside 2..32, or B*H*W*D >= 2^31 (which also keeps a bin within int32). */
+int fbbev_occ_classes(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                      long long stride_d, int B, int C, int c0, int H, int W, int D, uint8_t* classes, const uint8_t* gt,
+                      const uint8_t* mask, const uint8_t* column_mask, int32_t* hist, fbbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
