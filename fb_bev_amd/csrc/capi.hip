@@ -1422,6 +1422,132 @@ extern "C" int fbbev_msda_bwd_ws(const float* value, const int64_t* spatial_shap
 }
 
 // ------------------------------------------------------------------------------ fused DA cross-attention
+// The depth-aware (DA) cross-attention family.  Every entry fills ONE da_args from its positional C arguments and everything
+// below it works on that record.  Entry -> internal route:
+//   forward
+//     fbbev_da_cross_attn_fwd             da_fwd_rows: k_da_cross_attn_fwd_unit (a lane owns a (b, q, head) unit), else k_da_cross_attn_fwd
+//     fbbev_da_cross_attn_fwd_e           fp32 rows: da_fwd_rows; 16-bit rows: its own checks, the same unit kernel (da_fwd_unit_launch)
+//     fbbev_da_cross_attn_fwd_zt          k_da_cross_attn_fwd_pipe where da_pipe_shape_ok holds, else da_fwd_rows
+//     fbbev_da_cross_attn_fused[_e|_ln]   da_fused: k_da_cross_attn_fused (query rows -> slots; _ln: -> output_proj + LayerNorm rows)
+//     fbbev_da_cross_attn_fwd_planes      k_da_fwd_planes (the training forward on head planes)
+//   backward
+//     fbbev_da_cross_attn_bwd             da_bwd_atomic: k_da_cross_attn_bwd (global atomics)
+//     fbbev_da_cross_attn_bwd_ex          flag off: da_bwd_atomic; deterministic: k_da_cross_attn_bwd<GW, true> + fbbev_da_depth_taps_det
+//     fbbev_da_cross_attn_bwd_ws[_grid]   da_bwd_ws: da_bwd_owned_launch (output-owned planes), else the chunked scatter
+//                                         (da_bwd_unit_launch + k_da_cross_attn_bwd_scatter + k_da_bwd_reduce), else da_bwd_atomic
+//     fbbev_da_cross_attn_bwd_ws_grid_ex  flag off: da_bwd_ws; deterministic: da_bwd_det around da_bwd_ws (never da_bwd_atomic: -2)
+//     fbbev_da_cross_attn_bwd_planes      da_bwd_planes: da_bwd_owned_launch on the forward's head planes
+//     fbbev_da_cross_attn_bwd_planes_ex   flag off: da_bwd_planes; deterministic: da_bwd_det around da_bwd_planes
+//   probes and sizes (host only)
+//     fbbev_da_cross_attn_fwd_zt_fuses_softmax / _fused_supported / _fwd_planes_supported    the shape checks of their routes
+//     fbbev_da_cross_attn_bwd_ws_bytes[_za] / _bwd_planes_supported                          da_own_plan_make, da_bwd_tile_plan
+//     fbbev_da_cross_attn_bwd_det_ws_bytes / fbbev_da_bwd_det_ws_bytes / fbbev_da_depth_taps_det_ws_bytes    the deterministic workspaces
+struct da_args {
+    int B, Ncam, S, M, Dh, L, Q, P, Za, DC;
+    float d0, dstep;
+    int head_minor, HS, bev_w;                              // HS: floats per head in a value row (head_stride; 0 = Dh); bev_w 0 = no grid
+    fbbev_rt_stream stream;
+    const float* value;                                     // camera tokens as rows (fwd_e: 16-bit rows behind the same pointer) ...
+    const float* planes;                                    // ... or as head planes: an entry takes one of the two
+    const int64_t* spatial_shapes; const int64_t* level_start_index;
+    const float* pred_depth; const float* ref_cam; const uint8_t* mask; const float* qdepth;
+    const float* offsets; const float* attn;                // null in the fused entries (projected inside the kernel)
+    float* slots;                                           // the forward's output
+    const float* grad_slots;                                // the backward's input and outputs
+    float* grad_value; float* grad_pred_depth; float* grad_offsets; float* grad_attn;
+};
+// An entry's record: the braces list its operands in the order above -- what it does not have is nullptr / 0, and trailing members may
+// be left out (the probes and planners stop after bev_w: no operands) -- with head_stride in HS's place, resolved here.
+static inline da_args da_record(da_args a) { if (a.HS == 0) a.HS = a.Dh; return a; }
+
+// The checks the entries share.  Their ORDER inside an entry is part of the ABI (it decides the code where two defects coincide),
+// so every entry strings them together itself.
+// every dimension positive, except: Q >= q_min (0 admits the empty call) and bev_w >= w_min (0 admits "no grid")
+static inline bool da_dims_ok(const da_args& a, int q_min, int w_min) {
+    return a.B > 0 && a.Ncam > 0 && a.S > 0 && a.M > 0 && a.Dh > 0 && a.L > 0 && a.Q >= q_min && a.P > 0 && a.Za > 0 && a.DC > 0 &&
+           a.bev_w >= w_min;
+}
+static inline bool da_anchors_ok(const da_args& a) { return a.Za <= FBBEV_DA_MAX_ZA && a.P % a.Za == 0; }
+static inline bool da_geometry_present(const da_args& a) {
+    return a.spatial_shapes && a.level_start_index && a.pred_depth && a.ref_cam && a.mask && a.qdepth;
+}
+static inline bool da_fwd_present(const da_args& a) {
+    return (a.value || a.planes) && da_geometry_present(a) && a.offsets && a.attn && a.slots;
+}
+static inline bool da_bwd_present(const da_args& a) {
+    return (a.value || a.planes) && da_geometry_present(a) && a.offsets && a.attn && a.grad_slots && a.grad_value &&
+           a.grad_pred_depth && a.grad_offsets && a.grad_attn;
+}
+// 8-byte accesses to the (x, y) offset pairs and to channel pairs of the slots, in whichever direction the record has them
+static inline bool da_pairs_aligned(const da_args& a) {
+    return (((uintptr_t)a.offsets | (uintptr_t)a.slots | (uintptr_t)a.grad_offsets | (uintptr_t)a.grad_slots) & 7) == 0;
+}
+// the head-dimension ladders (they differ on purpose: the set of instantiations is each kernel's own)
+#define FBBEV_DA_DH_FWD(DH, X) do { if ((DH) == 10) X(10); else if ((DH) == 8) X(8); else if ((DH) == 16) X(16); else X(32); } while (0)
+#define FBBEV_DA_DH_BWD(DH, X) do { if ((DH) == 10) X(10); else if ((DH) == 8) X(8); else if ((DH) == 4) X(4); else X(16); } while (0)
+
+// k_da_cross_attn_fwd_unit: a lane owns all Dh channels of a (b, q, head) unit.  wide / qi: the row layout of fp32 tokens; et: 16-bit
+// tokens (1 bf16, 2 fp16: always chunk-major pieces)
+static int da_fwd_unit_launch(const da_args& a, bool wide, bool qi, int et) {
+    const long long units = (long long)a.B * a.Q * a.M;
+    long long ub = ((units + 255) / 256 + 7) / 8 * 8;             // XCD-contiguous order: a multiple of 8 workgroups
+    if (ub > 65536) ub = 65536;
+    // attention weights in (B,Q,M,L,P) staged through LDS ([256][L*P+1] floats) when 4 workgroups per CU still fit
+    const int LP = a.L * a.P;
+    const bool stage = !(a.head_minor & 2) && LP % 4 == 0 && LP <= 36 && aligned16(a.attn);
+    const size_t lds = stage ? (size_t)256 * (LP + 1) * sizeof(float) : 0;
+#define FBBEV_DA_UNIT_W(DH_, W_, Q_, ET_)                                                                                  \
+    FBBEV_LAUNCH((k_da_cross_attn_fwd_unit<DH_, W_, Q_, ET_>), ub, 256, lds, a.stream, units, a.value, a.spatial_shapes,    \
+                 a.level_start_index, a.pred_depth, a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn, a.B, a.Ncam, a.S, a.M, \
+                 a.L, a.Q, a.P, a.Za, a.DC, a.d0, a.dstep, a.head_minor & 3, a.HS, stage ? 1 : 0, a.slots)
+#define FBBEV_DA_UNIT(DH_)                                                                                       \
+    do {                                                                                                         \
+        if (et == 1) FBBEV_DA_UNIT_W(DH_, true, true, 1); else if (et == 2) FBBEV_DA_UNIT_W(DH_, true, true, 2); \
+        else if (qi) FBBEV_DA_UNIT_W(DH_, true, true, 0); else if (wide) FBBEV_DA_UNIT_W(DH_, true, false, 0);   \
+        else FBBEV_DA_UNIT_W(DH_, false, false, 0);                                                              \
+    } while (0)
+    FBBEV_DA_DH_FWD(a.Dh, FBBEV_DA_UNIT);
+#undef FBBEV_DA_UNIT_W
+#undef FBBEV_DA_UNIT
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// token rows -> slots: the unit-per-lane kernel where the rows allow it, else the lane-per-channel kernel
+static int da_fwd_rows(const da_args& a) {
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
+    if (!da_anchors_ok(a)) return FBBEV_E_UNSUPPORTED;
+    if (a.dstep == 0.f) return FBBEV_E_BADARG;
+    const long long n = (long long)a.B * a.Q * a.M * a.Dh;
+    if (n == 0) return 0;
+    if (!da_fwd_present(a)) return FBBEV_E_BADARG;
+    if (a.HS < a.Dh) return FBBEV_E_BADARG;
+    const bool wide = a.HS % 4 == 0 && a.HS >= (a.Dh + 3) / 4 * 4 && aligned16(a.value);
+    const bool qi = (a.head_minor & 4) != 0;                       // value rows stored [chunk][head][4 floats]
+    if (qi && !wide) return FBBEV_E_UNSUPPORTED;
+    const bool al8 = ((uintptr_t)a.value & 7) == 0 && da_pairs_aligned(a);
+    const bool fits32 = (long long)a.B * a.Ncam * a.S * a.M * a.HS * 4 < (1ll << 32);   // unit kernels: 32-bit byte offsets into value
+    if (qi && !fits32) return FBBEV_E_UNSUPPORTED;
+    if (al8 && fits32 && a.HS % 2 == 0 && (a.Dh == 10 || a.Dh == 8 || a.Dh == 16 || a.Dh == 32)) return da_fwd_unit_launch(a, wide, qi, 0);
+    long long blocks = (n + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    FBBEV_LAUNCH(k_da_cross_attn_fwd, blocks, 256, 0, a.stream, n, a.value, a.spatial_shapes, a.level_start_index, a.pred_depth,
+                 a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn, a.B, a.Ncam, a.S, a.M, a.Dh, a.L, a.Q, a.P, a.Za, a.DC, a.d0,
+                 a.dstep, a.head_minor & 7, a.HS, a.slots);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int fbbev_da_cross_attn_fwd(const float* value, const int64_t* spatial_shapes,
+                                       const int64_t* level_start_index, const float* pred_depth,
+                                       const float* ref_cam, const uint8_t* mask, const float* qdepth,
+                                       const float* offsets, const float* attn, int B, int Ncam, int S, int M,
+                                       int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
+                                       int head_minor, int head_stride, float* slots, fbbev_stream_t stream_) {
+    return da_fwd_rows(da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, 0, (fbbev_rt_stream)stream_,
+                                  value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                  slots}));
+}
+
 // 16-bit token rows (value_elem_type 1 = bf16, 2 = f16): chunk-major rows of 8-element pieces, unit-per-lane kernel only
 extern "C" int fbbev_da_cross_attn_fwd_e(const void* value, const int64_t* spatial_shapes,
                                          const int64_t* level_start_index, const float* pred_depth,
@@ -1430,118 +1556,45 @@ extern "C" int fbbev_da_cross_attn_fwd_e(const void* value, const int64_t* spati
                                          int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                                          int head_minor, int head_stride, int value_elem_type, float* slots,
                                          fbbev_stream_t stream_) {
-    if (value_elem_type == 0)
-        return fbbev_da_cross_attn_fwd(static_cast<const float*>(value), spatial_shapes, level_start_index, pred_depth, ref_cam,
-                                       mask, qdepth, offsets, attn, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor,
-                                       head_stride, slots, stream_);
+    da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, 0, (fbbev_rt_stream)stream_,
+                           static_cast<const float*>(value), nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask,
+                           qdepth, offsets, attn, slots});
+    if (value_elem_type == 0) return da_fwd_rows(a);
     if (value_elem_type != 1 && value_elem_type != 2) return FBBEV_E_BADARG;
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0)
-        return FBBEV_E_BADARG;
-    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
+    if (!da_anchors_ok(a)) return FBBEV_E_UNSUPPORTED;
     if (dstep == 0.f) return FBBEV_E_BADARG;
-    const long long units = (long long)B * Q * M;
-    if (units == 0) return 0;
-    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth ||
-        !offsets || !attn || !slots) return FBBEV_E_BADARG;
-    const int HS = head_stride;
+    if ((long long)B * Q * M == 0) return 0;
+    if (!da_fwd_present(a)) return FBBEV_E_BADARG;
+    a.HS = head_stride;                                            // 16-bit rows state their stride: 0 does not mean Dh here
     // chunk-major rows of 8-element pieces covering Dh; 32-bit byte offsets; 8-byte aligned offsets / slots
-    if (!(head_minor & 4) || HS % 8 != 0 || HS < (Dh + 7) / 8 * 8 || !aligned16(value) ||
-        (((uintptr_t)offsets | (uintptr_t)slots) & 7) != 0 || (long long)B * Ncam * S * M * HS * 2 >= (1ll << 32) ||
-        !(Dh == 10 || Dh == 8 || Dh == 16 || Dh == 32)) return FBBEV_E_UNSUPPORTED;
-    long long ub = ((units + 255) / 256 + 7) / 8 * 8;
-    if (ub > 65536) ub = 65536;
-    const int LP = L * P;
-    const bool stage = !(head_minor & 2) && LP % 4 == 0 && LP <= 36 && aligned16(attn);
-    const size_t lds = stage ? (size_t)256 * (LP + 1) * sizeof(float) : 0;
-#define FBBEV_DA_UNIT16(DH_, ET_)                                                                                    \
-    FBBEV_LAUNCH((k_da_cross_attn_fwd_unit<DH_, true, true, ET_>), ub, 256, lds, (fbbev_rt_stream)stream_, units, value, \
-                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M,  \
-                 L, Q, P, Za, DC, d0, dstep, head_minor & 3, HS, stage ? 1 : 0, slots)
-#define FBBEV_DA_UNIT16_ET(DH_) do { if (value_elem_type == 1) FBBEV_DA_UNIT16(DH_, 1); else FBBEV_DA_UNIT16(DH_, 2); } while (0)
-    if (Dh == 10) FBBEV_DA_UNIT16_ET(10);
-    else if (Dh == 8) FBBEV_DA_UNIT16_ET(8);
-    else if (Dh == 16) FBBEV_DA_UNIT16_ET(16);
-    else FBBEV_DA_UNIT16_ET(32);
-#undef FBBEV_DA_UNIT16_ET
-#undef FBBEV_DA_UNIT16
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int fbbev_da_cross_attn_fwd(const float* value, const int64_t* spatial_shapes,
-                                       const int64_t* level_start_index, const float* pred_depth,
-                                       const float* ref_cam, const uint8_t* mask, const float* qdepth,
-                                       const float* offsets, const float* attn, int B, int Ncam, int S, int M,
-                                       int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
-                                       int head_minor, int head_stride, float* slots, fbbev_stream_t stream_) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0)
-        return FBBEV_E_BADARG;
-    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
-    if (dstep == 0.f) return FBBEV_E_BADARG;
-    const long long n = (long long)B * Q * M * Dh;
-    if (n == 0) return 0;
-    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth ||
-        !offsets || !attn || !slots) return FBBEV_E_BADARG;
-    const int HS = head_stride == 0 ? Dh : head_stride;
-    if (HS < Dh) return FBBEV_E_BADARG;
-    const bool wide = HS % 4 == 0 && HS >= (Dh + 3) / 4 * 4 && aligned16(value);
-    const bool qi = (head_minor & 4) != 0;                         // value rows stored [chunk][head][4 floats]
-    if (qi && !wide) return FBBEV_E_UNSUPPORTED;
-    const bool al8 = (((uintptr_t)value | (uintptr_t)offsets | (uintptr_t)slots) & 7) == 0;
-    const bool fits32 = (long long)B * Ncam * S * M * HS * 4 < (1ll << 32);        // unit kernels: 32-bit byte offsets into value
-    if (qi && !fits32) return FBBEV_E_UNSUPPORTED;
-    if (al8 && fits32 && HS % 2 == 0 && (Dh == 10 || Dh == 8 || Dh == 16 || Dh == 32)) {   // a lane owns all Dh channels of a (b,q,head) unit
-        const long long units = (long long)B * Q * M;
-        long long ub = ((units + 255) / 256 + 7) / 8 * 8;         // XCD-contiguous order: a multiple of 8 workgroups
-        if (ub > 65536) ub = 65536;
-        // attention weights in (B,Q,M,L,P) staged through LDS ([256][L*P+1] floats) when 4 workgroups per CU still fit
-        const int LP = L * P;
-        const bool stage = !(head_minor & 2) && LP % 4 == 0 && LP <= 36 && aligned16(attn);
-        const size_t lds = stage ? (size_t)256 * (LP + 1) * sizeof(float) : 0;
-#define FBBEV_DA_UNIT_W(DH_, W_, Q_)                                                                                \
-    FBBEV_LAUNCH((k_da_cross_attn_fwd_unit<DH_, W_, Q_>), ub, 256, lds, (fbbev_rt_stream)stream_, units, value,      \
-                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M, \
-                 L, Q, P, Za, DC, d0, dstep, head_minor & 3, HS, stage ? 1 : 0, slots)
-#define FBBEV_DA_UNIT(DH_) do { if (qi) FBBEV_DA_UNIT_W(DH_, true, true); else if (wide) FBBEV_DA_UNIT_W(DH_, true, false); \
-                                else FBBEV_DA_UNIT_W(DH_, false, false); } while (0)
-        if (Dh == 10) FBBEV_DA_UNIT(10);
-        else if (Dh == 8) FBBEV_DA_UNIT(8);
-        else if (Dh == 16) FBBEV_DA_UNIT(16);
-        else FBBEV_DA_UNIT(32);
-#undef FBBEV_DA_UNIT_W
-#undef FBBEV_DA_UNIT
-        FBBEV_CHECK_LAUNCH();
-        return 0;
-    }
-    long long blocks = (n + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    FBBEV_LAUNCH(k_da_cross_attn_fwd, blocks, 256, 0, (fbbev_rt_stream)stream_, n, value, spatial_shapes,
-                 level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M, Dh, L, Q, P,
-                 Za, DC, d0, dstep, head_minor & 7, HS, slots);
-    FBBEV_CHECK_LAUNCH();
-    return 0;
+    if (!(head_minor & 4) || a.HS % 8 != 0 || a.HS < (Dh + 7) / 8 * 8 || !aligned16(value) || !da_pairs_aligned(a) ||
+        (long long)B * Ncam * S * M * a.HS * 2 >= (1ll << 32) || !(Dh == 10 || Dh == 8 || Dh == 16 || Dh == 32))
+        return FBBEV_E_UNSUPPORTED;
+    return da_fwd_unit_launch(a, true, true, value_elem_type);
 }
 
 static bool da_pipe_disabled() {
     static const bool off = fbbev_env_int("FBBEV_DA_PIPE", 1) == 0;   // A/B timing knob, read once
     return off;
 }
-static bool da_pipe_shape_ok(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int head_minor, int HS) {
-    const long long tokens = (long long)B * Ncam * S;
-    const int LP = L * P;
-    return (long long)B * Q * M > 0 && (head_minor & 7) == (1 | 4) &&                // head-minor offsets, (B,Q,M,L,P) attn, chunk-major rows
-           Za == 4 && P % 4 == 0 && (Dh == 8 || Dh == 10) && HS == (Dh + 3) / 4 * 4 && LP % 4 == 0 && LP <= 36 &&
-           (tokens + 1) * M * HS * 4 < (1ll << 32);                                  // 32-bit byte offsets incl. the zero token
+static bool da_pipe_shape_ok(const da_args& a) {
+    const long long tokens = (long long)a.B * a.Ncam * a.S;
+    const int LP = a.L * a.P;
+    return (long long)a.B * a.Q * a.M > 0 && (a.head_minor & 7) == (1 | 4) &&        // head-minor offsets, (B,Q,M,L,P) attn, chunk-major rows
+           a.Za == 4 && a.P % 4 == 0 && (a.Dh == 8 || a.Dh == 10) && a.HS == (a.Dh + 3) / 4 * 4 && LP % 4 == 0 && LP <= 36 &&
+           (tokens + 1) * a.M * a.HS * 4 < (1ll << 32);                              // 32-bit byte offsets incl. the zero token
 }
 extern "C" int fbbev_da_cross_attn_fwd_zt_fuses_softmax(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za,
                                                         int head_minor, int head_stride) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0) return 0;
-    return (!da_pipe_disabled() && da_pipe_shape_ok(B, Ncam, S, M, Dh, L, Q, P, Za, head_minor, head_stride == 0 ? Dh : head_stride)) ? 1 : 0;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, 1, 0.f, 0.f, head_minor, head_stride, 0});
+    if (!da_dims_ok(a, 1, 0)) return 0;
+    return (!da_pipe_disabled() && da_pipe_shape_ok(a)) ? 1 : 0;
 }
 
 // Pipelined forward (k_da_cross_attn_fwd_pipe): the value buffer holds ONE MORE token than B*Ncam*S -- token index
 // B*Ncam*S, M*HS floats, all +0.0f -- which padded corners and out-of-image samples read instead of branching around their
-// loads.  Shapes outside the pipelined kernel's preconditions run fbbev_da_cross_attn_fwd on the same buffer.
+// loads.  Shapes outside the pipelined kernel's preconditions run da_fwd_rows on the same buffer.
 extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spatial_shapes,
                                           const int64_t* level_start_index, const float* pred_depth,
                                           const float* ref_cam, const uint8_t* mask, const float* qdepth,
@@ -1549,22 +1602,20 @@ extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spa
                                           int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                                           int head_minor, int head_stride, int bev_w, float* slots,
                                           fbbev_stream_t stream_) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w < 0)
-        return FBBEV_E_BADARG;
-    const int HS = head_stride == 0 ? Dh : head_stride;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, bev_w, (fbbev_rt_stream)stream_,
+                                 value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 slots});
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
     const int LP = L * P;
     const long long units = (long long)B * Q * M;
     const long long tokens = (long long)B * Ncam * S;
-    const bool pipe = value && offsets && attn && slots && dstep != 0.f &&
-                      da_pipe_shape_ok(B, Ncam, S, M, Dh, L, Q, P, Za, head_minor, HS) && aligned16(attn) && aligned16(value) &&
-                      (((uintptr_t)offsets | (uintptr_t)slots) & 7) == 0;
+    const bool pipe = value && offsets && attn && slots && dstep != 0.f && da_pipe_shape_ok(a) && aligned16(attn) &&
+                      aligned16(value) && da_pairs_aligned(a);
     if (!pipe || da_pipe_disabled()) {
         if (head_minor & FBBEV_DA_ATTN_LOGITS) return FBBEV_E_UNSUPPORTED;     // only the pipelined kernel fuses the softmax
-        return fbbev_da_cross_attn_fwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
-                                       attn, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, slots,
-                                       stream_);
+        return da_fwd_rows(a);
     }
-    if (!spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth) return FBBEV_E_BADARG;
+    if (!da_geometry_present(a)) return FBBEV_E_BADARG;
     // patch mapping (a workgroup = the 8 heads of an 8 x 4 patch of the BEV grid): needs the grid's row length
     static const bool patch_off = fbbev_env_int("FBBEV_DA_PATCH", 1) == 0;   // A/B timing knob, read once
     const int pw = (!patch_off && bev_w > 0 && M == 8 && Q % bev_w == 0) ? bev_w : 0;
@@ -1572,11 +1623,11 @@ extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spa
     long long ub = (wgs + 7) / 8 * 8;                             // XCD-contiguous order: a multiple of 8 workgroups
     if (ub > 65536) ub = 65536;
     const size_t lds = (size_t)256 * (LP + 1) * sizeof(float);
-    const unsigned zero_bytes = (unsigned)(tokens * M * HS * 4);
+    const unsigned zero_bytes = (unsigned)(tokens * M * a.HS * 4);
 #define FBBEV_DA_PIPE(DH_, WPS_)                                                                                     \
-    FBBEV_LAUNCH((k_da_cross_attn_fwd_pipe<DH_, 4, WPS_>), ub, 256, lds, (fbbev_rt_stream)stream_, units, value,         \
-                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M, L, \
-                 Q, P, DC, d0, dstep, HS, zero_bytes, (head_minor & FBBEV_DA_ATTN_LOGITS) ? 1 : 0, pw, slots)
+    FBBEV_LAUNCH((k_da_cross_attn_fwd_pipe<DH_, 4, WPS_>), ub, 256, lds, a.stream, units, value, spatial_shapes,         \
+                 level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, M, L, Q, P, DC, d0,   \
+                 dstep, a.HS, zero_bytes, (head_minor & FBBEV_DA_ATTN_LOGITS) ? 1 : 0, pw, slots)
     static const int wps = fbbev_env_int("FBBEV_DA_PIPE_WPS", 2);   // tuning knob, read once (3: 168 registers, spills outside the loop)
     if (Dh == 10) { if (wps == 2) FBBEV_DA_PIPE(10, 2); else FBBEV_DA_PIPE(10, 3); }
     else { if (wps == 2) FBBEV_DA_PIPE(8, 2); else FBBEV_DA_PIPE(8, 3); }
@@ -1586,31 +1637,28 @@ extern "C" int fbbev_da_cross_attn_fwd_zt(const float* value, const int64_t* spa
 }
 
 // ---- fbbev_da_cross_attn_fused: query rows -> slots in one kernel (da_fused_kernels.h)
-static bool da_fused_shape_ok(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int bev_w) {
-    if (M != 8 || (Dh != 10 && Dh != 8) || P != FBBEV_DAF_P || Za != FBBEV_DAF_ZA || L < 1 || bev_w <= 0 || Q % bev_w != 0 || Ncam > 32) return false;
-    if (L > FBBEV_DAF_MAXL || fbbev_daf_lds_bytes(M * Dh, 8, Ncam) > 160 * 1024) return false;
-    return (long long)S * Dh * 4 < (1ll << 31) && S < (1 << 24);                     // 32-bit byte offsets inside a head plane, 24-bit token indices
+static bool da_fused_shape_ok(const da_args& a) {
+    if (a.M != 8 || (a.Dh != 10 && a.Dh != 8) || a.P != FBBEV_DAF_P || a.Za != FBBEV_DAF_ZA || a.L < 1 || a.bev_w <= 0 ||
+        a.Q % a.bev_w != 0 || a.Ncam > 32) return false;
+    if (a.L > FBBEV_DAF_MAXL || fbbev_daf_lds_bytes(a.M * a.Dh, 8, a.Ncam) > 160 * 1024) return false;
+    return (long long)a.S * a.Dh * 4 < (1ll << 31) && a.S < (1 << 24);               // 32-bit byte offsets inside a head plane, 24-bit token indices
 }
 extern "C" int fbbev_da_cross_attn_fused_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int bev_w) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0) return 0;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, 1, 0.f, 0.f, 0, 0, bev_w});
+    if (!da_dims_ok(a, 1, 0)) return 0;
     static const bool off = fbbev_env_int("FBBEV_DA_FUSED", 1) == 0;   // A/B timing knob, read once
-    return (!off && da_fused_shape_ok(B, Ncam, S, M, Dh, L, Q, P, Za, bev_w)) ? 1 : 0;
+    return (!off && da_fused_shape_ok(a)) ? 1 : 0;
 }
-static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                    const float* pred_depth, const float* ref_cam, const uint8_t* mask, const float* qdepth,
-                                    const float* query, long long query_row_stride, const float* addend,
-                                    long long addend_row_stride, long long addend_period, const void* offsets_fragments,
-                                    const float* offsets_bias, const void* attn_fragments, const float* attn_bias, int B,
-                                    int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
-                                    int bev_w, int min_level_width, float* slots, fbbev_stream_t stream_, fbbev_daf_outproj op,
-                                    int elem_type = 0) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w < 0 ||
-        elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
+// a: the planes, the geometry and the output (offsets and weights are projected in the kernel from the query rows' operands here)
+static int da_fused(const da_args& a, const float* query, long long query_row_stride, const float* addend,
+                    long long addend_row_stride, long long addend_period, const void* offsets_fragments, const float* offsets_bias,
+                    const void* attn_fragments, const float* attn_bias, int min_level_width, fbbev_daf_outproj op, int elem_type) {
+    if (!da_dims_ok(a, 0, 0) || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
     if (elem_type != 0 && op.w_frag) return FBBEV_E_UNSUPPORTED;          // 16-bit planes: the plain sampler only
-    if (Q == 0) return 0;
-    if (!planes || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !query ||
-        !offsets_fragments || !offsets_bias || !attn_fragments || !attn_bias || !slots || dstep == 0.f) return FBBEV_E_BADARG;
-    const int E = M * Dh;
+    if (a.Q == 0) return 0;
+    if (!a.planes || !da_geometry_present(a) || !query || !offsets_fragments || !offsets_bias || !attn_fragments || !attn_bias ||
+        !a.slots || a.dstep == 0.f) return FBBEV_E_BADARG;
+    const int E = a.M * a.Dh;
     if (query_row_stride == 0) query_row_stride = E;
     if (query_row_stride < E) return FBBEV_E_BADARG;
     if (addend) {
@@ -1620,16 +1668,16 @@ static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_
     } else { addend_row_stride = 0; addend_period = 1; }
     // min_level_width: the caller's host-side knowledge of the narrowest level (the x-corner runs are clamped into a row of at
     // least two tokens); the shapes themselves stay on the device
-    if (!da_fused_shape_ok(B, Ncam, S, M, Dh, L, Q, P, Za, bev_w) || min_level_width < 2) return FBBEV_E_UNSUPPORTED;
+    if (!da_fused_shape_ok(a) || min_level_width < 2) return FBBEV_E_UNSUPPORTED;
     if (query_row_stride % 4 != 0 || addend_row_stride % 4 != 0 || !aligned16(query) || (addend && !aligned16(addend)) ||
-        !aligned16(offsets_fragments) || !aligned16(attn_fragments) || !aligned16(offsets_bias) || ((uintptr_t)planes & 7) != 0 ||
-        ((uintptr_t)slots & 7) != 0)
+        !aligned16(offsets_fragments) || !aligned16(attn_fragments) || !aligned16(offsets_bias) || ((uintptr_t)a.planes & 7) != 0 ||
+        !da_pairs_aligned(a))
         return FBBEV_E_UNSUPPORTED;
     // heads per workgroup: 4 = two 256-thread workgroups per patch and per CU (one's prologue + projections under the other's
     // samples), 8 = one 512-thread workgroup per patch (FBBEV_DA_FUSED_HW, read once)
     FBBEV_KNOB_ONCE(int, hw_env, fbbev_env_int("FBBEV_DA_FUSED_HW", 4) == 8 ? 8 : 4);   // (the emulator tests run both forms)
     const int hw = op.w_frag ? 8 : (elem_type ? 4 : hw_env); // the output_proj + LayerNorm tail needs all 8 heads of a query in one workgroup
-    const long long wgs = (long long)B * ((bev_w + 7) / 8) * ((Q / bev_w + 7) / 8) * (8 / hw);
+    const long long wgs = (long long)a.B * ((a.bev_w + 7) / 8) * ((a.Q / a.bev_w + 7) / 8) * (8 / hw);
     const long long grid = (wgs + 7) / 8 * 8;
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     // round 5: floats of a wave's LDS staging region for coarse levels (the 8 x 22 level of BASELINE configs[2] at Dh = 10: 1 760);
@@ -1639,8 +1687,8 @@ static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_
     // (fbbev_da_cross_attn_fused_supported budgets LDS WITHOUT the staging region -- a launch whose staged layout does not
     // fit (8 heads per workgroup with ~25+ cameras) runs unstaged instead of failing after the probe said yes)
     int stage_eff = stage_floats;
-    if (fbbev_daf_lds_bytes(E, hw, Ncam, stage_eff) > 160 * 1024) stage_eff = 0;
-    const size_t lds = fbbev_daf_lds_bytes(E, hw, Ncam, stage_eff);
+    if (fbbev_daf_lds_bytes(E, hw, a.Ncam, stage_eff) > 160 * 1024) stage_eff = 0;
+    const size_t lds = fbbev_daf_lds_bytes(E, hw, a.Ncam, stage_eff);
     if (lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
     static const bool pre_off = fbbev_env_int("FBBEV_DA_FUSED_PRE", 1) == 0;   // A/B knob, read once
     static const int diag = [] {                                                         // timing diagnostics (wrong results), read once
@@ -1651,35 +1699,34 @@ static int da_cross_attn_fused_impl(const float* planes, const int64_t* spatial_
     const int stage_arg = stage_eff | (pre_off ? 0x40000000 : 0) | (diag << 24);
 #define FBBEV_DA_FUSED(DH_, NP_, HW_) FBBEV_DA_FUSED3(DH_, NP_, HW_, false, 0)
 #define FBBEV_DA_FUSED2(DH_, NP_, HW_, OP_) FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, 0)
-#define FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, ET_)                                                                                                     \
-    FBBEV_LAUNCH_DYN_LDS((k_da_cross_attn_fused<DH_, 8, NP_, HW_, OP_, ET_>), grid, 64 * HW_, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes, \
-                         level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend,                                      \
-                         addend_row_stride, addend_period, static_cast<const unsigned short*>(offsets_fragments),                                    \
-                         offsets_bias, static_cast<const unsigned short*>(attn_fragments), attn_bias, B, Ncam, S, L, Q,                              \
-                         bev_w, DC, d0, dstep, slots, op, stage_arg)
+#define FBBEV_DA_FUSED3(DH_, NP_, HW_, OP_, ET_) FBBEV_DA_FUSED4(DH_, NP_, HW_, OP_, ET_, false)
+#define FBBEV_DA_FUSED4(DH_, NP_, HW_, OP_, ET_, DIAG_)                                                                                    \
+    FBBEV_LAUNCH_DYN_LDS((k_da_cross_attn_fused<DH_, 8, NP_, HW_, OP_, ET_, DIAG_>), grid, 64 * HW_, lds, a.stream, a.planes,              \
+                         a.spatial_shapes, a.level_start_index, a.pred_depth, a.ref_cam, a.mask, a.qdepth, query, query_row_stride,        \
+                         addend, addend_row_stride, addend_period, static_cast<const unsigned short*>(offsets_fragments), offsets_bias,    \
+                         static_cast<const unsigned short*>(attn_fragments), attn_bias, a.B, a.Ncam, a.S, a.L, a.Q, a.bev_w, a.DC, a.d0,   \
+                         a.dstep, a.slots, op, stage_arg)
     // (three samples in flight per lane -- FBBEV_DA_FUSED_NP=3 in round 4 -- measured no gain and, with the staged levels' second
     // sample loop, no longer fits the register file: the instantiations are gone, two in flight is the form)
     // (round 5, 16-bit planes: three / four samples in flight per lane -- 234 registers / 256 with 5 spills -- measured 401.3 / 405.1 us
     // against 402.1 us with two at BASELINE configs[2]: the sampler is not waiting for its gathers; profiles/r05_exp_da_fused_where.md)
     if (elem_type == 1) {              // round 5: camera tokens stored as bf16 / fp16 head planes (fp32 products and sums)
-        if (Dh == 10) FBBEV_DA_FUSED3(10, 2, 4, false, 1); else FBBEV_DA_FUSED3(8, 2, 4, false, 1);
+        if (a.Dh == 10) FBBEV_DA_FUSED3(10, 2, 4, false, 1); else FBBEV_DA_FUSED3(8, 2, 4, false, 1);
     } else if (elem_type == 2) {
-        if (Dh == 10) FBBEV_DA_FUSED3(10, 2, 4, false, 2); else FBBEV_DA_FUSED3(8, 2, 4, false, 2);
+        if (a.Dh == 10) FBBEV_DA_FUSED3(10, 2, 4, false, 2); else FBBEV_DA_FUSED3(8, 2, 4, false, 2);
     } else if (op.w_frag) {
-        if (Dh == 10) FBBEV_DA_FUSED2(10, 2, 8, true); else FBBEV_DA_FUSED2(8, 2, 8, true);
+        if (a.Dh == 10) FBBEV_DA_FUSED2(10, 2, 8, true); else FBBEV_DA_FUSED2(8, 2, 8, true);
     } else if (hw == 8) {
-        if (Dh == 10) FBBEV_DA_FUSED(10, 2, 8); else FBBEV_DA_FUSED(8, 2, 8);
-    } else if (diag && Dh == 10) {     // FBBEV_DA_FUSED_DIAG: the instantiation with the timing-diagnostic bits (wrong results by design)
-        FBBEV_LAUNCH_DYN_LDS((k_da_cross_attn_fused<10, 8, 2, 4, false, 0, true>), grid, 256, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,
-                             level_start_index, pred_depth, ref_cam, mask, qdepth, query, query_row_stride, addend, addend_row_stride, addend_period,
-                             static_cast<const unsigned short*>(offsets_fragments), offsets_bias, static_cast<const unsigned short*>(attn_fragments),
-                             attn_bias, B, Ncam, S, L, Q, bev_w, DC, d0, dstep, slots, op, stage_arg);
+        if (a.Dh == 10) FBBEV_DA_FUSED(10, 2, 8); else FBBEV_DA_FUSED(8, 2, 8);
+    } else if (diag && a.Dh == 10) {   // FBBEV_DA_FUSED_DIAG: the instantiation with the timing-diagnostic bits (wrong results by design)
+        FBBEV_DA_FUSED4(10, 2, 4, false, 0, true);
     } else {
-        if (Dh == 10) FBBEV_DA_FUSED(10, 2, 4); else FBBEV_DA_FUSED(8, 2, 4);
+        if (a.Dh == 10) FBBEV_DA_FUSED(10, 2, 4); else FBBEV_DA_FUSED(8, 2, 4);
     }
 #undef FBBEV_DA_FUSED
 #undef FBBEV_DA_FUSED2
 #undef FBBEV_DA_FUSED3
+#undef FBBEV_DA_FUSED4
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -1691,10 +1738,10 @@ extern "C" int fbbev_da_cross_attn_fused(const float* planes, const int64_t* spa
                                          const float* offsets_bias, const void* attn_fragments, const float* attn_bias, int B,
                                          int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                                          int bev_w, int min_level_width, float* slots, fbbev_stream_t stream_) {
-    return da_cross_attn_fused_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, query,
-                                    query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
-                                    attn_fragments, attn_bias, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, bev_w, min_level_width,
-                                    slots, stream_, fbbev_daf_outproj{nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.f});
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, 0, 0, bev_w, (fbbev_rt_stream)stream_, nullptr, planes,
+                                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, nullptr, nullptr, slots});
+    return da_fused(a, query, query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
+                    attn_fragments, attn_bias, min_level_width, fbbev_daf_outproj{nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.f}, 0);
 }
 // The same kernel on 16-bit head planes (elem_type 1 bf16, 2 fp16; 0 = the entry above): the camera-token STORAGE option of the
 // cross-attention (fbbev_rows_linear_x3_planes_e writes them); every product and sum stays fp32.
@@ -1705,10 +1752,12 @@ extern "C" int fbbev_da_cross_attn_fused_e(const void* planes, int elem_type, co
                                          const float* offsets_bias, const void* attn_fragments, const float* attn_bias, int B,
                                          int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
                                          int bev_w, int min_level_width, float* slots, fbbev_stream_t stream_) {
-    return da_cross_attn_fused_impl(static_cast<const float*>(planes), spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth,
-                                    query, query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
-                                    attn_fragments, attn_bias, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, bev_w, min_level_width,
-                                    slots, stream_, fbbev_daf_outproj{nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.f}, elem_type);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, 0, 0, bev_w, (fbbev_rt_stream)stream_, nullptr,
+                                 static_cast<const float*>(planes), spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth,
+                                 nullptr, nullptr, slots});
+    return da_fused(a, query, query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
+                    attn_fragments, attn_bias, min_level_width, fbbev_daf_outproj{nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0.f},
+                    elem_type);
 }
 // ... followed, inside the same workgroups (8 heads per workgroup), by output_proj + residual + LayerNorm: out rows instead of slots
 extern "C" int fbbev_da_cross_attn_fused_ln(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
@@ -1720,18 +1769,19 @@ extern "C" int fbbev_da_cross_attn_fused_ln(const float* planes, const int64_t* 
                                             long long residual_row_stride, const float* ln_weight, const float* ln_bias, float ln_eps,
                                             int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
                                             float dstep, int bev_w, int min_level_width, float* out, fbbev_stream_t stream_) {
+    // (the tail's own checks come before the shared ones)
     if (!out_fragments || !out_bias || !ln_weight || !ln_bias || !(ln_eps >= 0.f) || M <= 0 || Dh <= 0) return FBBEV_E_BADARG;
     const int E = M * Dh;
     if (residual && residual_row_stride == 0) residual_row_stride = E;
     if (residual && residual_row_stride < E) return FBBEV_E_BADARG;
     if (E % 16 != 0 || !aligned16(out_fragments) || !aligned16(out_bias) || !aligned16(ln_weight) || !aligned16(ln_bias) ||
         !aligned16(out) || (residual && (!aligned16(residual) || residual_row_stride % 4 != 0))) return FBBEV_E_UNSUPPORTED;
-    return da_cross_attn_fused_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, query,
-                                    query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
-                                    attn_fragments, attn_bias, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, bev_w, min_level_width,
-                                    out, stream_,
-                                    fbbev_daf_outproj{static_cast<const unsigned short*>(out_fragments), out_bias, residual,
-                                                      residual_row_stride, ln_weight, ln_bias, ln_eps});
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, 0, 0, bev_w, (fbbev_rt_stream)stream_, nullptr, planes,
+                                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, nullptr, nullptr, out});
+    return da_fused(a, query, query_row_stride, addend, addend_row_stride, addend_period, offsets_fragments, offsets_bias,
+                    attn_fragments, attn_bias, min_level_width,
+                    fbbev_daf_outproj{static_cast<const unsigned short*>(out_fragments), out_bias, residual, residual_row_stride,
+                                      ln_weight, ln_bias, ln_eps}, 0);
 }
 
 // ---- Z-mean / Z-sum of a materialised (B*C, Z, Y*X) volume (training path; k_volume_zreduce)
@@ -1782,32 +1832,34 @@ extern "C" int fbbev_value_rows_to_head_planes(const float* value, long long n_t
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
-extern "C" int fbbev_da_cross_attn_fwd_planes_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0) return 0;
+static bool da_fwd_planes_shape_ok(const da_args& a) {
     static const bool off = fbbev_env_int("FBBEV_DA_FWD_PLANES", 1) == 0;   // A/B timing knob, read once
-    return (!off && M == 8 && (Dh == 10 || Dh == 8) && P == FBBEV_DAF_P && Za == FBBEV_DAF_ZA && (long long)S * Dh * 4 < (1ll << 31) &&
-            fbbev_dfp_lds_bytes(Ncam) <= 156 * 1024) ? 1 : 0;
+    return !off && a.M == 8 && (a.Dh == 10 || a.Dh == 8) && a.P == FBBEV_DAF_P && a.Za == FBBEV_DAF_ZA &&
+           (long long)a.S * a.Dh * 4 < (1ll << 31) && fbbev_dfp_lds_bytes(a.Ncam) <= 156 * 1024;
+}
+extern "C" int fbbev_da_cross_attn_fwd_planes_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za) {
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, 1});
+    return (da_dims_ok(a, 1, 0) && da_fwd_planes_shape_ok(a)) ? 1 : 0;
 }
 extern "C" int fbbev_da_cross_attn_fwd_planes(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                               const float* pred_depth, const float* ref_cam, const uint8_t* mask, const float* qdepth,
                                               const float* offsets, const float* attn, int B, int Ncam, int S, int M, int Dh, int L,
                                               int Q, int P, int Za, int DC, float d0, float dstep, int head_minor, int bev_w,
                                               int min_level_width, float* slots, fbbev_stream_t stream_) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w < 0)
-        return FBBEV_E_BADARG;
-    if (Q == 0) return 0;
-    if (!planes || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets || !attn ||
-        !slots || dstep == 0.f) return FBBEV_E_BADARG;
-    if (!fbbev_da_cross_attn_fwd_planes_supported(B, Ncam, S, M, Dh, L, Q, P, Za) || min_level_width < 2 ||
-        ((uintptr_t)planes & 7) != 0 || ((uintptr_t)slots & 7) != 0 || ((uintptr_t)offsets & 7) != 0 || !aligned16(ref_cam) ||
-        !aligned16(qdepth) || ((uintptr_t)mask & 3) != 0) return FBBEV_E_UNSUPPORTED;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, 0, bev_w, (fbbev_rt_stream)stream_, nullptr,
+                                 planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, slots});
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
+    if (Q == 0) return 0;                                          // (before dstep is looked at)
+    if (!da_fwd_present(a) || dstep == 0.f) return FBBEV_E_BADARG;
+    if (!da_fwd_planes_shape_ok(a) || min_level_width < 2 || ((uintptr_t)planes & 7) != 0 || !da_pairs_aligned(a) ||
+        !aligned16(ref_cam) || !aligned16(qdepth) || ((uintptr_t)mask & 3) != 0) return FBBEV_E_UNSUPPORTED;
     const int gw = (bev_w > 0 && Q % bev_w == 0) ? bev_w : 0;
     const long long wgs = gw > 0 ? (long long)B * ((gw + 7) / 8) * ((Q / gw + 7) / 8) : (long long)B * ((Q + 63) / 64);
     const long long grid = (wgs + 7) / 8 * 8;
     if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = fbbev_dfp_lds_bytes(Ncam);
 #define FBBEV_DA_FWD_PLANES(DH_)                                                                                            \
-    FBBEV_LAUNCH_DYN_LDS((k_da_fwd_planes<DH_, 8>), grid, 512, lds, (fbbev_rt_stream)stream_, planes, spatial_shapes,       \
+    FBBEV_LAUNCH_DYN_LDS((k_da_fwd_planes<DH_, 8>), grid, 512, lds, a.stream, planes, spatial_shapes,                       \
                          level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, B, Ncam, S, L, Q, gw, DC, d0, \
                          dstep, head_minor & 3, slots)
     if (Dh == 10) FBBEV_DA_FWD_PLANES(10); else FBBEV_DA_FWD_PLANES(8);
@@ -1907,6 +1959,29 @@ extern "C" int fbbev_rows_to_head_planes(const float* rows, long long n_rows, in
     return 0;
 }
 
+// global atomics: the route every shape can take
+static int da_bwd_atomic(const da_args& a) {
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
+    if (!da_anchors_ok(a)) return FBBEV_E_UNSUPPORTED;
+    if (a.dstep == 0.f) return FBBEV_E_BADARG;
+    const long long units = (long long)a.B * a.Q * a.M;
+    if (units == 0) return 0;
+    if (!da_bwd_present(a)) return FBBEV_E_BADARG;
+    if (a.Dh > 32) return FBBEV_E_UNSUPPORTED;
+    if (a.HS < a.Dh) return FBBEV_E_BADARG;
+    if ((a.head_minor & 4) && a.HS % 4 != 0) return FBBEV_E_UNSUPPORTED;
+    if ((units * 32 + 255) / 256 >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+#define FBBEV_DA_BWD(GW_)                                                                                                \
+    FBBEV_LAUNCH(k_da_cross_attn_bwd<GW_>, (units * GW_ + 255) / 256, 256, 0, a.stream, units, a.value, a.spatial_shapes, \
+                 a.level_start_index, a.pred_depth, a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn, a.grad_slots, a.B,   \
+                 a.Ncam, a.S, a.M, a.Dh, a.L, a.Q, a.P, a.Za, a.DC, a.d0, a.dstep, a.head_minor & 7, a.HS, a.grad_value, \
+                 a.grad_pred_depth, a.grad_offsets, a.grad_attn)
+    if (a.Dh <= 16) FBBEV_DA_BWD(16);
+    else FBBEV_DA_BWD(32);
+#undef FBBEV_DA_BWD
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int fbbev_da_cross_attn_bwd(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                        const float* pred_depth, const float* ref_cam, const uint8_t* mask,
                                        const float* qdepth, const float* offsets, const float* attn,
@@ -1914,29 +1989,9 @@ extern "C" int fbbev_da_cross_attn_bwd(const float* value, const int64_t* spatia
                                        int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
                                        float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                        float* grad_attn, fbbev_stream_t stream_) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0)
-        return FBBEV_E_BADARG;
-    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
-    if (dstep == 0.f) return FBBEV_E_BADARG;
-    const long long units = (long long)B * Q * M;
-    if (units == 0) return 0;
-    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets ||
-        !attn || !grad_slots || !grad_value || !grad_pred_depth || !grad_offsets || !grad_attn) return FBBEV_E_BADARG;
-    if (Dh > 32) return FBBEV_E_UNSUPPORTED;
-    const int HS = head_stride == 0 ? Dh : head_stride;
-    if (HS < Dh) return FBBEV_E_BADARG;
-    if ((head_minor & 4) && HS % 4 != 0) return FBBEV_E_UNSUPPORTED;
-#define FBBEV_DA_BWD(GW_)                                                                                             \
-    FBBEV_LAUNCH(k_da_cross_attn_bwd<GW_>, (units * GW_ + 255) / 256, 256, 0, (fbbev_rt_stream)stream_, units, value,  \
-                 spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B,  \
-                 Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor & 7, HS, grad_value, grad_pred_depth,        \
-                 grad_offsets, grad_attn)
-    if ((units * 32 + 255) / 256 >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (Dh <= 16) FBBEV_DA_BWD(16);
-    else FBBEV_DA_BWD(32);
-#undef FBBEV_DA_BWD
-    FBBEV_CHECK_LAUNCH();
-    return 0;
+    return da_bwd_atomic(da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, 0, (fbbev_rt_stream)stream_,
+                                    value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                    nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn}));
 }
 
 // ---- deterministic form of the global-atomic kernel (k_da_cross_attn_bwd<GW, true>): det_ws = [fixed-point value words]
@@ -1962,26 +2017,24 @@ extern "C" int fbbev_da_cross_attn_bwd_ex(const float* value, const int64_t* spa
                                           float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                           float* grad_attn, int H0, int W0, int flags, void* det_ws, size_t det_ws_bytes,
                                           fbbev_stream_t stream_) {
-    if (!(flags & FBBEV_FLAG_DETERMINISTIC))
-        return fbbev_da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                                       grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, grad_value,
-                                       grad_pred_depth, grad_offsets, grad_attn, stream_);
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || H0 <= 0 || W0 <= 0)
-        return FBBEV_E_BADARG;
-    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, 0, (fbbev_rt_stream)stream_,
+                                 value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC)) return da_bwd_atomic(a);
+    if (!da_dims_ok(a, 0, 0) || H0 <= 0 || W0 <= 0) return FBBEV_E_BADARG;
+    if (!da_anchors_ok(a)) return FBBEV_E_UNSUPPORTED;
     if (dstep == 0.f) return FBBEV_E_BADARG;
     const long long units = (long long)B * Q * M;
     if (units == 0) return 0;
-    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets ||
-        !attn || !grad_slots || !grad_value || !grad_pred_depth || !grad_offsets || !grad_attn || !det_ws) return FBBEV_E_BADARG;
+    if (!da_bwd_present(a) || !det_ws) return FBBEV_E_BADARG;
     if (Dh > 32) return FBBEV_E_UNSUPPORTED;
-    const int HS = head_stride == 0 ? Dh : head_stride;
+    const int HS = a.HS;
     if (HS < Dh) return FBBEV_E_BADARG;
     if ((head_minor & 4) && HS % 4 != 0) return FBBEV_E_UNSUPPORTED;
     if ((units * 32 + 255) / 256 >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     if (det_ws_bytes < fbbev_da_cross_attn_bwd_det_ws_bytes(B, Ncam, S, M, HS, Q, Za, DC, H0, W0) || !aligned16(det_ws))
         return FBBEV_E_WORKSPACE;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    fbbev_rt_stream stream = a.stream;
     char* w = static_cast<char*>(det_ws);
     const size_t fix_b = da_glob_det_fix_bytes(B, Ncam, S, M, HS);
     const long long cbq = (long long)Ncam * B * Q;
@@ -2074,23 +2127,22 @@ static da_bwd_overrides da_bwd_env() { FBBEV_KNOB_ONCE(da_bwd_overrides, o, da_b
 // LDS bytes of the fixed-point planes of one workgroup: 68 KB = two workgroups per CU (FBBEV_DA_BWD_LDS_KB tunes it)
 static int da_bwd_plane_kb() { const int v = da_bwd_env().lds_kb; return v >= 8 && v <= 144 ? v : 68; }
 
-static bool da_bwd_tile_plan(int B, int Ncam, int S, int M, int Dh, int Q, int HS, int L, int P, const int32_t* level_hw,
-                             da_bwd_plan* pl) {
-    if (Dh > 16 || HS % 4 != 0 || HS > 16 || Q <= 0) return false;
-    if (P > FBBEV_DA_BWD_MAXP || !(Dh == 10 || Dh == 8 || Dh == 16 || Dh == 4)) return false;
-    int budget = (da_bwd_plane_kb() * 1024) / (HS * (int)sizeof(long long)) - 8;   // tokens per LDS plane (64-bit words, skewed)
+static bool da_bwd_tile_plan(const da_args& a, const int32_t* level_hw, da_bwd_plan* pl) {
+    if (a.Dh > 16 || a.HS % 4 != 0 || a.HS > 16 || a.Q <= 0) return false;
+    if (a.P > FBBEV_DA_BWD_MAXP || !(a.Dh == 10 || a.Dh == 8 || a.Dh == 16 || a.Dh == 4)) return false;
+    int budget = (da_bwd_plane_kb() * 1024) / (a.HS * (int)sizeof(long long)) - 8;   // tokens per LDS plane (64-bit words, skewed)
     { const int v = da_bwd_env().tokens; if (v > 0 && v < budget) budget = v; }   // tests: force bands
-    pl->n_regions = da_bwd_regions(L, level_hw, S, budget, pl->reg, 32);
+    pl->n_regions = da_bwd_regions(a.L, level_hw, a.S, budget, pl->reg, 32);
     if (pl->n_regions == 0) return false;
     int max_tok = 0;
     for (int r = 0; r < pl->n_regions; ++r) max_tok = pl->reg[r].tok1 - pl->reg[r].tok0 > max_tok ? pl->reg[r].tok1 - pl->reg[r].tok0 : max_tok;
-    const size_t plane = (size_t)FBBEV_DA_PLANE_WORDS(max_tok, HS) * sizeof(long long);
+    const size_t plane = (size_t)FBBEV_DA_PLANE_WORDS(max_tok, a.HS) * sizeof(long long);
     // two workgroups per CU in one round (512 of them)
-    long long want = (512 + (long long)B * M - 1) / ((long long)B * M);
+    long long want = (512 + (long long)a.B * a.M - 1) / ((long long)a.B * a.M);
     { const int v = da_bwd_env().chunks; if (v > 0) want = v; }
     if (want < 1) want = 1;
     if (want > 256) want = 256;
-    int qpc = (int)((Q + want - 1) / want);
+    int qpc = (int)((a.Q + want - 1) / want);
     // one lane per query the camera sees: 512 threads (measured 0.177 vs 0.208 ms at the shipped shape) unless the chunk is short
     pl->threads = qpc >= 512 ? 512 : 256;
     { const int v = da_bwd_env().threads; if (v == 256 || v == 512) pl->threads = v; }
@@ -2098,11 +2150,11 @@ static bool da_bwd_tile_plan(int B, int Ncam, int S, int M, int Dh, int Q, int H
     qpc = (qpc + ng - 1) / ng * ng;
     if (qpc > 65535) return false;                                                // chunk-relative 16-bit query ids
     pl->q_per_chunk = qpc;
-    pl->chunks = (Q + qpc - 1) / qpc;
+    pl->chunks = (a.Q + qpc - 1) / qpc;
     // + the camera's hit list, its counter, the block maximum
     pl->lds = plane + (size_t)((qpc + 1) & ~1) * 2 + (size_t)(1 + pl->threads / 64) * sizeof(int);
     if (pl->lds > (size_t)(da_bwd_plane_kb() + 12) * 1024) return false;
-    pl->ws_part = ((size_t)B * M * pl->chunks * Ncam * S * HS * sizeof(float) + 255) / 256 * 256;
+    pl->ws_part = ((size_t)a.B * a.M * pl->chunks * a.Ncam * a.S * a.HS * sizeof(float) + 255) / 256 * 256;
     // pre-pass (k_da_bwd_hitinfo; FBBEV_DA_BWD_PREPASS=0 turns it off): per (b, camera, query) the camera count and the Za depth
     // weights, behind the partials -- worth it when several region launches would each recompute them (configs[2] pyramid:
     // scatter 2.43 -> 2.22 ms, profiles/r03_exp_da_bwd_prepass.jsonl)
@@ -2110,7 +2162,7 @@ static bool da_bwd_tile_plan(int B, int Ncam, int S, int M, int Dh, int Q, int H
     pl->ws = pl->ws_part;
     if (da_bwd_env().prepass != 0 && pl->n_regions > 1) {
         pl->info_stride = 8;                                        // 1 + Za <= 8 floats (Za is checked at the launch)
-        pl->ws += (size_t)B * Ncam * Q * pl->info_stride * sizeof(float);
+        pl->ws += (size_t)a.B * a.Ncam * a.Q * pl->info_stride * sizeof(float);
     }
     return true;
 }
@@ -2127,25 +2179,24 @@ static int da_bwd_owned_mode() {
 // LDS bytes of an owned plane: 136 KB = one 512-thread workgroup per CU; fewer, larger regions beat two workgroups per CU
 // (configs[2] pyramid: 1.06 ms at 136 KB / 512 threads, 1.38 ms at 68 KB / 256, 2.18 ms at 68 KB / 512, 3.47 ms at 34 KB)
 static int da_own_plane_kb() { const int v = da_bwd_env().lds_kb; return v >= 8 && v <= 144 ? v : 136; }
-static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int HS, int L, int P, int Za, const int32_t* level_hw,
-                             da_own_plan* pl) {
+static bool da_own_plan_make(const da_args& a, const int32_t* level_hw, da_own_plan* pl) {
     const int mode = da_bwd_owned_mode();
     if (mode == 0) return false;
-    if (Dh > 16 || HS % 4 != 0 || HS > 16 || Q <= 0 || P > FBBEV_DA_BWD_MAXP || !(Dh == 10 || Dh == 8 || Dh == 16 || Dh == 4)) return false;
+    if (a.Dh > 16 || a.HS % 4 != 0 || a.HS > 16 || a.Q <= 0 || a.P > FBBEV_DA_BWD_MAXP || !(a.Dh == 10 || a.Dh == 8 || a.Dh == 16 || a.Dh == 4)) return false;
     pl->info_stride = 0;
-    if (Za > FBBEV_DA_HIT_ZA) return false;                             // a hit record holds 4 anchors
+    if (a.Za > FBBEV_DA_HIT_ZA) return false;                             // a hit record holds 4 anchors
     const size_t budget_bytes = (size_t)da_own_plane_kb() * 1024;
-    int budget = (int)(budget_bytes / (HS * sizeof(long long))) - 8;             // tokens per LDS plane (64-bit words, skewed)
+    int budget = (int)(budget_bytes / (a.HS * sizeof(long long))) - 8;             // tokens per LDS plane (64-bit words, skewed)
     { const int v = da_bwd_env().tokens; if (v > 0 && v < budget) budget = v; }   // tests: force bands
     // one region per level (a level larger than the budget: bands of rows), so that every level gets the copies its size allows
     da_region reg[24];
     int n = 0;
     if (!level_hw) {
-        if (S > budget) return false;
-        reg[n++] = {0, L, 0, S};
+        if (a.S > budget) return false;
+        reg[n++] = {0, a.L, 0, a.S};
     } else {
         int start = 0;
-        for (int l = 0; l < L; ++l) {
+        for (int l = 0; l < a.L; ++l) {
             const int h = level_hw[2 * l], w = level_hw[2 * l + 1];
             if (h <= 0 || w <= 0) return false;
             const int cnt = h * w, rows = cnt > budget ? budget / w : h;
@@ -2156,7 +2207,7 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
             }
             start += cnt;
         }
-        if (start != S) return false;
+        if (start != a.S) return false;
     }
     // small regions first in the launch order: their adds collide most, they run longest
     // (measured: 1 121-1 128 us small-first against 1 152-1 154 us large-first, tools/sessions_r04/gpu_r04_s39_region_order.sh)
@@ -2170,7 +2221,7 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
         // more than it saves -- consecutive hits sample neighbouring rows, so whole waves skip the corners outside the band (-5 %)
         const bool band = level_hw && (reg[i].tok1 - reg[i].tok0) != level_hw[2 * reg[i].lvl0] * level_hw[2 * reg[i].lvl0 + 1];
         if (!band) pl->tab.perm |= 1u << i;
-        const size_t one = (size_t)FBBEV_DA_PLANE_WORDS(reg[i].tok1 - reg[i].tok0, HS) * sizeof(long long);
+        const size_t one = (size_t)FBBEV_DA_PLANE_WORDS(reg[i].tok1 - reg[i].tok0, a.HS) * sizeof(long long);
         int copies = (int)(budget_bytes / one);
         copies = copies < 1 ? 1 : (copies > 16 ? 16 : copies);
         { const int v = da_bwd_env().copies; if (v >= 1 && v < copies) copies = v; }
@@ -2182,12 +2233,12 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
     pl->lds = lds;
     pl->threads = 512;
     { const int v = da_bwd_env().threads; if (v == 256 || v == 512) pl->threads = v; }
-    if ((long long)n * B * Ncam * M >= (1ll << 31) || (long long)B * Ncam * Q >= (1ll << 31)) return false;
-    if (mode < 0 && (long long)n * B * Ncam * M < 256) return false;              // too few planes to fill the chip: chunked scatter
+    if ((long long)n * a.B * a.Ncam * a.M >= (1ll << 31) || (long long)a.B * a.Ncam * a.Q >= (1ll << 31)) return false;
+    if (mode < 0 && (long long)n * a.B * a.Ncam * a.M < 256) return false;              // too few planes to fill the chip: chunked scatter
     pl->off_list = 0;                                                  // hit records [B*Ncam][Q][16 floats] at the start of ws
-    pl->off_count = align_up((size_t)B * Ncam * Q * FBBEV_DA_HIT_REC * sizeof(float), 256);
-    pl->off_gmax = pl->off_count + align_up((size_t)B * Ncam * sizeof(int), 256);
-    pl->ws = pl->off_gmax + align_up((size_t)B * sizeof(unsigned int), 256);          // one fixed-point scale per sample
+    pl->off_count = align_up((size_t)a.B * a.Ncam * a.Q * FBBEV_DA_HIT_REC * sizeof(float), 256);
+    pl->off_gmax = pl->off_count + align_up((size_t)a.B * a.Ncam * sizeof(int), 256);
+    pl->ws = pl->off_gmax + align_up((size_t)a.B * sizeof(unsigned int), 256);          // one fixed-point scale per sample
     // unit gradients on head planes (k_da_bwd_unit_planes, da_bwd_planes_kernels.h; FBBEV_DA_BWD_UNIT_PLANES=0 keeps the row kernel):
     // M = 8, Dh in {8, 10}, 8 points, 4 anchors, every level at least 2 tokens wide; the planes sit behind the hit lists
     pl->unit_planes = 0;
@@ -2195,11 +2246,11 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
     {
         FBBEV_KNOB_ONCE(bool, on, fbbev_env_int("FBBEV_DA_BWD_UNIT_PLANES", 1) != 0);
         bool wide = level_hw != nullptr;
-        for (int l = 0; wide && l < L; ++l) wide = level_hw[2 * l + 1] >= 2;
-        if (on && wide && M == 8 && (Dh == 10 || Dh == 8) && P == FBBEV_DAF_P && (long long)S * Dh * 4 < (1ll << 31) &&
-            fbbev_dbp_lds_bytes(M, Ncam) <= 156 * 1024) {
+        for (int l = 0; wide && l < a.L; ++l) wide = level_hw[2 * l + 1] >= 2;
+        if (on && wide && a.M == 8 && (a.Dh == 10 || a.Dh == 8) && a.P == FBBEV_DAF_P && (long long)a.S * a.Dh * 4 < (1ll << 31) &&
+            fbbev_dbp_lds_bytes(a.M, a.Ncam) <= 156 * 1024) {
             pl->unit_planes = 1;
-            pl->ws += align_up((size_t)B * Ncam * M * S * Dh * sizeof(float), 256);
+            pl->ws += align_up((size_t)a.B * a.Ncam * a.M * a.S * a.Dh * sizeof(float), 256);
         }
     }
     return true;
@@ -2207,16 +2258,15 @@ static bool da_own_plan_make(int B, int Ncam, int S, int M, int Dh, int Q, int H
 
 extern "C" size_t fbbev_da_cross_attn_bwd_ws_bytes(int B, int Ncam, int S, int M, int Dh, int Q, int head_stride,
                                                    int num_levels, int num_points, const int32_t* level_hw_host) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || num_levels <= 0 || num_points <= 0) return 0;
-    da_bwd_plan pl;
-    const int HS = head_stride == 0 ? Dh : head_stride;
-    if (HS < Dh) return 0;
+    const da_args a = da_record({B, Ncam, S, M, Dh, num_levels, Q, num_points, 1 /* anchor: see below */, 1, 0.f, 0.f, 0, head_stride});
+    if (!da_dims_ok(a, 1, 0) || a.HS < Dh) return 0;
     // Za is not an argument here (the owned plan needs Za <= 4 and word-aligned records, which only the launch can check): the
     // size covers BOTH routes, so a launch whose owned plan fails still finds room for the chunked LDS planes instead of falling
     // back to global atomics
     da_own_plan op;
-    const size_t own = da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, num_levels, num_points, 1, level_hw_host, &op) ? op.ws : 0;
-    const size_t tile = da_bwd_tile_plan(B, Ncam, S, M, Dh, Q, HS, num_levels, num_points, level_hw_host, &pl) ? pl.ws : 0;
+    da_bwd_plan pl;
+    const size_t own = da_own_plan_make(a, level_hw_host, &op) ? op.ws : 0;
+    const size_t tile = da_bwd_tile_plan(a, level_hw_host, &pl) ? pl.ws : 0;
     return own > tile ? own : tile;
 }
 
@@ -2224,43 +2274,33 @@ extern "C" size_t fbbev_da_cross_attn_bwd_ws_bytes(int B, int Ncam, int S, int M
 // when their plan holds for this Za, the chunked planes otherwise) instead of the maximum over both.
 extern "C" size_t fbbev_da_cross_attn_bwd_ws_bytes_za(int B, int Ncam, int S, int M, int Dh, int Q, int head_stride, int num_levels,
                                                       int num_points, int num_z_anchors, const int32_t* level_hw_host) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || num_levels <= 0 || num_points <= 0 || num_z_anchors <= 0) return 0;
-    const int HS = head_stride == 0 ? Dh : head_stride;
-    if (HS < Dh) return 0;
+    const da_args a = da_record({B, Ncam, S, M, Dh, num_levels, Q, num_points, num_z_anchors, 1, 0.f, 0.f, 0, head_stride});
+    if (!da_dims_ok(a, 1, 0) || a.HS < Dh) return 0;
     da_own_plan op;
-    if (num_points % num_z_anchors == 0 &&
-        da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, num_levels, num_points, num_z_anchors, level_hw_host, &op)) return op.ws;
+    if (num_points % num_z_anchors == 0 && da_own_plan_make(a, level_hw_host, &op)) return op.ws;
     da_bwd_plan pl;
-    return da_bwd_tile_plan(B, Ncam, S, M, Dh, Q, HS, num_levels, num_points, level_hw_host, &pl) ? pl.ws : 0;
+    return da_bwd_tile_plan(a, level_hw_host, &pl) ? pl.ws : 0;
 }
 
 // (A) of both LDS-plane backward routes: unit-owned gradients (offsets / attention / depth distribution), the forward's launch shape
-static int da_bwd_unit_launch(fbbev_rt_stream stream, const float* value, const int64_t* spatial_shapes,
-                              const int64_t* level_start_index, const float* pred_depth, const float* ref_cam, const uint8_t* mask,
-                              const float* qdepth, const float* offsets, const float* attn, const float* grad_slots, int B,
-                              int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
-                              int head_minor, int HS, float* grad_pred_depth, float* grad_offsets, float* grad_attn,
-                              unsigned int* gmax_bits, bool det = false) {
-    // (A) unit-owned gradients, the forward's launch shape
-    const long long units = (long long)B * Q * M;
+static int da_bwd_unit_launch(const da_args& a, unsigned int* gmax_bits, bool det) {
+    const long long units = (long long)a.B * a.Q * a.M;
     long long ub = ((units + 255) / 256 + 7) / 8 * 8;
     if (ub > 65536) ub = 65536;
-    const size_t lds_a = (size_t)256 * (4 * P + 1) * sizeof(float);
-    const bool qi = (head_minor & 4) != 0;
-#define FBBEV_DA_BWD_UNIT_K(DH_, QI_, DET_)                                                                             \
-    FBBEV_LAUNCH((k_da_cross_attn_bwd_unit<DH_, QI_, DET_>), ub, 256, lds_a, stream, units, value, spatial_shapes,        \
-                 level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, \
-                 DC, d0, dstep, head_minor & 3, HS, grad_pred_depth, grad_offsets, grad_attn, gmax_bits)
+    const size_t lds_a = (size_t)256 * (4 * a.P + 1) * sizeof(float);
+    const bool qi = (a.head_minor & 4) != 0;
+#define FBBEV_DA_BWD_UNIT_K(DH_, QI_, DET_)                                                                              \
+    FBBEV_LAUNCH((k_da_cross_attn_bwd_unit<DH_, QI_, DET_>), ub, 256, lds_a, a.stream, units, a.value, a.spatial_shapes, \
+                 a.level_start_index, a.pred_depth, a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn, a.grad_slots, a.B,   \
+                 a.Ncam, a.S, a.M, a.L, a.Q, a.P, a.Za, a.DC, a.d0, a.dstep, a.head_minor & 3, a.HS, a.grad_pred_depth,  \
+                 a.grad_offsets, a.grad_attn, gmax_bits)
 #define FBBEV_DA_BWD_UNIT(DH_)                                                                                          \
     do {                                                                                                                \
     if (det) { if (qi) FBBEV_DA_BWD_UNIT_K(DH_, true, true); else FBBEV_DA_BWD_UNIT_K(DH_, false, true); }             \
     else if (qi) FBBEV_DA_BWD_UNIT_K(DH_, true, false);                                                                 \
     else FBBEV_DA_BWD_UNIT_K(DH_, false, false);                                                                        \
     } while (0)
-    if (Dh == 10) FBBEV_DA_BWD_UNIT(10);
-    else if (Dh == 8) FBBEV_DA_BWD_UNIT(8);
-    else if (Dh == 4) FBBEV_DA_BWD_UNIT(4);
-    else FBBEV_DA_BWD_UNIT(16);
+    FBBEV_DA_DH_BWD(a.Dh, FBBEV_DA_BWD_UNIT);
 #undef FBBEV_DA_BWD_UNIT
 #undef FBBEV_DA_BWD_UNIT_K
     FBBEV_CHECK_LAUNCH();
@@ -2268,66 +2308,56 @@ static int da_bwd_unit_launch(fbbev_rt_stream stream, const float* value, const 
 }
 
 // output-owned route: unit gradients, then init + hit lists + ONE scatter launch over every token region
-static int da_bwd_owned_launch(const da_own_plan& op, fbbev_rt_stream stream, const float* value, const int64_t* spatial_shapes,
-                               const int64_t* level_start_index, const float* pred_depth, const float* ref_cam, const uint8_t* mask,
-                               const float* qdepth, const float* offsets, const float* attn, const float* grad_slots, int B,
-                               int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0, float dstep,
-                               int head_minor, int HS, float* grad_value, float* grad_pred_depth, float* grad_offsets,
-                               float* grad_attn, void* ws, int bev_w, const float* planes_in = nullptr, bool det = false) {
+static int da_bwd_owned_launch(const da_own_plan& op, const da_args& a, void* ws, bool det) {
     char* w = static_cast<char*>(ws);
     float* hit_rec = reinterpret_cast<float*>(w + op.off_list);
     int* hit_count = reinterpret_cast<int*>(w + op.off_count);
     unsigned int* gmax_bits = reinterpret_cast<unsigned int*>(w + op.off_gmax);
-    FBBEV_LAUNCH(k_da_bwd_init, 1, 256, 0, stream, B * Ncam, hit_count, B, gmax_bits);
+    FBBEV_LAUNCH(k_da_bwd_init, 1, 256, 0, a.stream, a.B * a.Ncam, hit_count, a.B, gmax_bits);
     FBBEV_CHECK_LAUNCH();
     int e = 0;
     // (the plane kernel reads a record's 4 mask bytes / 8 reference floats / 4 depths as whole words: alignment of the geometry inputs)
-    if (op.unit_planes && Za == FBBEV_DAF_ZA && aligned16(ref_cam) && aligned16(qdepth) && ((uintptr_t)mask & 3) == 0) {
+    if (op.unit_planes && a.Za == FBBEV_DAF_ZA && aligned16(a.ref_cam) && aligned16(a.qdepth) && ((uintptr_t)a.mask & 3) == 0) {
         // camera tokens as head planes, then the unit gradients with the forward's (head, patch) mapping
-        const float* planes = planes_in;
+        const float* planes = a.planes;
         if (!planes) {                                                 // (round 6: the training forward's own head planes may be handed in)
             float* pl_w = reinterpret_cast<float*>(w + op.off_planes);
-            const long long n_el = (long long)B * Ncam * S * M * Dh;
-            FBBEV_LAUNCH(k_value_rows_to_head_planes, (n_el + 255) / 256, 256, 0, stream, value, (long long)B * Ncam * S, S, M, Dh, HS,
-                         (head_minor & 4) ? 1 : 0, pl_w);
+            const long long n_el = (long long)a.B * a.Ncam * a.S * a.M * a.Dh;
+            FBBEV_LAUNCH(k_value_rows_to_head_planes, (n_el + 255) / 256, 256, 0, a.stream, a.value, (long long)a.B * a.Ncam * a.S, a.S,
+                         a.M, a.Dh, a.HS, (a.head_minor & 4) ? 1 : 0, pl_w);
             FBBEV_CHECK_LAUNCH();
             planes = pl_w;
         }
-        const int gw = (bev_w > 0 && Q % bev_w == 0) ? bev_w : 0;
-        const long long wgs_u = gw > 0 ? (long long)B * ((gw + 7) / 8) * ((Q / gw + 7) / 8) : (long long)B * ((Q + 63) / 64);
+        const int gw = (a.bev_w > 0 && a.Q % a.bev_w == 0) ? a.bev_w : 0;
+        const long long wgs_u = gw > 0 ? (long long)a.B * ((gw + 7) / 8) * ((a.Q / gw + 7) / 8) : (long long)a.B * ((a.Q + 63) / 64);
         const long long grid_u = (wgs_u + 7) / 8 * 8;
-        const size_t lds_u = fbbev_dbp_lds_bytes(M, Ncam);
+        const size_t lds_u = fbbev_dbp_lds_bytes(a.M, a.Ncam);
         if (grid_u >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-#define FBBEV_DA_UNIT_PLANES(DH_, DET_)                                                                                       \
-    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_unit_planes<DH_, 8, DET_>), grid_u, 512, lds_u, stream, (const float*)planes,             \
-                         spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, \
-                         Ncam, S, L, Q, gw, DC, d0, dstep, head_minor & 3, grad_pred_depth, grad_offsets, grad_attn,         \
-                         gmax_bits)
-        if (det) { if (Dh == 10) FBBEV_DA_UNIT_PLANES(10, true); else FBBEV_DA_UNIT_PLANES(8, true); }
-        else if (Dh == 10) FBBEV_DA_UNIT_PLANES(10, false); else FBBEV_DA_UNIT_PLANES(8, false);
+#define FBBEV_DA_UNIT_PLANES(DH_, DET_)                                                                                        \
+    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_unit_planes<DH_, 8, DET_>), grid_u, 512, lds_u, a.stream, (const float*)planes,             \
+                         a.spatial_shapes, a.level_start_index, a.pred_depth, a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn,  \
+                         a.grad_slots, a.B, a.Ncam, a.S, a.L, a.Q, gw, a.DC, a.d0, a.dstep, a.head_minor & 3, a.grad_pred_depth, \
+                         a.grad_offsets, a.grad_attn, gmax_bits)
+        if (det) { if (a.Dh == 10) FBBEV_DA_UNIT_PLANES(10, true); else FBBEV_DA_UNIT_PLANES(8, true); }
+        else if (a.Dh == 10) FBBEV_DA_UNIT_PLANES(10, false); else FBBEV_DA_UNIT_PLANES(8, false);
 #undef FBBEV_DA_UNIT_PLANES
         FBBEV_CHECK_LAUNCH();
     } else {
-        e = da_bwd_unit_launch(stream, value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                               grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS, grad_pred_depth,
-                               grad_offsets, grad_attn, gmax_bits, det);
+        e = da_bwd_unit_launch(a, gmax_bits, det);
         if (e) return e;
     }
-    FBBEV_LAUNCH(k_da_bwd_hitlist, (long long)B * ((Q + 255) / 256), 256, 0, stream, spatial_shapes, pred_depth, ref_cam, mask,
-                 qdepth, B, Ncam, Q, Za, DC, d0, dstep, hit_rec, hit_count);
+    FBBEV_LAUNCH(k_da_bwd_hitlist, (long long)a.B * ((a.Q + 255) / 256), 256, 0, a.stream, a.spatial_shapes, a.pred_depth, a.ref_cam,
+                 a.mask, a.qdepth, a.B, a.Ncam, a.Q, a.Za, a.DC, a.d0, a.dstep, hit_rec, hit_count);
     FBBEV_CHECK_LAUNCH();
     const fbbev_da_bwd_region_tab& tab = op.tab;
-    const long long wgs = (long long)tab.n * B * Ncam * M;
-#define FBBEV_DA_OWN(NT_, DH_)                                                                                            \
-    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_scatter_owned<NT_, DH_>), wgs, NT_, op.lds, stream, spatial_shapes, level_start_index, \
-                         ref_cam, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, head_minor & 3, HS, tab,         \
-                         (const float*)hit_rec, (const int*)hit_count,                                                    \
-                         (const unsigned int*)gmax_bits, (head_minor & 4) ? 1 : 0, grad_value)
+    const long long wgs = (long long)tab.n * a.B * a.Ncam * a.M;
+#define FBBEV_DA_OWN(NT_, DH_)                                                                                                  \
+    FBBEV_LAUNCH_DYN_LDS((k_da_bwd_scatter_owned<NT_, DH_>), wgs, NT_, op.lds, a.stream, a.spatial_shapes, a.level_start_index, \
+                         a.ref_cam, a.offsets, a.attn, a.grad_slots, a.B, a.Ncam, a.S, a.M, a.L, a.Q, a.P, a.Za,                \
+                         a.head_minor & 3, a.HS, tab, (const float*)hit_rec, (const int*)hit_count,                             \
+                         (const unsigned int*)gmax_bits, (a.head_minor & 4) ? 1 : 0, a.grad_value)
 #define FBBEV_DA_OWN_NT(DH_) do { if (op.threads == 512) FBBEV_DA_OWN(512, DH_); else FBBEV_DA_OWN(256, DH_); } while (0)   /* 1024 threads measured slower */
-    if (Dh == 10) FBBEV_DA_OWN_NT(10);
-    else if (Dh == 8) FBBEV_DA_OWN_NT(8);
-    else if (Dh == 4) FBBEV_DA_OWN_NT(4);
-    else FBBEV_DA_OWN_NT(16);
+    FBBEV_DA_DH_BWD(a.Dh, FBBEV_DA_OWN_NT);
 #undef FBBEV_DA_OWN_NT
 #undef FBBEV_DA_OWN
     FBBEV_CHECK_LAUNCH();
@@ -2381,106 +2411,78 @@ extern "C" size_t fbbev_da_bwd_det_ws_bytes(int B, int Ncam, int Q, int Za, int 
 // The unit kernels' DET instantiations store the head-summed d / d depth weight into the front of det_ws (zeroed here first: a unit
 // no camera sees stores nothing), `run` launches the route with that buffer as its grad_pred_depth, then the taps are added.
 template <class Run>
-static int da_bwd_det(int B, int Ncam, int M, int Q, int Za, int DC, const int32_t* level_hw_host, const float* ref_cam,
-                      const float* qdepth, float d0, float dstep, float* grad_pred_depth, void* det_ws, size_t det_ws_bytes,
-                      fbbev_stream_t stream_, Run run) {
-    if (!level_hw_host || !det_ws || !ref_cam || !qdepth || !grad_pred_depth) return FBBEV_E_BADARG;
-    if (B <= 0 || Ncam <= 0 || Q <= 0 || Za <= 0 || DC <= 0 || dstep == 0.f) return FBBEV_E_BADARG;
-    if (M > 64 || (M & (M - 1)) != 0) return FBBEV_E_UNSUPPORTED;                  // the unit kernel's head reduction
+static int da_bwd_det(const da_args& a, const int32_t* level_hw_host, void* det_ws, size_t det_ws_bytes, Run run) {
+    if (!level_hw_host || !det_ws || !a.ref_cam || !a.qdepth || !a.grad_pred_depth) return FBBEV_E_BADARG;
+    if (a.B <= 0 || a.Ncam <= 0 || a.Q <= 0 || a.Za <= 0 || a.DC <= 0 || a.dstep == 0.f) return FBBEV_E_BADARG;
+    if (a.M > 64 || (a.M & (a.M - 1)) != 0) return FBBEV_E_UNSUPPORTED;            // the unit kernel's head reduction
     const int H0 = level_hw_host[0], W0 = level_hw_host[1];
     if (H0 <= 0 || W0 <= 0) return FBBEV_E_BADARG;
-    if (det_ws_bytes < fbbev_da_bwd_det_ws_bytes(B, Ncam, Q, Za, DC, H0, W0) || !aligned16(det_ws)) return FBBEV_E_WORKSPACE;
-    const size_t sum_bytes = align_up((size_t)Ncam * B * Q * Za * sizeof(float), 256);
-    float* dsum = static_cast<float*>(det_ws);
-    int e = fbbev_rt_memset_async(dsum, 0, sum_bytes, (fbbev_rt_stream)stream_);
+    if (det_ws_bytes < fbbev_da_bwd_det_ws_bytes(a.B, a.Ncam, a.Q, a.Za, a.DC, H0, W0) || !aligned16(det_ws)) return FBBEV_E_WORKSPACE;
+    const size_t sum_bytes = align_up((size_t)a.Ncam * a.B * a.Q * a.Za * sizeof(float), 256);
+    da_args d = a;
+    d.grad_pred_depth = static_cast<float*>(det_ws);
+    int e = fbbev_rt_memset_async(d.grad_pred_depth, 0, sum_bytes, a.stream);
     if (e) return e;
-    e = run(dsum);
+    e = run(d);
     if (e) return e;
-    return fbbev_da_depth_taps_det(dsum, ref_cam, qdepth, B, Ncam, Q, Za, DC, H0, W0, d0, dstep, grad_pred_depth,
-                                   static_cast<char*>(det_ws) + sum_bytes, det_ws_bytes - sum_bytes, stream_);
+    return fbbev_da_depth_taps_det(d.grad_pred_depth, a.ref_cam, a.qdepth, a.B, a.Ncam, a.Q, a.Za, a.DC, H0, W0, a.d0, a.dstep,
+                                   a.grad_pred_depth, static_cast<char*>(det_ws) + sum_bytes, det_ws_bytes - sum_bytes,
+                                   (fbbev_stream_t)a.stream);
 }
 
-static int da_cross_attn_bwd_ws_impl(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                          const float* pred_depth, const float* ref_cam, const uint8_t* mask,
-                                          const float* qdepth, const float* offsets, const float* attn,
-                                          const float* grad_slots, int B, int Ncam, int S, int M, int Dh, int L, int Q,
-                                          int P, int Za, int DC, float d0, float dstep, int head_minor, int head_stride,
-                                          float* grad_value, float* grad_pred_depth, float* grad_offsets,
-                                          float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
-                                          fbbev_stream_t stream_, int bev_w, bool det = false) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q < 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w < 0)
-        return FBBEV_E_BADARG;
-    const int HS = head_stride == 0 ? Dh : head_stride;
+// the LDS-plane routes on token rows: output-owned planes, else the chunked scatter, else (unless det) the global atomics
+static int da_bwd_ws(const da_args& a, const int32_t* level_hw_host, void* ws, size_t ws_bytes, bool det) {
+    if (!da_dims_ok(a, 0, 0)) return FBBEV_E_BADARG;
     {
         da_own_plan op;
-        if (HS >= Dh && Q > 0 && ws && aligned16(ws) && aligned16(grad_value) && value && spatial_shapes && level_start_index &&
-            pred_depth && ref_cam && mask && qdepth && offsets && attn && grad_slots && grad_value && grad_pred_depth &&
-            grad_offsets && grad_attn && dstep != 0.f && P % Za == 0 &&
-            (((uintptr_t)offsets | (uintptr_t)grad_offsets | (uintptr_t)grad_slots) & 7) == 0 &&
-            da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, L, P, Za, level_hw_host, &op) && ws_bytes >= op.ws)
-            return da_bwd_owned_launch(op, (fbbev_rt_stream)stream_, value, spatial_shapes, level_start_index, pred_depth, ref_cam,
-                                       mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep,
-                                       head_minor, HS, grad_value, grad_pred_depth, grad_offsets, grad_attn, ws, bev_w, nullptr, det);
+        if (a.HS >= a.Dh && a.Q > 0 && ws && aligned16(ws) && aligned16(a.grad_value) && da_bwd_present(a) && a.dstep != 0.f &&
+            a.P % a.Za == 0 && da_pairs_aligned(a) && da_own_plan_make(a, level_hw_host, &op) && ws_bytes >= op.ws)
+            return da_bwd_owned_launch(op, a, ws, det);
     }
     da_bwd_plan pl;
-    if (HS < Dh || Q == 0 || !ws || !aligned16(ws) || !aligned16(grad_value) || !aligned16(value) ||
-        !da_bwd_tile_plan(B, Ncam, S, M, Dh, Q, HS, L, P, level_hw_host, &pl) || ws_bytes < pl.ws ||
-        (long long)B * M * pl.chunks >= (1ll << 31) || (long long)B * Ncam * S * M * HS * 4 >= (1ll << 32) ||
-        (((uintptr_t)offsets | (uintptr_t)grad_offsets | (uintptr_t)grad_slots) & 7) != 0)
-        return det ? FBBEV_E_UNSUPPORTED : fbbev_da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
-                                       attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor,
-                                       head_stride, grad_value, grad_pred_depth, grad_offsets, grad_attn, stream_);
-    if (Za > FBBEV_DA_MAX_ZA || P % Za != 0) return FBBEV_E_UNSUPPORTED;
-    if (dstep == 0.f) return FBBEV_E_BADARG;
-    if (!value || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets ||
-        !attn || !grad_slots || !grad_value || !grad_pred_depth || !grad_offsets || !grad_attn) return FBBEV_E_BADARG;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    if (a.HS < a.Dh || a.Q == 0 || !ws || !aligned16(ws) || !aligned16(a.grad_value) || !aligned16(a.value) ||
+        !da_bwd_tile_plan(a, level_hw_host, &pl) || ws_bytes < pl.ws || (long long)a.B * a.M * pl.chunks >= (1ll << 31) ||
+        (long long)a.B * a.Ncam * a.S * a.M * a.HS * 4 >= (1ll << 32) || !da_pairs_aligned(a))
+        return det ? FBBEV_E_UNSUPPORTED : da_bwd_atomic(a);
+    if (!da_anchors_ok(a)) return FBBEV_E_UNSUPPORTED;
+    if (a.dstep == 0.f) return FBBEV_E_BADARG;
+    if (!da_bwd_present(a)) return FBBEV_E_BADARG;
     float* part = static_cast<float*>(ws);
-    const long long wgs = (long long)B * M * pl.chunks;
+    const long long wgs = (long long)a.B * a.M * pl.chunks;
     const float* info = nullptr;
-    if (pl.info_stride > 0 && 1 + Za <= pl.info_stride) {
+    if (pl.info_stride > 0 && 1 + a.Za <= pl.info_stride) {
         float* info_w = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.ws_part);
-        FBBEV_LAUNCH(k_da_bwd_hitinfo, ((long long)B * Q + 255) / 256, 256, 0, stream, spatial_shapes, pred_depth, ref_cam, mask,
-                     qdepth, B, Ncam, Q, Za, DC, d0, dstep, pl.info_stride, info_w);
+        FBBEV_LAUNCH(k_da_bwd_hitinfo, ((long long)a.B * a.Q + 255) / 256, 256, 0, a.stream, a.spatial_shapes, a.pred_depth, a.ref_cam,
+                     a.mask, a.qdepth, a.B, a.Ncam, a.Q, a.Za, a.DC, a.d0, a.dstep, pl.info_stride, info_w);
         FBBEV_CHECK_LAUNCH();
         info = info_w;
     }
-    {
-        {
-            const int e = da_bwd_unit_launch(stream, value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
-                                             attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS,
-                                             grad_pred_depth, grad_offsets, grad_attn, nullptr, det);
-            if (e) return e;
-        }
-        // (B) value gradient, one launch per token region
-        for (int r = 0; r < pl.n_regions; ++r) {
-            const da_region& rg = pl.reg[r];
-            // small regions (coarse levels): up to 4 copies of the plane inside the LDS budget of the largest region
-            const size_t one = (size_t)FBBEV_DA_PLANE_WORDS(rg.tok1 - rg.tok0, HS) * sizeof(long long);
-            int copies = (int)((size_t)(da_bwd_plane_kb() * 1024) / one);
-            copies = copies < 1 ? 1 : (copies > 4 ? 4 : copies);
-            { const int v = da_bwd_env().copies; if (v >= 1 && v <= copies) copies = v; }
-            const size_t lds_b = one * copies + (size_t)((pl.q_per_chunk + 1) & ~1) * 2 + (size_t)(1 + pl.threads / 64) * sizeof(int);
-#define FBBEV_DA_BWD_SC(NT_, DH_)                                                                                       \
-    FBBEV_LAUNCH((k_da_cross_attn_bwd_scatter<NT_, DH_>), wgs, NT_, lds_b, stream, spatial_shapes, level_start_index,     \
-                 pred_depth, ref_cam, mask, qdepth, offsets, attn, grad_slots, B, Ncam, S, M, L, Q, P, Za, DC, d0, dstep, \
-                 head_minor & 3, HS, pl.chunks, pl.q_per_chunk, rg.lvl0, rg.lvl1, rg.tok0, rg.tok1, copies, part, info,  \
-                 pl.info_stride)
+    if (const int e = da_bwd_unit_launch(a, nullptr, det)) return e;
+    // (B) value gradient, one launch per token region
+    for (int r = 0; r < pl.n_regions; ++r) {
+        const da_region& rg = pl.reg[r];
+        // small regions (coarse levels): up to 4 copies of the plane inside the LDS budget of the largest region
+        const size_t one = (size_t)FBBEV_DA_PLANE_WORDS(rg.tok1 - rg.tok0, a.HS) * sizeof(long long);
+        int copies = (int)((size_t)(da_bwd_plane_kb() * 1024) / one);
+        copies = copies < 1 ? 1 : (copies > 4 ? 4 : copies);
+        { const int v = da_bwd_env().copies; if (v >= 1 && v <= copies) copies = v; }
+        const size_t lds_b = one * copies + (size_t)((pl.q_per_chunk + 1) & ~1) * 2 + (size_t)(1 + pl.threads / 64) * sizeof(int);
+#define FBBEV_DA_BWD_SC(NT_, DH_)                                                                                              \
+    FBBEV_LAUNCH((k_da_cross_attn_bwd_scatter<NT_, DH_>), wgs, NT_, lds_b, a.stream, a.spatial_shapes, a.level_start_index, \
+                 a.pred_depth, a.ref_cam, a.mask, a.qdepth, a.offsets, a.attn, a.grad_slots, a.B, a.Ncam, a.S, a.M, a.L,    \
+                 a.Q, a.P, a.Za, a.DC, a.d0, a.dstep, a.head_minor & 3, a.HS, pl.chunks, pl.q_per_chunk, rg.lvl0, rg.lvl1,  \
+                 rg.tok0, rg.tok1, copies, part, info, pl.info_stride)
 #define FBBEV_DA_BWD_SC_NT(DH_) do { if (pl.threads == 512) FBBEV_DA_BWD_SC(512, DH_); else FBBEV_DA_BWD_SC(256, DH_); } while (0)
-            if (Dh == 10) FBBEV_DA_BWD_SC_NT(10);
-            else if (Dh == 8) FBBEV_DA_BWD_SC_NT(8);
-            else if (Dh == 4) FBBEV_DA_BWD_SC_NT(4);
-            else FBBEV_DA_BWD_SC_NT(16);
+        FBBEV_DA_DH_BWD(a.Dh, FBBEV_DA_BWD_SC_NT);
 #undef FBBEV_DA_BWD_SC_NT
 #undef FBBEV_DA_BWD_SC
-            FBBEV_CHECK_LAUNCH();
-        }
+        FBBEV_CHECK_LAUNCH();
     }
-    const long long n = (long long)B * Ncam * S * M * HS;
+    const long long n = (long long)a.B * a.Ncam * a.S * a.M * a.HS;
     long long rb = (n + 255) / 256;
     if (rb > 65536) rb = 65536;
-    FBBEV_LAUNCH(k_da_bwd_reduce, rb, 256, 0, stream, (const float*)part, B, Ncam, S, M, HS, pl.chunks, (head_minor & 4) ? 1 : 0,
-                 grad_value);
+    FBBEV_LAUNCH(k_da_bwd_reduce, rb, 256, 0, a.stream, (const float*)part, a.B, a.Ncam, a.S, a.M, a.HS, pl.chunks,
+                 (a.head_minor & 4) ? 1 : 0, a.grad_value);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2493,9 +2495,10 @@ extern "C" int fbbev_da_cross_attn_bwd_ws(const float* value, const int64_t* spa
                                           float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                           float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
                                           fbbev_stream_t stream_) {
-    return da_cross_attn_bwd_ws_impl(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                                     grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
-                                     grad_value, grad_pred_depth, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, stream_, 0);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, 0, (fbbev_rt_stream)stream_,
+                                 value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    return da_bwd_ws(a, level_hw_host, ws, ws_bytes, false);
 }
 // ... with the BEV grid's width: the queries are a (Q / bev_w) x bev_w grid, so the unit gradients take 8 x 8 patches of it
 // (k_da_bwd_unit_planes; bev_w = 0 or not a divisor of Q: runs of 64 consecutive queries)
@@ -2507,10 +2510,10 @@ extern "C" int fbbev_da_cross_attn_bwd_ws_grid(const float* value, const int64_t
                                                float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                                float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
                                                int bev_w, fbbev_stream_t stream_) {
-    return da_cross_attn_bwd_ws_impl(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                                     grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
-                                     grad_value, grad_pred_depth, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, stream_,
-                                     bev_w);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, bev_w, (fbbev_rt_stream)stream_,
+                                 value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    return da_bwd_ws(a, level_hw_host, ws, ws_bytes, false);
 }
 // ... with a flags word (FBBEV_FLAG_DETERMINISTIC: the depth taps as 64-bit fixed point, no float atomics; det_ws of
 // fbbev_da_bwd_det_ws_bytes; a shape neither LDS-plane route takes is FBBEV_E_UNSUPPORTED instead of the global-atomic kernel)
@@ -2522,15 +2525,12 @@ extern "C" int fbbev_da_cross_attn_bwd_ws_grid_ex(const float* value, const int6
                                                   float* grad_value, float* grad_pred_depth, float* grad_offsets,
                                                   float* grad_attn, const int32_t* level_hw_host, void* ws, size_t ws_bytes,
                                                   int bev_w, int flags, void* det_ws, size_t det_ws_bytes, fbbev_stream_t stream_) {
-    const bool det = (flags & FBBEV_FLAG_DETERMINISTIC) != 0;
-    auto run = [&](float* gpd) {
-        return da_cross_attn_bwd_ws_impl(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                                         grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
-                                         grad_value, gpd, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, stream_, bev_w, det);
-    };
-    if (!det) return run(grad_pred_depth);
-    return da_bwd_det(B, Ncam, M, Q, Za, DC, level_hw_host, ref_cam, qdepth, d0, dstep, grad_pred_depth, det_ws, det_ws_bytes, stream_,
-                      run);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, bev_w, (fbbev_rt_stream)stream_,
+                                 value, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC)) return da_bwd_ws(a, level_hw_host, ws, ws_bytes, false);
+    return da_bwd_det(a, level_hw_host, det_ws, det_ws_bytes,
+                      [&](const da_args& d) { return da_bwd_ws(d, level_hw_host, ws, ws_bytes, true); });
 }
 
 // Round 6: the backward of fbbev_da_cross_attn_fused for the training step that runs the one-kernel forward -- the camera tokens arrive as
@@ -2541,35 +2541,23 @@ extern "C" int fbbev_da_cross_attn_bwd_ws_grid_ex(const float* value, const int6
 // bev_w-wide grid; FBBEV_E_UNSUPPORTED otherwise (the caller keeps fbbev_da_cross_attn_bwd_ws_grid on row tokens).
 extern "C" int fbbev_da_cross_attn_bwd_planes_supported(int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int head_stride,
                                                         const int32_t* level_hw_host, int bev_w) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0 || bev_w <= 0 || Q % bev_w != 0) return 0;
-    const int HS = head_stride == 0 ? Dh : head_stride;
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, 1, 0.f, 0.f, 0, head_stride, bev_w});
+    if (!da_dims_ok(a, 1, 1) || Q % bev_w != 0) return 0;
     da_own_plan op;
-    if (HS < Dh || P % Za != 0 || Za != FBBEV_DAF_ZA || !da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, L, P, Za, level_hw_host, &op)) return 0;
+    if (a.HS < Dh || P % Za != 0 || Za != FBBEV_DAF_ZA || !da_own_plan_make(a, level_hw_host, &op)) return 0;
     return op.unit_planes ? 1 : 0;
 }
-static int da_cross_attn_bwd_planes_impl(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
-                                         const float* pred_depth, const float* ref_cam, const uint8_t* mask,
-                                         const float* qdepth, const float* offsets, const float* attn, const float* grad_slots,
-                                         int B, int Ncam, int S, int M, int Dh, int L, int Q, int P, int Za, int DC, float d0,
-                                         float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
-                                         float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
-                                         size_t ws_bytes, int bev_w, fbbev_stream_t stream_, bool det) {
-    if (B <= 0 || Ncam <= 0 || S <= 0 || M <= 0 || Dh <= 0 || L <= 0 || Q <= 0 || P <= 0 || Za <= 0 || DC <= 0 || bev_w <= 0)
-        return FBBEV_E_BADARG;
-    if (!planes || !spatial_shapes || !level_start_index || !pred_depth || !ref_cam || !mask || !qdepth || !offsets || !attn ||
-        !grad_slots || !grad_value || !grad_pred_depth || !grad_offsets || !grad_attn || !ws) return FBBEV_E_BADARG;
-    if (dstep == 0.f) return FBBEV_E_BADARG;
-    const int HS = head_stride == 0 ? Dh : head_stride;
+static int da_bwd_planes(const da_args& a, const int32_t* level_hw_host, void* ws, size_t ws_bytes, bool det) {
+    if (!da_dims_ok(a, 1, 1)) return FBBEV_E_BADARG;
+    if (!da_bwd_present(a) || !ws) return FBBEV_E_BADARG;
+    if (a.dstep == 0.f) return FBBEV_E_BADARG;
     da_own_plan op;
-    if (HS < Dh || P % Za != 0 || Za != FBBEV_DAF_ZA || Q % bev_w != 0 ||
-        !da_own_plan_make(B, Ncam, S, M, Dh, Q, HS, L, P, Za, level_hw_host, &op) || !op.unit_planes) return FBBEV_E_UNSUPPORTED;
-    if (!aligned16(ws) || !aligned16(grad_value) || !aligned16(ref_cam) || !aligned16(qdepth) || ((uintptr_t)mask & 3) != 0 ||
-        ((uintptr_t)planes & 7) != 0 || (((uintptr_t)offsets | (uintptr_t)grad_offsets | (uintptr_t)grad_slots) & 7) != 0)
-        return FBBEV_E_UNSUPPORTED;
+    if (a.HS < a.Dh || a.P % a.Za != 0 || a.Za != FBBEV_DAF_ZA || a.Q % a.bev_w != 0 || !da_own_plan_make(a, level_hw_host, &op) ||
+        !op.unit_planes) return FBBEV_E_UNSUPPORTED;
+    if (!aligned16(ws) || !aligned16(a.grad_value) || !aligned16(a.ref_cam) || !aligned16(a.qdepth) || ((uintptr_t)a.mask & 3) != 0 ||
+        ((uintptr_t)a.planes & 7) != 0 || !da_pairs_aligned(a)) return FBBEV_E_UNSUPPORTED;
     if (ws_bytes < op.ws) return FBBEV_E_WORKSPACE;
-    return da_bwd_owned_launch(op, (fbbev_rt_stream)stream_, nullptr, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth,
-                               offsets, attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, HS, grad_value,
-                               grad_pred_depth, grad_offsets, grad_attn, ws, bev_w, planes, det);
+    return da_bwd_owned_launch(op, a, ws, det);
 }
 extern "C" int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
                                               const float* pred_depth, const float* ref_cam, const uint8_t* mask,
@@ -2578,9 +2566,10 @@ extern "C" int fbbev_da_cross_attn_bwd_planes(const float* planes, const int64_t
                                               float dstep, int head_minor, int head_stride, float* grad_value, float* grad_pred_depth,
                                               float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
                                               size_t ws_bytes, int bev_w, fbbev_stream_t stream_) {
-    return da_cross_attn_bwd_planes_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
-                                         grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, grad_value,
-                                         grad_pred_depth, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, bev_w, stream_, false);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, bev_w, (fbbev_rt_stream)stream_,
+                                 nullptr, planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    return da_bwd_planes(a, level_hw_host, ws, ws_bytes, false);
 }
 // ... with a flags word (FBBEV_FLAG_DETERMINISTIC: the depth taps as 64-bit fixed point, det_ws of fbbev_da_bwd_det_ws_bytes)
 extern "C" int fbbev_da_cross_attn_bwd_planes_ex(const float* planes, const int64_t* spatial_shapes, const int64_t* level_start_index,
@@ -2591,15 +2580,12 @@ extern "C" int fbbev_da_cross_attn_bwd_planes_ex(const float* planes, const int6
                                                  float* grad_offsets, float* grad_attn, const int32_t* level_hw_host, void* ws,
                                                  size_t ws_bytes, int bev_w, int flags, void* det_ws, size_t det_ws_bytes,
                                                  fbbev_stream_t stream_) {
-    const bool det = (flags & FBBEV_FLAG_DETERMINISTIC) != 0;
-    auto run = [&](float* gpd) {
-        return da_cross_attn_bwd_planes_impl(planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets,
-                                             attn, grad_slots, B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride,
-                                             grad_value, gpd, grad_offsets, grad_attn, level_hw_host, ws, ws_bytes, bev_w, stream_, det);
-    };
-    if (!det) return run(grad_pred_depth);
-    return da_bwd_det(B, Ncam, M, Q, Za, DC, level_hw_host, ref_cam, qdepth, d0, dstep, grad_pred_depth, det_ws, det_ws_bytes, stream_,
-                      run);
+    const da_args a = da_record({B, Ncam, S, M, Dh, L, Q, P, Za, DC, d0, dstep, head_minor, head_stride, bev_w, (fbbev_rt_stream)stream_,
+                                 nullptr, planes, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
+                                 nullptr, grad_slots, grad_value, grad_pred_depth, grad_offsets, grad_attn});
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC)) return da_bwd_planes(a, level_hw_host, ws, ws_bytes, false);
+    return da_bwd_det(a, level_hw_host, det_ws, det_ws_bytes,
+                      [&](const da_args& d) { return da_bwd_planes(d, level_hw_host, ws, ws_bytes, true); });
 }
 
 // ---------------------------------------------------------------- fused lift-splat backward (training)

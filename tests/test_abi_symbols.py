@@ -169,3 +169,365 @@ def test_invalid_arguments_return_error_codes_without_touching_the_gpu():
     assert wgrad(P16, 82, P16, 0, P16, 40, 1, 256, 80, 80, P16, P16, P16, 1 << 30, NULL) == -1     # short addend rows before grad_out % 4
     assert wgrad(P16, 0, P16, 0, P8, 0, 1, 256, 80, 80, P16, P16, NULL, 0, NULL) == -2             # addend before the workspace (-3)
     assert wgrad(P16, 0, P8, 0, NULL, 0, 0, 256, 80, 80, P16, P16, NULL, 0, NULL) == -2            # x before the workspace
+
+
+# ---- the depth-aware cross-attention family: one table per entry, recorded on the launchers before they shared an argument record
+DA_NULL = ctypes.c_void_p(0)
+DA_P16, DA_P8, DA_P4 = ctypes.c_void_p(0x1000), ctypes.c_void_p(0x1008), ctypes.c_void_p(0x1004)   # 16-byte aligned / 8 / 4
+DA_GEOMETRY = ['spatial_shapes', 'level_start_index', 'pred_depth', 'ref_cam', 'mask', 'qdepth']
+DA_DIMS = ['B', 'Ncam', 'S', 'M', 'Dh', 'L', 'Q', 'P', 'Za', 'DC']
+DA_FWD = ['value'] + DA_GEOMETRY + ['offsets', 'attn'] + DA_DIMS + ['d0', 'dstep', 'head_minor']
+DA_BWD = (['value'] + DA_GEOMETRY + ['offsets', 'attn', 'grad_slots'] + DA_DIMS + ['d0', 'dstep', 'head_minor', 'head_stride'] +
+          ['grad_value', 'grad_pred_depth', 'grad_offsets', 'grad_attn'])
+DA_FUSED = (DA_GEOMETRY + ['query', 'query_row_stride', 'addend', 'addend_row_stride', 'addend_period', 'offsets_fragments',
+                           'offsets_bias', 'attn_fragments', 'attn_bias'])
+DA_FUSED_TAIL = DA_DIMS + ['d0', 'dstep', 'bev_w', 'min_level_width', 'slots', 'stream']
+DA_LN = ['out_fragments', 'out_bias', 'residual', 'residual_row_stride', 'ln_weight', 'ln_bias', 'ln_eps']
+DA_PARAMS = {
+    'fwd': DA_FWD + ['head_stride', 'slots', 'stream'],
+    'fwd_e': DA_FWD + ['head_stride', 'elem_type', 'slots', 'stream'],
+    'fwd_zt': DA_FWD + ['head_stride', 'bev_w', 'slots', 'stream'],
+    'fwd_planes': DA_FWD + ['bev_w', 'min_level_width', 'slots', 'stream'],
+    'fused': ['value'] + DA_FUSED + DA_FUSED_TAIL,
+    'fused_e': ['value', 'elem_type'] + DA_FUSED + DA_FUSED_TAIL,
+    'fused_ln': ['value'] + DA_FUSED + DA_LN + DA_FUSED_TAIL,
+    'bwd': DA_BWD + ['stream'],
+    'bwd_ex': DA_BWD + ['H0', 'W0', 'flags', 'det_ws', 'det_ws_bytes', 'stream'],
+    'bwd_ws': DA_BWD + ['level_hw', 'ws', 'ws_bytes', 'stream'],
+    'bwd_ws_grid': DA_BWD + ['level_hw', 'ws', 'ws_bytes', 'bev_w', 'stream'],
+    'bwd_ws_grid_ex': DA_BWD + ['level_hw', 'ws', 'ws_bytes', 'bev_w', 'flags', 'det_ws', 'det_ws_bytes', 'stream'],
+    'bwd_planes': DA_BWD + ['level_hw', 'ws', 'ws_bytes', 'bev_w', 'stream'],
+    'bwd_planes_ex': DA_BWD + ['level_hw', 'ws', 'ws_bytes', 'bev_w', 'flags', 'det_ws', 'det_ws_bytes', 'stream'],
+}
+# a call that would LAUNCH (so no row below is this alone): one sample, 6 cameras, one 22 x 32 level, 8 heads of 10 channels,
+# 100 queries on a 10-wide grid, 8 points on 4 anchors, 80 depth bins; every pointer non-null and 16-byte aligned
+DA_BASE = dict(B=1, Ncam=6, S=704, M=8, Dh=10, L=1, Q=100, P=8, Za=4, DC=80, d0=2.0, dstep=0.5, head_minor=0, head_stride=0,
+               elem_type=1, bev_w=10, min_level_width=2, query_row_stride=0, addend=DA_NULL, addend_row_stride=0, addend_period=0,
+               residual=DA_NULL, residual_row_stride=0, ln_eps=1e-5, H0=22, W0=32, flags=1, det_ws_bytes=1 << 40, level_hw=DA_NULL,
+               ws_bytes=1 << 40, stream=DA_NULL)
+DA_INTS = set(DA_DIMS) | {'head_minor', 'head_stride', 'elem_type', 'bev_w', 'min_level_width', 'query_row_stride',
+                          'addend_row_stride', 'addend_period', 'residual_row_stride', 'H0', 'W0', 'flags', 'det_ws_bytes', 'ws_bytes'}
+
+
+def da_call(lib, entry, case):
+    """`entry` with DA_BASE's operands, `case` on top of them; 'null': every pointer the entry takes is null unless `case` names it"""
+    case = dict(case)
+    null = case.pop('null', False)
+    args = []
+    for name in DA_PARAMS[entry]:
+        if name in case:
+            args.append(case.pop(name))
+        elif name in DA_BASE and (name in DA_INTS or name in ('d0', 'dstep', 'ln_eps') or not null):
+            args.append(DA_BASE[name])
+        else:
+            args.append(DA_NULL if null else DA_P16)
+    assert not case, (entry, 'operands the entry does not take', case)
+    return getattr(lib, 'fbbev_da_cross_attn_' + entry)(*args)
+
+
+def test_da_cross_attn_entries_keep_their_error_codes_and_plan_sizes():
+    """Every entry of the depth-aware cross-attention family: the code of each argument check, and which code wins where two
+    defects coincide (the order of an entry's checks is part of the ABI).  Every row returns BEFORE any runtime call, so this
+    runs without a GPU.  Below the table, the pure host functions (probes, workspace sizes) as the numbers they returned when
+    the table was recorded."""
+    lib = _capi.declare(ctypes.CDLL(_capi.LIB_PATH))
+    NULL, P16, P8, P4 = DA_NULL, DA_P16, DA_P8, DA_P4
+    LOGITS = 0x10                                                    # FBBEV_DA_ATTN_LOGITS
+    hw_22x32 = (ctypes.c_int32 * 2)(22, 32)
+    hw_2x2 = (ctypes.c_int32 * 2)(2, 2)
+    hw_bad = (ctypes.c_int32 * 2)(0, 32)
+    small_det = dict(level_hw=hw_22x32, det_ws_bytes=16)
+    # the smallest shape fbbev_da_cross_attn_bwd_planes_supported takes with the knobs unset: 256 (sample, camera, head) planes of
+    # one 2 x 2 level, rows padded to 12 floats
+    planes_ok = dict(B=4, Ncam=8, S=4, Q=64, bev_w=8, head_stride=12, level_hw=hw_2x2)
+    assert lib.fbbev_da_cross_attn_bwd_planes_supported(4, 8, 4, 8, 10, 1, 64, 8, 4, 12, hw_2x2, 8) == 1
+    assert lib.fbbev_da_cross_attn_bwd_planes_supported(4, 7, 4, 8, 10, 1, 64, 8, 4, 12, hw_2x2, 8) == 0      # 224 planes
+    table = [
+        # ---- fbbev_da_cross_attn_fwd: dimensions, Za / P % Za (-2), dstep (-1), empty (0), null pointers, row layout
+        ('fwd', dict(B=0), -1),
+        ('fwd', dict(DC=0), -1),
+        ('fwd', dict(Q=-1), -1),
+        ('fwd', dict(Q=0, null=True), 0),
+        ('fwd', dict(slots=NULL), -1),
+        ('fwd', dict(value=NULL), -1),
+        ('fwd', dict(Za=16), -2),
+        ('fwd', dict(P=6), -2),
+        ('fwd', dict(dstep=0.0), -1),
+        ('fwd', dict(Za=16, dstep=0.0), -2),
+        ('fwd', dict(Za=16, B=0), -1),
+        ('fwd', dict(Za=16, Q=0, null=True), -2),
+        ('fwd', dict(Q=0, dstep=0.0, null=True), -1),
+        ('fwd', dict(Za=16, mask=NULL), -2),
+        ('fwd', dict(head_stride=8), -1),
+        ('fwd', dict(head_stride=8, attn=NULL), -1),
+        ('fwd', dict(head_minor=4, head_stride=10), -2),
+        ('fwd', dict(head_minor=4, head_stride=8), -1),
+        ('fwd', dict(head_minor=4, head_stride=12, value=P8), -2),
+        ('fwd', dict(head_minor=4, head_stride=12, B=3000), -2),                   # chunk-major rows past 32-bit byte offsets
+        # ---- fbbev_da_cross_attn_fwd_e: the element type first, then fwd's order; 16-bit rows are chunk-major pieces of 8
+        ('fwd_e', dict(elem_type=3), -1),
+        ('fwd_e', dict(elem_type=-1, Za=16), -1),
+        ('fwd_e', dict(elem_type=0, Za=16), -2),
+        ('fwd_e', dict(elem_type=0, head_stride=8), -1),
+        ('fwd_e', dict(elem_type=0, Q=0, null=True), 0),
+        ('fwd_e', dict(B=0), -1),
+        ('fwd_e', dict(Q=0, null=True), 0),
+        ('fwd_e', dict(elem_type=2, Q=0, null=True), 0),
+        ('fwd_e', dict(attn=NULL), -1),
+        ('fwd_e', dict(Za=16), -2),
+        ('fwd_e', dict(dstep=0.0), -1),
+        ('fwd_e', dict(Za=16, dstep=0.0), -2),
+        ('fwd_e', dict(Q=0, dstep=0.0, null=True), -1),
+        ('fwd_e', dict(head_minor=0, head_stride=16), -2),
+        ('fwd_e', dict(head_minor=0, head_stride=16, slots=NULL), -1),
+        ('fwd_e', dict(head_minor=4, head_stride=16, Dh=12), -2),
+        ('fwd_e', dict(head_minor=4, head_stride=8), -2),                          # a row of 8 does not hold Dh = 10
+        ('fwd_e', dict(head_minor=4, head_stride=0, Dh=8), -2),                    # 16-bit rows: 0 is no stride (not "dense")
+        ('fwd_e', dict(head_minor=4, head_stride=16, slots=P4), -2),
+        ('fwd_e', dict(head_minor=4, head_stride=16, value=P8), -2),
+        # ---- fbbev_da_cross_attn_fwd_zt: its own dimensions (with bev_w), then the pipelined kernel or fwd's checks
+        ('fwd_zt', dict(bev_w=-1), -1),
+        ('fwd_zt', dict(B=0), -1),
+        ('fwd_zt', dict(Q=0, null=True), 0),
+        ('fwd_zt', dict(head_minor=LOGITS), -2),
+        ('fwd_zt', dict(head_minor=LOGITS | 5, head_stride=12, Za=2), -2),         # the pipelined kernel takes 4 anchors
+        ('fwd_zt', dict(head_minor=LOGITS, B=0), -1),
+        ('fwd_zt', dict(head_minor=LOGITS, dstep=0.0), -2),
+        ('fwd_zt', dict(head_minor=LOGITS, slots=NULL), -2),
+        ('fwd_zt', dict(Za=16), -2),
+        ('fwd_zt', dict(dstep=0.0), -1),
+        ('fwd_zt', dict(Za=16, dstep=0.0), -2),
+        ('fwd_zt', dict(slots=NULL), -1),
+        ('fwd_zt', dict(head_stride=8), -1),
+        ('fwd_zt', dict(head_minor=5, head_stride=12, spatial_shapes=NULL), -1),   # a shape the pipelined kernel takes
+        ('fwd_zt', dict(head_minor=5, head_stride=12, qdepth=NULL), -1),
+        # ---- fbbev_da_cross_attn_fwd_planes: dimensions, empty (0) BEFORE dstep, null pointers / dstep, shape and alignment
+        ('fwd_planes', dict(B=0), -1),
+        ('fwd_planes', dict(bev_w=-1), -1),
+        ('fwd_planes', dict(Q=0, null=True), 0),
+        ('fwd_planes', dict(Q=0, dstep=0.0, null=True), 0),
+        ('fwd_planes', dict(dstep=0.0), -1),
+        ('fwd_planes', dict(value=NULL), -1),
+        ('fwd_planes', dict(value=NULL, M=4), -1),
+        ('fwd_planes', dict(M=4), -2),
+        ('fwd_planes', dict(M=4, dstep=0.0), -1),
+        ('fwd_planes', dict(Za=8), -2),
+        ('fwd_planes', dict(min_level_width=1), -2),
+        ('fwd_planes', dict(offsets=P4), -2),
+        ('fwd_planes', dict(slots=P4), -2),
+        ('fwd_planes', dict(ref_cam=P8), -2),
+        ('fwd_planes', dict(mask=ctypes.c_void_p(0x1002)), -2),
+        # ---- fbbev_da_cross_attn_fused / _e / _ln
+        ('fused', dict(B=0), -1),
+        ('fused', dict(bev_w=-1), -1),
+        ('fused', dict(Q=0, null=True), 0),
+        ('fused', dict(Q=0, dstep=0.0, null=True), 0),
+        ('fused', dict(query=NULL), -1),
+        ('fused', dict(value=NULL), -1),
+        ('fused', dict(dstep=0.0), -1),
+        ('fused', dict(query_row_stride=40), -1),
+        ('fused', dict(query_row_stride=82), -2),
+        ('fused', dict(addend=P16, addend_period=0), -1),
+        ('fused', dict(addend=P16, addend_period=1, addend_row_stride=40), -1),
+        ('fused', dict(addend=P16, addend_period=1, addend_row_stride=82), -2),
+        ('fused', dict(addend=P8, addend_period=1), -2),
+        ('fused', dict(min_level_width=1), -2),
+        ('fused', dict(M=4), -2),
+        ('fused', dict(bev_w=0), -2),
+        ('fused', dict(bev_w=7), -2),
+        ('fused', dict(Ncam=33), -2),
+        ('fused', dict(value=P4), -2),
+        ('fused', dict(slots=P4), -2),
+        ('fused', dict(M=4, query_row_stride=20), -1),
+        ('fused', dict(min_level_width=1, addend=P16, addend_period=0), -1),
+        ('fused', dict(M=4, query=NULL), -1),
+        ('fused_e', dict(elem_type=3), -1),
+        ('fused_e', dict(elem_type=3, Q=0, null=True), -1),
+        ('fused_e', dict(elem_type=0, M=4), -2),
+        ('fused_e', dict(Q=0, null=True), 0),
+        ('fused_e', dict(query_row_stride=40), -1),
+        ('fused_e', dict(query_row_stride=82), -2),
+        ('fused_e', dict(elem_type=2, addend=P16, addend_period=0), -1),
+        ('fused_e', dict(elem_type=2, min_level_width=1), -2),
+        # (_ln: the tail's own checks come first)
+        ('fused_ln', dict(out_bias=NULL), -1),
+        ('fused_ln', dict(ln_eps=-1.0), -1),
+        ('fused_ln', dict(M=0, out_fragments=P8), -1),
+        ('fused_ln', dict(residual=P8, B=0), -2),
+        ('fused_ln', dict(residual=P16, residual_row_stride=40), -1),
+        ('fused_ln', dict(residual=P16, residual_row_stride=82), -2),
+        ('fused_ln', dict(residual=P16, residual_row_stride=40, ln_bias=P8), -1),
+        ('fused_ln', dict(Dh=9), -2),                                              # E % 16
+        ('fused_ln', dict(slots=P8), -2),
+        ('fused_ln', dict(slots=P8, out_bias=NULL), -1),
+        ('fused_ln', dict(B=0), -1),
+        ('fused_ln', dict(query=NULL), -1),
+        ('fused_ln', dict(query_row_stride=40), -1),
+        ('fused_ln', dict(query_row_stride=82), -2),
+        ('fused_ln', dict(addend=P16, addend_period=0), -1),
+        ('fused_ln', dict(min_level_width=1), -2),
+        # ---- fbbev_da_cross_attn_bwd: fwd's order, then Dh > 32 (-2), the row stride (-1), chunk-major rows (-2)
+        ('bwd', dict(B=0), -1),
+        ('bwd', dict(Q=0, null=True), 0),
+        ('bwd', dict(grad_attn=NULL), -1),
+        ('bwd', dict(grad_slots=NULL), -1),
+        ('bwd', dict(Za=16), -2),
+        ('bwd', dict(P=6), -2),
+        ('bwd', dict(dstep=0.0), -1),
+        ('bwd', dict(Za=16, dstep=0.0), -2),
+        ('bwd', dict(Q=0, dstep=0.0, null=True), -1),
+        ('bwd', dict(Za=16, grad_value=NULL), -2),
+        ('bwd', dict(Dh=40), -2),
+        ('bwd', dict(Dh=40, grad_attn=NULL), -1),
+        ('bwd', dict(head_stride=8), -1),
+        ('bwd', dict(Dh=40, head_stride=8), -2),
+        ('bwd', dict(head_minor=4, head_stride=10), -2),
+        ('bwd', dict(head_minor=4, head_stride=8), -1),
+        ('bwd', dict(B=1 << 15, Q=1 << 16), -2),                                   # more workgroups than a grid holds
+        # ---- fbbev_da_cross_attn_bwd_ex: without the flag it is bwd; with it H0 / W0 join the dimensions, det_ws the pointers
+        ('bwd_ex', dict(flags=0, Za=16), -2),
+        ('bwd_ex', dict(flags=0, H0=0, Dh=40), -2),
+        ('bwd_ex', dict(flags=0, det_ws=NULL, grad_attn=NULL), -1),
+        ('bwd_ex', dict(flags=0, Q=0, null=True), 0),
+        ('bwd_ex', dict(H0=0), -1),
+        ('bwd_ex', dict(W0=0, Za=16), -1),
+        ('bwd_ex', dict(B=0), -1),
+        ('bwd_ex', dict(Za=16), -2),
+        ('bwd_ex', dict(dstep=0.0), -1),
+        ('bwd_ex', dict(Za=16, dstep=0.0), -2),
+        ('bwd_ex', dict(Q=0, null=True), 0),
+        ('bwd_ex', dict(det_ws=NULL), -1),
+        ('bwd_ex', dict(grad_offsets=NULL), -1),
+        ('bwd_ex', dict(Dh=40), -2),
+        ('bwd_ex', dict(Dh=40, det_ws=NULL), -1),
+        ('bwd_ex', dict(head_stride=8), -1),
+        ('bwd_ex', dict(head_minor=4, head_stride=10), -2),
+        ('bwd_ex', dict(det_ws_bytes=16), -3),
+        ('bwd_ex', dict(det_ws=P8), -3),                                           # enough bytes, 8-byte aligned only
+        ('bwd_ex', dict(head_minor=4, head_stride=10, det_ws_bytes=16), -2),
+        ('bwd_ex', dict(head_stride=8, det_ws_bytes=16), -1),
+        # ---- fbbev_da_cross_attn_bwd_ws / _ws_grid without a workspace (or with one too small for either plan): bwd's checks
+        ('bwd_ws', dict(ws=NULL, B=0), -1),
+        ('bwd_ws', dict(ws=NULL, Q=0, null=True), 0),
+        ('bwd_ws', dict(ws=NULL, Za=16), -2),
+        ('bwd_ws', dict(ws=NULL, dstep=0.0), -1),
+        ('bwd_ws', dict(ws=NULL, Za=16, dstep=0.0), -2),
+        ('bwd_ws', dict(ws=NULL, grad_attn=NULL), -1),
+        ('bwd_ws', dict(ws=NULL, Dh=40), -2),
+        ('bwd_ws', dict(ws=NULL, head_stride=8), -1),
+        ('bwd_ws', dict(ws_bytes=16, dstep=0.0), -1),
+        ('bwd_ws', dict(ws_bytes=16, Za=16, level_hw=hw_22x32), -2),
+        ('bwd_ws', dict(ws=P8, Dh=40), -2),
+        ('bwd_ws_grid', dict(ws=NULL, bev_w=-1), -1),
+        ('bwd_ws_grid', dict(ws=NULL, bev_w=-1, Za=16), -1),
+        ('bwd_ws_grid', dict(ws=NULL, B=0), -1),
+        ('bwd_ws_grid', dict(ws=NULL, Q=0, null=True), 0),
+        ('bwd_ws_grid', dict(ws=NULL, Za=16), -2),
+        ('bwd_ws_grid', dict(ws=NULL, dstep=0.0), -1),
+        ('bwd_ws_grid', dict(ws=NULL, value=NULL), -1),
+        ('bwd_ws_grid', dict(ws_bytes=16, level_hw=hw_22x32, dstep=0.0), -1),
+        # ---- _bwd_ws_grid_ex / _bwd_planes_ex: without the flag the plain entry; with it the deterministic wrapper's checks first
+        # (no row passes them: the next thing it does is a runtime memset)
+        ('bwd_ws_grid_ex', dict(flags=0, ws=NULL, Za=16), -2),
+        ('bwd_ws_grid_ex', dict(flags=0, ws=NULL, bev_w=-1), -1),
+        ('bwd_ws_grid_ex', dict(flags=0, ws=NULL, dstep=0.0, det_ws=NULL), -1),
+        ('bwd_ws_grid_ex', dict(flags=0, ws=NULL, Q=0, null=True), 0),
+        ('bwd_ws_grid_ex', dict(), -1),                                            # level_hw_host is required
+        ('bwd_ws_grid_ex', dict(M=3), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, M=3), -2),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, M=128), -2),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, det_ws=NULL), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, grad_pred_depth=NULL), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, B=0), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, Q=0), -1),                      # (no empty case on this route)
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, dstep=0.0, M=3), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_bad), -1),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_bad, M=3), -2),
+        ('bwd_ws_grid_ex', small_det, -3),
+        ('bwd_ws_grid_ex', dict(small_det, M=3), -2),
+        ('bwd_ws_grid_ex', dict(level_hw=hw_22x32, det_ws=P8), -3),
+        ('bwd_planes_ex', dict(flags=0, ws=NULL), -1),
+        ('bwd_planes_ex', dict(flags=0, Za=8), -2),
+        ('bwd_planes_ex', dict(flags=0, bev_w=0), -1),
+        ('bwd_planes_ex', dict(flags=0, ws_bytes=16, **planes_ok), -3),
+        ('bwd_planes_ex', dict(), -1),
+        ('bwd_planes_ex', dict(level_hw=hw_22x32, M=3), -2),
+        ('bwd_planes_ex', dict(level_hw=hw_22x32, qdepth=NULL), -1),
+        ('bwd_planes_ex', dict(level_hw=hw_22x32, Q=0), -1),
+        ('bwd_planes_ex', small_det, -3),
+        ('bwd_planes_ex', dict(small_det, M=3), -2),
+        ('bwd_planes_ex', dict(level_hw=hw_22x32, det_ws=P8), -3),
+        # ---- fbbev_da_cross_attn_bwd_planes: dimensions (Q and bev_w positive), pointers, dstep, the route's shape (-2),
+        # alignment (-2), workspace (-3)
+        ('bwd_planes', dict(level_hw=hw_22x32, bev_w=0), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, Q=0, null=True), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, ws=NULL), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, value=NULL), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, dstep=0.0), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, Za=8), -2),
+        ('bwd_planes', dict(level_hw=hw_22x32, Za=8, dstep=0.0), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, Za=8, ws=NULL), -1),
+        ('bwd_planes', dict(level_hw=hw_22x32, head_stride=8), -2),                # (a short row stride is -2 on this route)
+        ('bwd_planes', dict(level_hw=hw_22x32, bev_w=7), -2),
+        ('bwd_planes', dict(head_stride=12), -2),                                  # no host level shapes: no head-plane route
+        ('bwd_planes', dict(ws_bytes=16, **planes_ok), -3),
+        ('bwd_planes', dict(grad_value=P8, **planes_ok), -2),
+        ('bwd_planes', dict(grad_value=P8, ws_bytes=16, **planes_ok), -2),
+        ('bwd_planes', dict(grad_slots=P4, **planes_ok), -2),
+        ('bwd_planes', dict(ws=P8, **planes_ok), -2),
+    ]
+    got = [(entry, {k: (v.value if isinstance(v, ctypes.c_void_p) else v) for k, v in case.items() if k != 'level_hw'},
+            da_call(lib, entry, case)) for entry, case, _ in table]
+    want = [(entry, {k: (v.value if isinstance(v, ctypes.c_void_p) else v) for k, v in case.items() if k != 'level_hw'}, code)
+            for entry, case, code in table]
+    assert got == want, [(g, w[2]) for g, w in zip(got, want) if g != w]
+    # ---- the pure host functions: every one goes through a plan or a shape check of this family
+    pyramid = (ctypes.c_int32 * 8)(16, 44, 32, 88, 8, 22, 4, 11)
+    shapes = {
+        # BASELINE configs[2]: 4 samples, 6 cameras, the 4-level pyramid, 8 heads of 10 channels in rows of 12, 200 x 200 queries
+        'configs2': dict(B=4, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        'one 2 x 2 level': dict(B=1, Ncam=2, S=4, M=8, Dh=10, L=1, Q=16, P=8, Za=4, DC=8, HS=12, bev_w=4, hw=hw_2x2, H0=2, W0=2),
+        'one level, no host shapes': dict(B=2, Ncam=6, S=704, M=8, Dh=8, L=1, Q=2500, P=8, Za=4, DC=59, HS=0, bev_w=50, hw=NULL,
+                                          H0=22, W0=32),
+        '33 cameras': dict(B=4, Ncam=33, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        '4 heads': dict(B=4, Ncam=6, S=3740, M=4, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        '2 anchors': dict(B=4, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=2, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        'no samples': dict(B=0, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        'no queries': dict(B=4, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=0, P=8, Za=4, DC=59, HS=12, bev_w=200, hw=pyramid, H0=16, W0=44),
+        'rows shorter than a head': dict(B=4, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=8, bev_w=200, hw=pyramid,
+                                         H0=16, W0=44),
+        'queries off the grid': dict(B=4, Ncam=6, S=3740, M=8, Dh=10, L=4, Q=40000, P=8, Za=4, DC=59, HS=12, bev_w=199, hw=pyramid,
+                                     H0=16, W0=44),
+    }
+    functions = {
+        'bwd_ws_bytes': ('B', 'Ncam', 'S', 'M', 'Dh', 'Q', 'HS', 'L', 'P', 'hw'),
+        'bwd_ws_bytes_za': ('B', 'Ncam', 'S', 'M', 'Dh', 'Q', 'HS', 'L', 'P', 'Za', 'hw'),
+        'bwd_det_ws_bytes': ('B', 'Ncam', 'S', 'M', 'HS', 'Q', 'Za', 'DC', 'H0', 'W0'),
+        'fused_supported': ('B', 'Ncam', 'S', 'M', 'Dh', 'L', 'Q', 'P', 'Za', 'bev_w'),
+        'fwd_planes_supported': ('B', 'Ncam', 'S', 'M', 'Dh', 'L', 'Q', 'P', 'Za'),
+        'bwd_planes_supported': ('B', 'Ncam', 'S', 'M', 'Dh', 'L', 'Q', 'P', 'Za', 'HS', 'hw', 'bev_w'),
+        'fwd_zt_fuses_softmax': ('B', 'Ncam', 'S', 'M', 'Dh', 'L', 'Q', 'P', 'Za', 'head_minor', 'HS'),
+    }
+    # columns: the seven functions above in order, then fbbev_da_bwd_det_ws_bytes and fbbev_da_depth_taps_det_ws_bytes
+    recorded = {
+        'configs2': (582205440, 90163712, 215151104, 1, 1, 1, 1, 23335168, 7975168),
+        'one 2 x 2 level': (3072, 3072, 11776, 1, 1, 0, 1, 1280, 768),
+        'one level, no host shapes': (21626880, 21626880, 0, 1, 1, 0, 1, 4467712, 3987712),
+        '33 cameras': (3202129920, 337921024, 1183328768, 0, 1, 0, 1, 128342272, 43862272),
+        '4 heads': (496035840, 61440512, 119243264, 0, 0, 0, 1, 23335168, 7975168),
+        '2 anchors': (582205440, 90163712, 146031104, 0, 0, 0, 0, 15655168, 7975168),
+        'no samples': (0, 0, 0, 0, 0, 0, 0, 0, 0),
+        'no queries': (0, 0, 76911104, 0, 0, 0, 0, 0, 7975168),
+        'rows shorter than a head': (0, 0, 192172544, 1, 1, 0, 0, 23335168, 7975168),
+        'queries off the grid': (582205440, 90163712, 215151104, 0, 1, 0, 1, 23335168, 7975168),
+    }
+    for name, s in shapes.items():
+        s = dict(s, head_minor=5)
+        row = tuple(getattr(lib, 'fbbev_da_cross_attn_' + f)(*(s[k] for k in keys)) for f, keys in functions.items())
+        row += (lib.fbbev_da_bwd_det_ws_bytes(*(s[k] for k in ('B', 'Ncam', 'Q', 'Za', 'DC', 'H0', 'W0'))),
+                lib.fbbev_da_depth_taps_det_ws_bytes(*(s[k] for k in ('B', 'Ncam', 'DC', 'H0', 'W0'))))
+        assert row == recorded[name], (name, row)
+    # the pipelined forward takes head-minor offsets on chunk-major rows only
+    s = shapes['configs2']
+    assert lib.fbbev_da_cross_attn_fwd_zt_fuses_softmax(*(s[k] for k in functions['fwd_zt_fuses_softmax'][:9]), 1, 12) == 0
+    assert lib.fbbev_da_cross_attn_fwd_zt_fuses_softmax(*(s[k] for k in functions['fwd_zt_fuses_softmax'][:9]), 5, 0) == 0
