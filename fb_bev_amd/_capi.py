@@ -780,9 +780,10 @@ def da_cross_attn_bwd_ws_bytes(B, Ncam, S, M, Dh, Q, HS, L, P, level_hw=None, Za
 
 def da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_cam, mask, qdepth, offsets, attn,
                       grad_slots, d0, dstep, head_minor, grad_value, grad_pred_depth, grad_offsets, grad_attn, head_dim=None,
-                      lds_planes=True, level_hw=None, bev_w=0):
+                      lds_planes=True, level_hw=None, bev_w=0, grid_entry=True):
     """Backward of da_cross_attn_fwd; the four grad tensors must be pre-zeroed (accumulated into).  bev_w: width of the BEV grid
-    the Q queries form (0 = a plain list): lets the unit-gradient kernel take 8 x 8 patches of it."""
+    the Q queries form (0 = a plain list): lets the unit-gradient kernel take 8 x 8 patches of it.  grid_entry=False (bev_w must be
+    0): the LDS-plane routes through fbbev_da_cross_attn_bwd_ws, the entry without a grid width."""
     Ncam, B, Q, Za = mask.shape
     _, S, M, HS = value.shape
     Dh = HS if head_dim is None else int(head_dim)
@@ -810,6 +811,11 @@ def da_cross_attn_bwd(value, spatial_shapes, level_start_index, pred_depth, ref_
             if any(t.data_ptr() % 8 for t in (offsets, grad_offsets, grad_slots)):       # the owned route's alignment: size for both
                 need = max(need, lib().fbbev_da_cross_attn_bwd_ws_bytes(B, Ncam, S, M, Dh, Q, HS, L, P, arr))
             ws = torch.empty(need // 4, dtype=torch.float32, device=value.device)
+            if not grid_entry:
+                if bev_w:
+                    raise FbbevError('da_cross_attn_bwd: grid_entry=False takes no bev_w')
+                _check(lib().fbbev_da_cross_attn_bwd_ws(*args, arr, ws.data_ptr(), need, _stream()), 'fbbev_da_cross_attn_bwd_ws')
+                return
             _check(lib().fbbev_da_cross_attn_bwd_ws_grid(*args, arr, ws.data_ptr(), need, int(bev_w or 0), _stream()),
                    'fbbev_da_cross_attn_bwd_ws_grid')
         else:

@@ -1,5 +1,7 @@
 """Random DA cross-attention cases + the oracle's composite result, shared by the emulator tests (tests/test_emu_kernels.py)
-and the GPU bound test of the fused backward (tests/test_gpu_backward_projection.py).  Test infrastructure."""
+and the GPU bound test of the fused backward (tests/test_gpu_backward_projection.py).  Test infrastructure.
+The route-by-route case table of the same kernel family -- exact dyadic inputs, derived bounds, a float64 reference written from the
+contract -- is tests/da_kernel_cases.py."""
 import torch
 
 

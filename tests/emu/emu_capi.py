@@ -411,10 +411,10 @@ def da_cross_attn_fused(planes, ss, ls, pred_depth, ref_cam, mask, qdepth, query
         return code, slots
     if planes.dtype in (torch.bfloat16, torch.float16):      # fbbev_da_cross_attn_fused_e: 16-bit head planes
         code = lib().fbbev_da_cross_attn_fused_e(p(planes), 1 if planes.dtype == torch.bfloat16 else 2, p(ss), p(ls), p(pred_depth), p(ref_cam),
-                                                 p(m8), p(qdepth), p(query), query.stride(1), *a, p_so, p(b_so), p_aw, p(b_aw), B, Ncam, S, M,
+                                                 p(m8), p(qdepth), c_void_p(query.data_ptr()), query.stride(1), *a, p_so, p(b_so), p_aw, p(b_aw), B, Ncam, S, M,
                                                  Dh, L, Q, P, Za, pred_depth.shape[1], d0, dstep, bev_w, min_level_width, p(slots), None)
         return code, slots
-    code = lib().fbbev_da_cross_attn_fused(p(planes), p(ss), p(ls), p(pred_depth), p(ref_cam), p(m8), p(qdepth), p(query),
+    code = lib().fbbev_da_cross_attn_fused(p(planes), p(ss), p(ls), p(pred_depth), p(ref_cam), p(m8), p(qdepth), c_void_p(query.data_ptr()),
                                            query.stride(1), *a, p_so, p(b_so), p_aw, p(b_aw), B, Ncam, S, M, Dh, L, Q, P, Za,
                                            pred_depth.shape[1], d0, dstep, bev_w, min_level_width, p(slots), None)
     return code, slots
@@ -746,3 +746,71 @@ def softmax_groups(x, group):
 def softmax_groups_bwd(y, gy, group):
     out = torch.full_like(y, float('nan'))
     return lib().fbbev_softmax_groups_bwd(p(y), p(gy), y.numel() // group, group, p(out), None), out
+
+
+def da_cross_attn_bwd_entry(entry, src, ss, ls, pred_depth, ref_cam, mask, qdepth, offsets, attn, d0, dstep, grad_slots, head_dim, HS,
+                            head_minor=0, level_hw=None, bev_w=0, flags=None, prefill=None):
+    """Any DA backward entry on CPU tensors.  entry: 'bwd' | 'ws' | 'ws_grid' | 'planes' (flags not None: its _ex form; 'ws' has
+    none).  src: value rows (B*Ncam, S, M, HS) -- or, for 'planes', head planes (B*Ncam, M, S, Dh).  prefill: {'gv' | 'gd' | 'go' |
+    'ga': fill} for outputs that do not start as zeros.  Returns (code, grad_value rows (B*Ncam, S, M, HS), gd, go, ga)."""
+    Ncam, B, Q, Za = mask.shape
+    if entry == 'planes':
+        BN, M, S, _ = src.shape
+    else:
+        BN, S, M, _ = src.shape
+    Dh = int(head_dim)
+    L, P = (attn.shape[2], attn.shape[3]) if head_minor & 2 else (attn.shape[3], attn.shape[4])
+    DC = pred_depth.shape[1]
+    prefill = prefill or {}
+    gv = torch.full((BN, S, M, HS), float(prefill.get('gv', 0.0)))
+    gd = torch.full_like(pred_depth, float(prefill.get('gd', 0.0)))
+    go = torch.full_like(offsets, float(prefill.get('go', 0.0)))
+    ga = torch.full_like(attn, float(prefill.get('ga', 0.0)))
+    m8 = mask.to(torch.uint8).contiguous()
+    args = (p(src), p(ss), p(ls), p(pred_depth), p(ref_cam), p(m8), p(qdepth), p(offsets), p(attn), p(grad_slots), B, Ncam,
+            S, M, Dh, L, Q, P, Za, DC, d0, dstep, int(head_minor), HS, p(gv), p(gd), p(go), p(ga))
+    H0, W0 = (int(x) for x in ss[0].tolist())
+    if entry == 'bwd':
+        if flags is None:
+            return lib().fbbev_da_cross_attn_bwd(*args, None), gv, gd, go, ga
+        need = lib().fbbev_da_cross_attn_bwd_det_ws_bytes(B, Ncam, S, M, HS, Q, Za, DC, H0, W0)
+        dws = torch.full(((need + 15) // 16 * 4,), float('nan'))
+        return lib().fbbev_da_cross_attn_bwd_ex(*args, H0, W0, flags, p(dws), need, None), gv, gd, go, ga
+    arr = _capi._level_hw(level_hw, L)
+    need = lib().fbbev_da_cross_attn_bwd_ws_bytes_za(B, Ncam, S, M, Dh, Q, HS, L, P, Za, arr)
+    ws = torch.full((max(need, 16) // 4,), float('nan'))
+    tail = (arr, p(ws), need)
+    if flags is not None:
+        dneed = lib().fbbev_da_bwd_det_ws_bytes(B, Ncam, Q, Za, DC, H0, W0)
+        dws = torch.full((dneed // 4 + 4,), float('nan'))
+        fn = lib().fbbev_da_cross_attn_bwd_planes_ex if entry == 'planes' else lib().fbbev_da_cross_attn_bwd_ws_grid_ex
+        assert entry in ('planes', 'ws_grid')
+        return fn(*args, *tail, int(bev_w), flags, p(dws), dneed, None), gv, gd, go, ga
+    if entry == 'planes':
+        return lib().fbbev_da_cross_attn_bwd_planes(*args, *tail, int(bev_w), None), gv, gd, go, ga
+    if entry == 'ws_grid':
+        return lib().fbbev_da_cross_attn_bwd_ws_grid(*args, *tail, int(bev_w), None), gv, gd, go, ga
+    assert entry == 'ws'
+    return lib().fbbev_da_cross_attn_bwd_ws(*args, *tail, None), gv, gd, go, ga
+
+
+def value_rows_to_head_planes(rows, head_dim, interleaved=False):
+    """fbbev_value_rows_to_head_planes: (B*Ncam, S, M, HS) token rows -> (B*Ncam, M, S, Dh) head planes"""
+    BN, S, M, HS = rows.shape
+    planes = torch.full((BN, M, S, head_dim), float('nan'))
+    ok(lib().fbbev_value_rows_to_head_planes(p(rows), BN * S, S, M, head_dim, HS, 1 if interleaved else 0, p(planes), None))
+    return planes
+
+
+def da_cross_attn_fwd_planes_on(planes, ss, ls, pred_depth, ref_cam, mask, qdepth, offsets, attn, d0, dstep, head_minor=0, bev_w=0,
+                                min_level_width=2):
+    """fbbev_da_cross_attn_fwd_planes on head planes the caller holds -> (code, slots)"""
+    Ncam, B, Q, Za = mask.shape
+    BN, M, S, Dh = planes.shape
+    L, P = (attn.shape[2], attn.shape[3]) if head_minor & 2 else (attn.shape[3], attn.shape[4])
+    slots = torch.full((B, Q, M * Dh), float('nan'))
+    m8 = mask.to(torch.uint8).contiguous()
+    code = lib().fbbev_da_cross_attn_fwd_planes(p(planes), p(ss), p(ls), p(pred_depth), p(ref_cam), p(m8), p(qdepth), p(offsets), p(attn),
+                                                B, Ncam, S, M, Dh, L, Q, P, Za, pred_depth.shape[1], d0, dstep, int(head_minor) & 3,
+                                                int(bev_w), int(min_level_width), p(slots), None)
+    return code, slots

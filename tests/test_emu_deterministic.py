@@ -147,24 +147,10 @@ def test_depth_taps_all_zero_and_non_finite():
 
 def _da_bwd_ex(value, ss, ls, pred, ref_cam, mask, qdepth, offsets, attn, d0, dstep, grad_slots, shapes, bev_w, flags, Dh, planes=None):
     """fbbev_da_cross_attn_bwd_ws_grid_ex (planes None) / fbbev_da_cross_attn_bwd_planes_ex on the emulator"""
-    Ncam, B, Q, Za = mask.shape
-    _, S, M, HS = value.shape
-    L, P = attn.shape[3], attn.shape[4]
-    DC = pred.shape[1]
-    gv, gd, go, ga = (torch.zeros_like(t) for t in (value, pred, offsets, attn))
-    m8 = mask.to(torch.uint8).contiguous()
-    arr = _capi._level_hw(shapes, L)
-    need = E.lib().fbbev_da_cross_attn_bwd_ws_bytes_za(B, Ncam, S, M, Dh, Q, HS, L, P, Za, arr)
-    assert need > 0
-    ws = torch.full((need // 4,), float('nan'))
-    dneed = E.lib().fbbev_da_bwd_det_ws_bytes(B, Ncam, Q, Za, DC, *shapes[0])
-    dws = torch.full((dneed // 4 + 4,), float('nan'))
-    src = planes if planes is not None else value
-    args = (E.p(src), E.p(ss), E.p(ls), E.p(pred), E.p(ref_cam), E.p(m8), E.p(qdepth), E.p(offsets), E.p(attn), E.p(grad_slots), B, Ncam,
-            S, M, Dh, L, Q, P, Za, DC, d0, dstep, 0, HS, E.p(gv), E.p(gd), E.p(go), E.p(ga), arr, E.p(ws), need, bev_w, flags,
-            E.p(dws), dneed, None)
-    fn = E.lib().fbbev_da_cross_attn_bwd_planes_ex if planes is not None else E.lib().fbbev_da_cross_attn_bwd_ws_grid_ex
-    E.ok(fn(*args))
+    code, gv, gd, go, ga = E.da_cross_attn_bwd_entry('planes' if planes is not None else 'ws_grid', planes if planes is not None else value,
+                                                     ss, ls, pred, ref_cam, mask, qdepth, offsets, attn, d0, dstep, grad_slots, Dh,
+                                                     value.shape[-1], level_hw=shapes, bev_w=bev_w, flags=flags)
+    E.ok(code)
     return gv, gd, go, ga
 
 
