@@ -176,6 +176,11 @@ SIGNATURES = {
     'fbbev_da_cross_attn_fwd_planes_supported': (c_int, [c_int] * 9),
     'fbbev_da_cross_attn_fwd_planes': (c_int, [c_void_p] * 9 + [c_int] * 10 + [c_float, c_float, c_int, c_int, c_int] + [c_void_p, c_void_p]),
     'fbbev_occ_classes': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 6 + [c_void_p] * 6),
+    'fbbev_occ_loss_ws_bytes': (c_size_t, [c_int] * 5),
+    'fbbev_occ_loss_stats': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 3 + [c_int, c_int, c_float, c_float] +
+                             [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'fbbev_occ_loss_grad': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 3 + [c_int, c_int, c_float, c_float] +
+                            [c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1926,4 +1931,67 @@ def occ_classes(logits, c0=0, gt=None, mask=None, column_mask=None, hist=None, o
         _check(lib().fbbev_occ_classes(c_void_p(logits.data_ptr()), *[int(s) for s in logits.stride()], B, C, int(c0), H, W, D,
                                        _dev(out, U8, 'out'), opt(gt, U8, 'gt'), opt(mask, U8, 'mask'),
                                        opt(column_mask, U8, 'column_mask'), opt(hist, I32, 'hist'), _stream()), 'fbbev_occ_classes')
+    return out
+
+
+OCC_LOSS_FOCAL = 1                # include/fbbev.h FBBEV_OCC_LOSS_FOCAL
+
+
+def _occ_loss_args(logits, labels, class_weight, plane_weight, empty_idx, focal, gamma, alpha):
+    """the arguments fbbev_occ_loss_stats and fbbev_occ_loss_grad share, checked"""
+    require_gpu(logits, 'logits')
+    if logits.dtype != F32 or logits.dim() != 5:
+        raise FbbevError(f'logits must be a 5-D float32 tensor (B, C, H, W, D), got {logits.dtype} {tuple(logits.shape)}')
+    B, C, H, W, D = logits.shape
+    if tuple(labels.shape) != (B, H, W, D):
+        raise FbbevError(f'labels must be {(B, H, W, D)}, got {tuple(labels.shape)}')
+    if class_weight is not None and tuple(class_weight.shape) != (C,):
+        raise FbbevError(f'class_weight must be {(C,)}, got {tuple(class_weight.shape)}')
+    if plane_weight is not None and tuple(plane_weight.shape) != (H, W):
+        raise FbbevError(f'plane_weight must be {(H, W)}, got {tuple(plane_weight.shape)}')
+    if focal and plane_weight is None:
+        raise FbbevError('the focal mode needs plane_weight (H, W)')
+    opt = lambda t, name: None if t is None else _dev(t, F32, name)  # noqa: E731
+    return (c_void_p(logits.data_ptr()), *[int(s) for s in logits.stride()], B, C, H, W, D, _dev(labels, U8, 'labels'),
+            opt(class_weight, 'class_weight'), opt(plane_weight, 'plane_weight'), int(empty_idx), OCC_LOSS_FOCAL if focal else 0,
+            float(gamma), float(alpha))
+
+
+def occ_loss_stats(logits, labels, class_weight=None, plane_weight=None, empty_idx=0, focal=False, gamma=2.0, alpha=0.25,
+                   stats_f=None, stats_i=None, ws=None):
+    """fbbev_occ_loss_stats: the sufficient statistics of the occupancy head's voxel losses from one pass over logits (B, C, H, W, D)
+    f32 with ANY strides (no copy is made) and labels (B, H, W, D) uint8 (255 = not counted).  -> stats_f (3C + 4,) f32 = P, N, Q,
+    G, CLS, 0, 0 and stats_i (C + 1,) int32 = cnt, n_valid; see include/fbbev.h.  Bit-identical from run to run."""
+    args = _occ_loss_args(logits, labels, class_weight, plane_weight, empty_idx, focal, gamma, alpha)
+    B, C, H, W, D = logits.shape
+    if stats_f is None:
+        stats_f = torch.empty(3 * C + 4, dtype=F32, device=logits.device)
+    if stats_i is None:
+        stats_i = torch.empty(C + 1, dtype=I32, device=logits.device)
+    if tuple(stats_f.shape) != (3 * C + 4,) or tuple(stats_i.shape) != (C + 1,):
+        raise FbbevError(f'stats_f / stats_i must be {(3 * C + 4,)} / {(C + 1,)}, got {tuple(stats_f.shape)} / {tuple(stats_i.shape)}')
+    need = lib().fbbev_occ_loss_ws_bytes(B, C, H, W, D)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=U8, device=logits.device)
+    with _on(logits):
+        _check(lib().fbbev_occ_loss_stats(*args, _dev(stats_f, F32, 'stats_f'), _dev(stats_i, I32, 'stats_i'), _dev(ws, U8, 'ws'),
+                                          ws.numel(), _stream()), 'fbbev_occ_loss_stats')
+    return stats_f, stats_i
+
+
+def occ_loss_grad(logits, labels, grad_stats, class_weight=None, plane_weight=None, empty_idx=0, focal=False, gamma=2.0, alpha=0.25,
+                  out=None):
+    """fbbev_occ_loss_grad: the gradient of the logits from grad_stats (3C + 4,) f32, the gradient of occ_loss_stats' stats_f.  `out`
+    has the strides of logits (default: allocated so); every element of it is written."""
+    args = _occ_loss_args(logits, labels, class_weight, plane_weight, empty_idx, focal, gamma, alpha)
+    C = logits.shape[1]
+    if tuple(grad_stats.shape) != (3 * C + 4,):
+        raise FbbevError(f'grad_stats must be {(3 * C + 4,)}, got {tuple(grad_stats.shape)}')
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=F32, device=logits.device)
+    elif out.shape != logits.shape or out.stride() != logits.stride():
+        raise FbbevError(f'out must have the shape and strides of logits, got {tuple(out.shape)} {out.stride()}')
+    with _on(logits):
+        _check(lib().fbbev_occ_loss_grad(*args, _dev(grad_stats, F32, 'grad_stats'), _dev(out, F32, 'out', contiguous=False), _stream()),
+               'fbbev_occ_loss_grad')
     return out

@@ -25,6 +25,7 @@
 #include "conv3d_kernels.h"
 #include "det_kernels.h"
 #include "occ_kernels.h"
+#include "occ_loss_kernels.h"
 #include "../../include/fbbev.h"
 
 #include "capi_common.h"
@@ -3948,6 +3949,101 @@ extern "C" int fbbev_occ_classes(const float* logits, long long stride_b, long l
     else if (vec4) FBBEV_OCC_LAUNCH(false, true);
     else FBBEV_OCC_LAUNCH(false, false);
 #undef FBBEV_OCC_LAUNCH
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ occupancy voxel losses: statistics + gradient
+namespace {
+struct occl_plan {
+    int T, TD, nth, ntw, ntd, staged, row_runs;
+    long long ntiles, blocks;
+};
+// the tile walk of fbbev_occ_classes; the grid is a function of the shape alone (the workgroup records are added in grid order)
+occl_plan occl_plan_of(long long stride_c, long long stride_w, long long stride_d, int B, int C, int H, int W, int D) {
+    occl_plan p;
+    p.TD = D < 64 ? D : 64;
+    p.T = p.TD >= 16 ? 8 : 16;
+    p.nth = (H + p.T - 1) / p.T; p.ntw = (W + p.T - 1) / p.T; p.ntd = (D + p.TD - 1) / p.TD;
+    p.ntiles = (long long)B * p.nth * p.ntw * p.ntd;
+    p.blocks = p.ntiles < FBBEV_OCCL_MAX_BLOCKS ? p.ntiles : FBBEV_OCCL_MAX_BLOCKS;
+    p.staged = (stride_c == 1 && stride_d == C) ? 1 : 0;
+    p.row_runs = (p.staged && p.TD == D && stride_w == (long long)D * C) ? 1 : 0;
+    return p;
+}
+// the checks both entries share; 1 = nothing to do (B == 0)
+int occl_check(const void* logits, int B, int C, int H, int W, int D, const void* labels, const void* plane_weight, int empty_idx,
+               int flags, const void* a, const void* b) {
+    if (!logits || !labels || !a || !b || B < 0 || C <= 0 || H <= 0 || W <= 0 || D <= 0) return FBBEV_E_BADARG;
+    if (empty_idx < 0 || empty_idx >= C || ((flags & FBBEV_OCC_LOSS_FOCAL) && !plane_weight)) return FBBEV_E_BADARG;
+    if (B == 0) return 1;
+    if (C < 2 || C > 32) return FBBEV_E_UNSUPPORTED;
+    long long nvox = B;                                  // factor by factor: each is below 2^31, so no product leaves 64 bits
+    for (const int f : {H, W, D}) {
+        nvox *= f;
+        if (nvox >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" size_t fbbev_occ_loss_ws_bytes(int B, int C, int H, int W, int D) {
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || D <= 0) return 0;
+    const occl_plan p = occl_plan_of(0, 0, 0, B, C, H, W, D);
+    return align_up((size_t)p.blocks * (3 * C + 4) * sizeof(float), 16) + align_up((size_t)p.blocks * (C + 1) * sizeof(int32_t), 16);
+}
+
+extern "C" int fbbev_occ_loss_stats(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                                    long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels,
+                                    const float* class_weight, const float* plane_weight, int empty_idx, int flags, float gamma,
+                                    float alpha, float* stats_f, int32_t* stats_i, void* ws, size_t ws_bytes, fbbev_stream_t stream_) {
+    if (B > 0 && !ws) return FBBEV_E_BADARG;
+    const int chk = occl_check(logits, B, C, H, W, D, labels, plane_weight, empty_idx, flags, stats_f, stats_i);
+    if (chk < 0) return chk;
+    if (chk == 1) {
+        int e = fbbev_rt_memset_async(stats_f, 0, (size_t)(3 * C + 4) * sizeof(float), (fbbev_rt_stream)stream_);
+        if (!e) e = fbbev_rt_memset_async(stats_i, 0, (size_t)(C + 1) * sizeof(int32_t), (fbbev_rt_stream)stream_);
+        return e;
+    }
+    if (ws_bytes < fbbev_occ_loss_ws_bytes(B, C, H, W, D) || !aligned16(ws)) return FBBEV_E_WORKSPACE;
+    const occl_plan p = occl_plan_of(stride_c, stride_w, stride_d, B, C, H, W, D);
+    float* part_f = static_cast<float*>(ws);
+    int* part_i = reinterpret_cast<int*>(static_cast<char*>(ws) + align_up((size_t)p.blocks * (3 * C + 4) * sizeof(float), 16));
+    const size_t lds = ((size_t)FBBEV_OCCL_THREADS * C + 2 * FBBEV_OCCL_THREADS + C) * 4;
+    const int focal = flags & FBBEV_OCC_LOSS_FOCAL;
+#define FBBEV_OCCL_LAUNCH(S)                                                                                                              \
+    FBBEV_LAUNCH((k_occ_loss_stats<S>), p.blocks, FBBEV_OCCL_THREADS, lds, (fbbev_rt_stream)stream_, logits, stride_b, stride_c, stride_h, \
+                 stride_w, stride_d, C, H, W, D, p.T, p.TD, p.nth, p.ntw, p.ntd, (int)p.ntiles, p.row_runs, labels, class_weight,         \
+                 plane_weight, empty_idx, focal, gamma, alpha, part_f, part_i)
+    if (p.staged) FBBEV_OCCL_LAUNCH(true);
+    else FBBEV_OCCL_LAUNCH(false);
+#undef FBBEV_OCCL_LAUNCH
+    FBBEV_CHECK_LAUNCH();
+    const size_t lds_reduce = (size_t)FBBEV_OCCL_REDUCE_CHUNK * (4 * C + 5) * 4;          // a chunk of float and int records
+    FBBEV_LAUNCH(k_occ_loss_reduce, 1, FBBEV_OCCL_THREADS, lds_reduce, (fbbev_rt_stream)stream_, part_f, part_i, (int)p.blocks, C,
+                 stats_f, stats_i);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_occ_loss_grad(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                                   long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels,
+                                   const float* class_weight, const float* plane_weight, int empty_idx, int flags, float gamma,
+                                   float alpha, const float* grad_stats, float* grad_logits, fbbev_stream_t stream_) {
+    const int chk = occl_check(logits, B, C, H, W, D, labels, plane_weight, empty_idx, flags, grad_stats, grad_logits);
+    if (chk < 0) return chk;
+    if (chk == 1) return 0;
+    const occl_plan p = occl_plan_of(stride_c, stride_w, stride_d, B, C, H, W, D);
+    const size_t lds = ((size_t)FBBEV_OCCL_THREADS * C + 4 * C + 4) * 4;
+    const int focal = flags & FBBEV_OCC_LOSS_FOCAL;
+    const long long blocks = p.ntiles < 2048 ? p.ntiles : 2048;     // nothing is added across workgroups here: any grid gives the same bits
+#define FBBEV_OCCL_LAUNCH(S)                                                                                                           \
+    FBBEV_LAUNCH((k_occ_loss_grad<S>), blocks, FBBEV_OCCL_THREADS, lds, (fbbev_rt_stream)stream_, logits, stride_b, stride_c, stride_h, \
+                 stride_w, stride_d, C, H, W, D, p.T, p.TD, p.nth, p.ntw, p.ntd, (int)p.ntiles, p.row_runs, labels, class_weight,      \
+                 plane_weight, empty_idx, focal, gamma, alpha, grad_stats, grad_logits)
+    if (p.staged) FBBEV_OCCL_LAUNCH(true);
+    else FBBEV_OCCL_LAUNCH(false);
+#undef FBBEV_OCCL_LAUNCH
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

@@ -174,3 +174,73 @@ class CustomFocalLoss(torch.nn.Module):
         loss = loss.sum(-1) * self.c.to(loss.device)[None, :, :, None]                  # radial weight (:250-252)
         visf = vis.to(loss.dtype)
         return self.loss_weight * (loss * visf).sum() / visf.sum()                      # .sum(-1).mean() over visible
+
+
+# ---------------------------------------------------------------------------------------------------- fused voxel losses
+def losses_from_stats(stats_f, stats_i, class_weights, empty_idx, focal, loss_weight=1.0):
+    """(CE_ssc_loss or CustomFocalLoss, sem_scal_loss, geo_scal_loss) from the sums fbbev_occ_loss_stats leaves (include/fbbev.h):
+    stats_f (3C + 4,) = P, N, Q, G, CLS, 0, 0 and stats_i (C + 1,) = cnt, n_valid.  The formulas above on (C,) vectors: pure torch
+    on any device, no host branch, differentiable in stats_f.  Q and G arrive as sums of their own, not as n_valid - P - cnt + N and
+    n_valid - P[e], which cancel when almost every voxel is free."""
+    C = stats_i.shape[0] - 1
+    P, N, Q = stats_f[:C], stats_f[C:2 * C], stats_f[2 * C:3 * C]
+    G, CLS = stats_f[3 * C], stats_f[3 * C + 1]
+    cnt, n_valid = stats_i[:C].to(stats_f.dtype), stats_i[C].to(stats_f.dtype)
+    eps = 1e-5
+    if focal:
+        cls = loss_weight * CLS / n_valid                                               # CustomFocalLoss.forward
+    else:
+        cls = CLS / (class_weights.to(stats_f.dtype) * cnt).sum()                       # F.cross_entropy(weight, 'mean')
+    e = empty_idx
+    begin = 1 if C == 19 else 0                                                         # sem_scal_loss's classes
+    s = slice(begin, C - 1)
+    K = C - 1 - begin
+    not_t = n_valid - cnt[s]
+    # all 3 K + 3 ratios through ONE _bce_to_one (a dozen tiny kernels per call, forward and backward): sem_scal's precision, recall
+    # and specificity per class, then geo_scal's three
+    ratios = torch.cat([N[s] / (P[s] + eps), N[s] / (cnt[s] + eps), Q[s] / (not_t + eps),
+                        torch.stack([Q[e] / (G + eps), Q[e] / (n_valid - cnt[e] + eps), N[e] / (cnt[e] + eps)])])
+    b = _bce_to_one(ratios)
+    geo = b[3 * K:].sum()                                                               # geo_scal_loss
+    zero = torch.zeros_like(cnt[s])
+    per_class = torch.where(P[s] > 0, b[:K], zero) + b[K:2 * K] + torch.where(not_t > 0, b[2 * K:3 * K], zero)
+    present = cnt[s] > 0
+    sem = torch.where(present, per_class, zero).sum() / present.to(stats_f.dtype).sum()
+    return cls, sem, geo
+
+
+class _VoxelStats(torch.autograd.Function):
+    """the two kernels of fb_bev_amd/csrc/occ_loss_kernels.h: logits, labels -> (stats_f, stats_i); backward: grad of stats_f ->
+    grad of the logits.  Only the logits and the labels are kept for the backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, class_weights, plane_weight, empty_idx, focal, gamma, alpha):
+        from . import _capi
+        stats_f, stats_i = _capi.occ_loss_stats(logits, labels, class_weights, plane_weight, empty_idx, focal, gamma, alpha)
+        ctx.save_for_backward(logits, labels)
+        ctx.weights = (class_weights, plane_weight)
+        ctx.args = (empty_idx, focal, gamma, alpha)
+        ctx.mark_non_differentiable(stats_i)
+        return stats_f, stats_i
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats, _):
+        from . import _capi
+        logits, labels = ctx.saved_tensors
+        grad = _capi.occ_loss_grad(logits, labels, grad_stats.contiguous(), *ctx.weights, *ctx.args)
+        return grad, None, None, None, None, None, None, None
+
+
+def voxel_losses_fused(logits, target, class_weights, plane_weight=None, empty_idx=0, focal=False, gamma=2.0, alpha=0.25,
+                       loss_weight=1.0):
+    """-> (ce or focal, sem_scal, geo_scal) of logits (B, C, H, W, D) f32 in any strides and target (B, H, W, D) (255 = ignored),
+    equal to CE_ssc_loss / CustomFocalLoss, sem_scal_loss and geo_scal_loss of nan_to_num(logits, 0, 0, 0) up to fp32 summation
+    order.  One pass over the logits forward, one backward; no full-size temporary is kept."""
+    labels = target.to(torch.uint8).contiguous()
+    cw = None if class_weights is None else class_weights.to(device=logits.device, dtype=torch.float32).contiguous()
+    pw = None if plane_weight is None else plane_weight.to(device=logits.device, dtype=torch.float32).contiguous()
+    stats_f, stats_i = _VoxelStats.apply(logits.float(), labels, cw, pw, int(empty_idx), bool(focal), float(gamma), float(alpha))
+    if cw is None:
+        cw = torch.ones(logits.shape[1], device=logits.device)
+    return losses_from_stats(stats_f, stats_i, cw, int(empty_idx), bool(focal), loss_weight)

@@ -1169,6 +1169,43 @@ int fbbev_occ_classes(const float* logits, long long stride_b, long long stride_
                       long long stride_d, int B, int C, int c0, int H, int W, int D, uint8_t* classes, const uint8_t* gt,
                       const uint8_t* mask, const uint8_t* column_mask, int32_t* hist, fbbev_stream_t stream);
 
+/* Voxel losses of the occupancy head from ONE pass over the logits (training).  With x = nan_to_num(logits, 0, 0, 0), p = softmax(x)
+ * over the classes, t = the voxel's label, m = (t != 255), e = empty_idx, w = class_weight (NULL: ones), r = plane_weight:
+ *   P[c] = sum m p[c]   N[c] = sum m [t == c] p[c]   Q[c] = sum m [t != c] (1 - p[c])   G = sum m (1 - p[e])
+ *   CLS = sum m w[t] (-log p[t])                               cross entropy            (replaces semkitti.py:167-182)
+ *   CLS = sum m r[h, w] sum_c w[c] focal(x[c], [t == c])       FBBEV_OCC_LOSS_FOCAL     (replaces focal_loss.py:13-54,191-286)
+ *   cnt[c] = sum m [t == c]   n_valid = sum m
+ * which are all that sem_scal_loss and geo_scal_loss (semkitti.py:78-182) need of the tensor as well.
+ *   logits (B, C, H, W, D) f32 with the given strides in elements (any pattern; fast for channels-last -- stride_c == 1,
+ *   stride_d == C -- and for class planes, stride_d == 1).  labels (B, H, W, D) bytes, contiguous: 0..C-1, or 255 = not counted
+ *   (the results for a label in C..254 are unspecified: the reference raises on one).
+ *   plane_weight (H, W) f32, needed with FBBEV_OCC_LOSS_FOCAL only.  gamma, alpha: the focal loss's.
+ *   stats_f (3C + 4 f32) = P, N, Q, G, CLS, 0, 0;  stats_i (C + 1 i32) = cnt, n_valid.  Both are written, not added to.
+ *   ws: fbbev_occ_loss_ws_bytes(B, C, H, W, D) bytes, 16-byte aligned; its contents on entry do not matter.
+ * No atomics: every workgroup leaves one record in ws and one workgroup adds the records in ascending order (floats in double, rounded
+ * once), with a grid that depends on the shape alone, so the results are bit-identical from run to run and from device to device.
+ * FBBEV_E_BADARG: a null logits / labels / stats_f / stats_i / ws (ws with B > 0), B < 0, a non-positive C / H / W / D, empty_idx
+ * outside 0..C-1, FBBEV_OCC_LOSS_FOCAL without plane_weight.  B == 0: 0, no launch, stats_f and stats_i zeroed.
+ * FBBEV_E_UNSUPPORTED: C outside 2..32, or B*H*W*D >= 2^31.  FBBEV_E_WORKSPACE: ws too small or not 16-byte aligned. */
+#define FBBEV_OCC_LOSS_FOCAL 1
+size_t fbbev_occ_loss_ws_bytes(int B, int C, int H, int W, int D);
+int fbbev_occ_loss_stats(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                         long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, const float* class_weight,
+                         const float* plane_weight, int empty_idx, int flags, float gamma, float alpha, float* stats_f,
+                         int32_t* stats_i, void* ws, size_t ws_bytes, fbbev_stream_t stream);
+
+/* Backward of fbbev_occ_loss_stats: grad_logits from grad_stats, the gradient with respect to stats_f (3C + 4 f32 in DEVICE memory,
+ * same layout; the two spare slots are ignored).  With g_c = m (gP[c] + [t == c] gN[c] - [t != c] gQ[c]) - [c == e] m gG:
+ *   grad x[j] = p[j] (g_j - sum_c g_c p[c]) + gCLS m w[t] (p[j] - [j == t])                      cross entropy
+ *                                           + gCLS m r[h, w] w[j] focal'(x[j], [t == j])         FBBEV_OCC_LOSS_FOCAL
+ * and 0 where logits[j] was NaN or infinite (nan_to_num's backward; replaces the autograd passes of focal_loss.py:13-54,191-286 and
+ * semkitti.py:78-182).  grad_logits has the strides of logits; EVERY element of the (B, C, H, W, D) view is written, zeros for voxels
+ * labelled 255 included, and nothing else.  The other arguments and the error codes are fbbev_occ_loss_stats' (no workspace). */
+int fbbev_occ_loss_grad(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                        long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, const float* class_weight,
+                        const float* plane_weight, int empty_idx, int flags, float gamma, float alpha, const float* grad_stats,
+                        float* grad_logits, fbbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
