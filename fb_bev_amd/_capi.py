@@ -181,6 +181,9 @@ SIGNATURES = {
                              [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     'fbbev_occ_loss_grad': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 3 + [c_int, c_int, c_float, c_float] +
                             [c_void_p, c_void_p, c_void_p]),
+    'fbbev_occ_lovasz_ws_bytes': (c_size_t, [c_int] * 5),
+    'fbbev_occ_lovasz_fwd': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    'fbbev_occ_lovasz_grad': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 5),
 }
 
 _lib = None
@@ -1994,4 +1997,64 @@ def occ_loss_grad(logits, labels, grad_stats, class_weight=None, plane_weight=No
     with _on(logits):
         _check(lib().fbbev_occ_loss_grad(*args, _dev(grad_stats, F32, 'grad_stats'), _dev(out, F32, 'out', contiguous=False), _stream()),
                'fbbev_occ_loss_grad')
+    return out
+
+
+def _occ_lovasz_args(logits, labels):
+    """the arguments fbbev_occ_lovasz_fwd and fbbev_occ_lovasz_grad share, checked"""
+    require_gpu(logits, 'logits')
+    if logits.dtype != F32 or logits.dim() != 5:
+        raise FbbevError(f'logits must be a 5-D float32 tensor (B, C, H, W, D), got {logits.dtype} {tuple(logits.shape)}')
+    B, C, H, W, D = logits.shape
+    if tuple(labels.shape) != (B, H, W, D):
+        raise FbbevError(f'labels must be {(B, H, W, D)}, got {tuple(labels.shape)}')
+    return (c_void_p(logits.data_ptr()), *[int(s) for s in logits.stride()], B, C, H, W, D, _dev(labels, U8, 'labels'))
+
+
+def occ_lovasz_fwd(logits, labels, loss_c=None, fg_count=None, coef=None, errors_out=None, ws=None):
+    """fbbev_occ_lovasz_fwd: the Lovasz-softmax term per class from logits (B, C, H, W, D) f32 with ANY strides (no copy is made) and
+    labels (B, H, W, D) uint8 (255 = takes no rank).  -> loss_c (C,) f32, fg_count (C + 1,) int32 = G, n_valid, coef (C, B, H, W, D) f32
+    = the signed Lovasz coefficients occ_lovasz_grad reads; see include/fbbev.h.  errors_out (C, B, H, W, D) f32, where given,
+    receives the errors the device sorted.  Bit-identical from run to run; nothing waits for the host."""
+    args = _occ_lovasz_args(logits, labels)
+    B, C, H, W, D = logits.shape
+    dev = logits.device
+    if loss_c is None:
+        loss_c = torch.empty(C, dtype=F32, device=dev)
+    if fg_count is None:
+        fg_count = torch.empty(C + 1, dtype=I32, device=dev)
+    if coef is None:
+        coef = torch.empty((C, B, H, W, D), dtype=F32, device=dev)
+    if tuple(loss_c.shape) != (C,) or tuple(fg_count.shape) != (C + 1,):
+        raise FbbevError(f'loss_c / fg_count must be {(C,)} / {(C + 1,)}, got {tuple(loss_c.shape)} / {tuple(fg_count.shape)}')
+    for t, name in ((coef, 'coef'), (errors_out, 'errors_out')):
+        if t is not None and tuple(t.shape) != (C, B, H, W, D):
+            raise FbbevError(f'{name} must be {(C, B, H, W, D)}, got {tuple(t.shape)}')
+    need = lib().fbbev_occ_lovasz_ws_bytes(B, C, H, W, D)
+    if ws is None:
+        ws = torch.empty(max(need, 16), dtype=U8, device=dev)
+    with _on(logits):
+        _check(lib().fbbev_occ_lovasz_fwd(*args, _dev(loss_c, F32, 'loss_c'), _dev(fg_count, I32, 'fg_count'), _dev(coef, F32, 'coef'),
+                                          None if errors_out is None else _dev(errors_out, F32, 'errors_out'), _dev(ws, U8, 'ws'),
+                                          ws.numel(), _stream()), 'fbbev_occ_lovasz_fwd')
+    return loss_c, fg_count, coef
+
+
+def occ_lovasz_grad(logits, labels, coef, scale, out=None):
+    """fbbev_occ_lovasz_grad: the gradient of the logits from coef (C, B, H, W, D) f32 of occ_lovasz_fwd and scale, a one-element f32
+    tensor on the device (upstream gradient / number of present classes).  `out` has the strides of logits (default: allocated so);
+    every element of it is written."""
+    args = _occ_lovasz_args(logits, labels)
+    B, C, H, W, D = logits.shape
+    if tuple(coef.shape) != (C, B, H, W, D):
+        raise FbbevError(f'coef must be {(C, B, H, W, D)}, got {tuple(coef.shape)}')
+    if scale.numel() != 1:
+        raise FbbevError(f'scale must hold one element, got {tuple(scale.shape)}')
+    if out is None:
+        out = torch.empty_strided(logits.shape, logits.stride(), dtype=F32, device=logits.device)
+    elif out.shape != logits.shape or out.stride() != logits.stride():
+        raise FbbevError(f'out must have the shape and strides of logits, got {tuple(out.shape)} {out.stride()}')
+    with _on(logits):
+        _check(lib().fbbev_occ_lovasz_grad(*args, _dev(coef, F32, 'coef'), _dev(scale, F32, 'scale'),
+                                           _dev(out, F32, 'out', contiguous=False), _stream()), 'fbbev_occ_lovasz_grad')
     return out

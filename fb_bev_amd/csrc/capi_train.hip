@@ -6,6 +6,7 @@
 #include "capi_common.h"
 #include "wgrad_kernels.h"
 #include "rows_wgrad_f32_kernels.h"
+#include "occ_lovasz_kernels.h"
 #include "../../include/fbbev.h"
 
 // ------------------------------------------------------------------------------ weight / bias gradient of a row-wise linear layer
@@ -270,4 +271,158 @@ extern "C" int fbbev_softmax_groups(const float* x, long long n_groups, int grou
 extern "C" int fbbev_softmax_groups_bwd(const float* y, const float* grad_y, long long n_groups, int group, float* grad_x,
                                         fbbev_stream_t stream_) {
     return softmax_groups_launch<true>(y, grad_y, n_groups, group, grad_x, stream_);
+}
+
+// ------------------------------------------------------------------------------ Lovasz-softmax occupancy loss: segmented sort + scan
+namespace {
+struct occlv_plan {
+    int T, TD, nth, ntw, ntd, staged, row_runs;          // the tile walk of fbbev_occ_loss_stats
+    long long ntiles, blocks;
+    int nvox, cps, group;                                // voxels, sort chunks per class, classes sorted together
+    size_t off_b, off_matrix, off_tot, off_cstat, off_sfg, off_part, total;
+};
+// 1 = nothing to do (B == 0)
+int occlv_check(const void* logits, int B, int C, int H, int W, int D, const void* labels) {
+    if (!logits || !labels || B < 0 || C <= 0 || H <= 0 || W <= 0 || D <= 0) return FBBEV_E_BADARG;
+    if (B == 0) return 1;
+    if (C < 2 || C > 32) return FBBEV_E_UNSUPPORTED;
+    long long nvox = B;                                  // factor by factor: each is below 2^31, so no product leaves 64 bits
+    for (const int f : {H, W, D}) {
+        nvox *= f;
+        if (nvox >= (1ll << 26)) return FBBEV_E_UNSUPPORTED;
+    }
+    return 0;
+}
+// B H W D < 2^26 has been checked
+occlv_plan occlv_plan_of(long long stride_c, long long stride_w, long long stride_d, int B, int C, int H, int W, int D) {
+    occlv_plan p;
+    p.TD = D < 64 ? D : 64;
+    p.T = p.TD >= 16 ? 8 : 16;
+    p.nth = (H + p.T - 1) / p.T; p.ntw = (W + p.T - 1) / p.T; p.ntd = (D + p.TD - 1) / p.TD;
+    p.ntiles = (long long)B * p.nth * p.ntw * p.ntd;
+    p.blocks = p.ntiles < FBBEV_OCCLV_MAX_BLOCKS ? p.ntiles : FBBEV_OCCLV_MAX_BLOCKS;
+    p.staged = (stride_c == 1 && stride_d == C) ? 1 : 0;
+    p.row_runs = (p.staged && p.TD == D && stride_w == (long long)D * C) ? 1 : 0;
+    p.nvox = B * H * W * D;
+    p.cps = (p.nvox + FBBEV_OCCLV_TILE - 1) / FBBEV_OCCLV_TILE;
+    // classes per group: two pair buffers of 8 bytes per (class, voxel) stay below 2 x 128 MiB (all 19 classes at once at the shipped
+    // shape with B = 1, six at a time at B = 4, one at a time from B = 14); the emulator's tests shrink it to walk several groups at
+    // their sizes
+    long long pairs = FBBEV_KNOB_EMU_INT("FBBEV_OCC_LOVASZ_GROUP_PAIRS", 1 << 24);
+    if (pairs < 1) pairs = 1;
+    long long group = pairs / p.nvox;
+    p.group = (int)(group < 1 ? 1 : (group > C ? C : group));
+    const size_t g = (size_t)p.group, seg = align_up(g * p.nvox * sizeof(uint2), 16);
+    p.off_b = seg;
+    p.off_matrix = 2 * seg;
+    p.off_tot = p.off_matrix + align_up(g * p.cps * FBBEV_OCCLV_MAX_NB * sizeof(int), 16);
+    p.off_cstat = p.off_tot + align_up(g * FBBEV_OCCLV_MAX_NB * sizeof(int), 16);
+    p.off_sfg = p.off_cstat + align_up(g * p.cps * sizeof(int2), 16);
+    p.off_part = p.off_sfg + align_up(g * p.cps * sizeof(int), 16);
+    p.total = p.off_part + align_up(g * p.cps * sizeof(double), 16);
+    return p;
+}
+}  // namespace
+
+extern "C" size_t fbbev_occ_lovasz_ws_bytes(int B, int C, int H, int W, int D) {
+    int dummy = 0;
+    if (occlv_check(&dummy, B, C, H, W, D, &dummy) != 0) return 0;
+    return occlv_plan_of(0, 0, 0, B, C, H, W, D).total;
+}
+
+extern "C" int fbbev_occ_lovasz_fwd(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                                    long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, float* loss_c,
+                                    int32_t* fg_count, float* coef, float* errors_out, void* ws, size_t ws_bytes,
+                                    fbbev_stream_t stream_) {
+    if (!loss_c || !fg_count || (B > 0 && (!coef || !ws))) return FBBEV_E_BADARG;
+    const int chk = occlv_check(logits, B, C, H, W, D, labels);
+    if (chk < 0) return chk;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    if (chk == 1) {
+        int e = fbbev_rt_memset_async(loss_c, 0, (size_t)C * sizeof(float), stream);
+        if (!e) e = fbbev_rt_memset_async(fg_count, 0, (size_t)(C + 1) * sizeof(int32_t), stream);
+        return e;
+    }
+    const occlv_plan p = occlv_plan_of(stride_c, stride_w, stride_d, B, C, H, W, D);
+    if (ws_bytes < p.total || !aligned16(ws)) return FBBEV_E_WORKSPACE;
+    // digit width of the radix passes: 10 bits = 3 passes, 8 bits = 4 passes over the 30 key bits (DESIGN 3.9 has the measurement)
+    FBBEV_KNOB_ONCE(int, env_rb, fbbev_env_int("FBBEV_OCC_LOVASZ_DIGIT_BITS", 10));
+    const int rb = env_rb == 8 ? 8 : 10, nb = 1 << rb, passes = rb == 8 ? 4 : 3;
+    char* w8 = static_cast<char*>(ws);
+    uint2* buf_a = reinterpret_cast<uint2*>(w8);
+    uint2* buf_b = reinterpret_cast<uint2*>(w8 + p.off_b);
+    unsigned int* keys0 = reinterpret_cast<unsigned int*>(buf_b);        // read by the first pass only, which writes buf_a
+    int* matrix = reinterpret_cast<int*>(w8 + p.off_matrix);
+    int* tot = reinterpret_cast<int*>(w8 + p.off_tot);
+    int2* cstat = reinterpret_cast<int2*>(w8 + p.off_cstat);
+    int* sfg = reinterpret_cast<int*>(w8 + p.off_sfg);
+    double* part = reinterpret_cast<double*>(w8 + p.off_part);
+    const size_t lds = (size_t)FBBEV_OCCL_THREADS * C * 4;
+    for (int c0 = 0; c0 < C; c0 += p.group) {
+        const int g = C - c0 < p.group ? C - c0 : p.group;
+#define FBBEV_OCCLV_KEYS(S)                                                                                                             \
+    FBBEV_LAUNCH((k_occ_lovasz_keys<S>), p.blocks, FBBEV_OCCL_THREADS, lds, stream, logits, stride_b, stride_c, stride_h, stride_w,    \
+                 stride_d, C, H, W, D, p.T, p.TD, p.nth, p.ntw, p.ntd, (int)p.ntiles, p.row_runs, labels, c0, g, p.nvox, keys0, coef,  \
+                 errors_out)
+        if (p.staged) FBBEV_OCCLV_KEYS(true);
+        else FBBEV_OCCLV_KEYS(false);
+#undef FBBEV_OCCLV_KEYS
+        FBBEV_CHECK_LAUNCH();
+        const long long chunks = (long long)g * p.cps;
+        const uint2* src = nullptr;
+        uint2* dst = buf_a;
+        for (int pass = 0; pass < passes; ++pass) {
+            if (pass == 0) {
+                FBBEV_LAUNCH(k_occ_lovasz_hist<true>, chunks, FBBEV_OCCLV_NT, 0, stream, (const unsigned int*)keys0, src, pass, rb, p.nvox,
+                             p.cps, C, c0, (const int*)fg_count, matrix, cstat);
+                FBBEV_CHECK_LAUNCH();
+                FBBEV_LAUNCH(k_occ_lovasz_colscan<true>, g * (nb >> 8), 256, 0, stream, rb, p.cps, C, c0, fg_count, matrix, tot,
+                             (const int2*)cstat);
+                FBBEV_CHECK_LAUNCH();
+                FBBEV_LAUNCH(k_occ_lovasz_scatter<true>, chunks, FBBEV_OCCLV_NT, 0, stream, (const unsigned int*)keys0, src, pass, rb,
+                             p.nvox, p.cps, C, c0, (const int*)fg_count, (const int*)matrix, (const int*)tot, dst);
+                FBBEV_CHECK_LAUNCH();
+            } else {
+                FBBEV_LAUNCH(k_occ_lovasz_hist<false>, chunks, FBBEV_OCCLV_NT, 0, stream, (const unsigned int*)nullptr, src, pass, rb,
+                             p.nvox, p.cps, C, c0, (const int*)fg_count, matrix, cstat);
+                FBBEV_CHECK_LAUNCH();
+                FBBEV_LAUNCH(k_occ_lovasz_colscan<false>, g * (nb >> 8), 256, 0, stream, rb, p.cps, C, c0, fg_count, matrix, tot,
+                             (const int2*)cstat);
+                FBBEV_CHECK_LAUNCH();
+                FBBEV_LAUNCH(k_occ_lovasz_scatter<false>, chunks, FBBEV_OCCLV_NT, 0, stream, (const unsigned int*)nullptr, src, pass, rb,
+                             p.nvox, p.cps, C, c0, (const int*)fg_count, (const int*)matrix, (const int*)tot, dst);
+                FBBEV_CHECK_LAUNCH();
+            }
+            src = dst;
+            dst = dst == buf_a ? buf_b : buf_a;
+        }
+        FBBEV_LAUNCH(k_occ_lovasz_fgsum, chunks, FBBEV_OCCLV_NT, 0, stream, src, p.nvox, p.cps, C, c0, (const int*)fg_count, sfg);
+        FBBEV_CHECK_LAUNCH();
+        FBBEV_LAUNCH(k_occ_lovasz_coef, chunks, FBBEV_OCCLV_NT, 0, stream, src, p.nvox, p.cps, C, c0, (const int*)fg_count,
+                     (const int*)sfg, coef, part);
+        FBBEV_CHECK_LAUNCH();
+        FBBEV_LAUNCH(k_occ_lovasz_loss, g, FBBEV_OCCLV_NT, 0, stream, p.cps, C, c0, (const int*)fg_count, (const double*)part, loss_c);
+        FBBEV_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+extern "C" int fbbev_occ_lovasz_grad(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                                     long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, const float* coef,
+                                     const float* scale, float* grad_logits, fbbev_stream_t stream_) {
+    if (!scale || !grad_logits || (B > 0 && !coef)) return FBBEV_E_BADARG;
+    const int chk = occlv_check(logits, B, C, H, W, D, labels);
+    if (chk < 0) return chk;
+    if (chk == 1) return 0;
+    const occlv_plan p = occlv_plan_of(stride_c, stride_w, stride_d, B, C, H, W, D);
+    const size_t lds = (size_t)2 * FBBEV_OCCL_THREADS * C * 4;            // <= 64 KiB at C = 32
+#define FBBEV_OCCLV_GRAD(S)                                                                                                             \
+    FBBEV_LAUNCH((k_occ_lovasz_grad<S>), p.blocks, FBBEV_OCCL_THREADS, lds, (fbbev_rt_stream)stream_, logits, stride_b, stride_c,       \
+                 stride_h, stride_w, stride_d, C, H, W, D, p.T, p.TD, p.nth, p.ntw, p.ntd, (int)p.ntiles, p.row_runs, labels, coef,    \
+                 p.nvox, scale, grad_logits)
+    if (p.staged) FBBEV_OCCLV_GRAD(true);
+    else FBBEV_OCCLV_GRAD(false);
+#undef FBBEV_OCCLV_GRAD
+    FBBEV_CHECK_LAUNCH();
+    return 0;
 }

@@ -79,6 +79,8 @@ class FBOCC(nn.Module):
         frame of a stream on (bit-identical results; the convolution stacks stay outside the graph);
         fused_occ_losses=True: the head's ce / focal, sem_scal and geo_scal losses from one pass over the logits, forward and
         backward (occ_loss.voxel_losses_fused; same values up to fp32 summation order; default off);
+        fused_lovasz=True: the head's Lovasz-softmax loss from a segmented radix sort on the logits, forward and backward
+        (occ_loss.lovasz_softmax_fused; no full-size softmax, error matrix or permutation is kept; default off);
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -119,6 +121,8 @@ class FBOCC(nn.Module):
         self.occupancy_head = _build(occupancy_head, **cp, compute_dtype=_dtype(ex.get('head_dtype')))
         if self.occupancy_head is not None and ex.get('fused_occ_losses') is not None:
             self.occupancy_head.fused_losses = bool(ex['fused_occ_losses'])
+        if self.occupancy_head is not None and ex.get('fused_lovasz') is not None:
+            self.occupancy_head.fused_lovasz = bool(ex['fused_lovasz'])
         # eval-mode image encoder / voxel encoder / head on the hand-written implicit-GEMM kernels (mfma_conv3d.py).
         # GPU-validated in round 2 (tests/test_gpu_conv3d.py) and measured against the vendor route on the shipped
         # config (profiles/r02_time_full.jsonl: S4 22.2 ms fp32-MFMA vs 41.1 ms vendor bf16), so exact-fp32 MFMA is

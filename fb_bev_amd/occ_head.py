@@ -32,9 +32,10 @@ class OccHead(nn.Module):
                  conv_cfg=dict(type='Conv3d', bias=False), norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
                  point_cloud_range=(-51.2, -51.2, -5.0, 51.2, 51.2, 3.0), final_occ_size=(256, 256, 20), empty_idx=0,
                  balance_cls_weight=True, train_cfg=None, test_cfg=None, with_cp=False, use_focal_loss=False,
-                 use_dice_loss=False, use_deblock=True, compute_dtype=torch.float32, fused_losses=False):
+                 use_dice_loss=False, use_deblock=True, compute_dtype=torch.float32, fused_losses=False, fused_lovasz=False):
         super().__init__()
         self.fused_losses = fused_losses          # ce / focal, sem_scal and geo_scal from one pass over the logits
+        self.fused_lovasz = fused_lovasz          # Lovasz-softmax from the segmented sort on the logits
         if use_dice_loss:
             raise NotImplementedError('DiceLoss (:114-116) is mmseg-external and unused by the fb_occ configs')
         in_channels = list(in_channels) if isinstance(in_channels, (list, tuple)) else [in_channels]
@@ -143,24 +144,30 @@ class OccHead(nn.Module):
             output_voxels, target_voxels, ignore_index=255)
         loss[f'loss_voxel_geo_scal_{tag}'] = self.loss_voxel_geo_scal_weight * L.geo_scal_loss(
             output_voxels, target_voxels, ignore_index=255, non_empty_idx=self.empty_idx)
-        loss[f'loss_voxel_lovasz_{tag}'] = self.loss_voxel_lovasz_weight * L.lovasz_softmax(
-            torch.softmax(output_voxels, dim=1), target_voxels, ignore=255)
+        loss[f'loss_voxel_lovasz_{tag}'] = self.loss_voxel_lovasz_weight * self._lovasz(output_voxels, target_voxels, True)
         return loss
+
+    def _lovasz(self, logits, target_voxels, cleaned):
+        """the Lovasz-softmax term: fused_lovasz sorts on the device from the logits themselves (the kernels clean them as :222-223
+        does), otherwise occ_loss.lovasz_softmax of a full-size softmax of the cleaned logits."""
+        if self.fused_lovasz:
+            return L.lovasz_softmax_fused(logits, target_voxels, ignore=255)
+        if not cleaned:
+            logits = torch.nan_to_num(logits.float(), nan=0.0, posinf=0.0, neginf=0.0)
+        return L.lovasz_softmax(torch.softmax(logits, dim=1), target_voxels.long(), ignore=255)
 
     def _loss_voxel_fused(self, output_voxels, target_voxels, tag):
         """loss_voxel with the three sum-shaped terms from occ_loss.voxel_losses_fused (the kernels clean the logits as :222-223
-        does); Lovasz needs a sort per class and stays on its own function.  Same keys, same weights."""
+        does); Lovasz needs a sort per class and has its own switch (fused_lovasz).  Same keys, same weights."""
         focal = self.focal_loss if self.use_focal_loss else None
         ce, sem, geo = L.voxel_losses_fused(
             output_voxels, target_voxels, self.class_weights, plane_weight=focal.c if focal is not None else None,
             empty_idx=self.empty_idx, focal=focal is not None, gamma=focal.gamma if focal is not None else 2.0,
             alpha=focal.alpha if focal is not None else 0.25, loss_weight=focal.loss_weight if focal is not None else 1.0)
-        clean = torch.nan_to_num(output_voxels.float(), nan=0.0, posinf=0.0, neginf=0.0)
         return {f'loss_voxel_ce_{tag}': self.loss_voxel_ce_weight * ce,
                 f'loss_voxel_sem_scal_{tag}': self.loss_voxel_sem_scal_weight * sem,
                 f'loss_voxel_geo_scal_{tag}': self.loss_voxel_geo_scal_weight * geo,
-                f'loss_voxel_lovasz_{tag}': self.loss_voxel_lovasz_weight * L.lovasz_softmax(
-                    torch.softmax(clean, dim=1), target_voxels.long(), ignore=255)}
+                f'loss_voxel_lovasz_{tag}': self.loss_voxel_lovasz_weight * self._lovasz(output_voxels, target_voxels, False)}
 
     def loss(self, output_voxels=None, output_coords_fine=None, output_voxels_fine=None, target_voxels=None,
              visible_mask=None, **kwargs):

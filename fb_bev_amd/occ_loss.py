@@ -244,3 +244,38 @@ def voxel_losses_fused(logits, target, class_weights, plane_weight=None, empty_i
     if cw is None:
         cw = torch.ones(logits.shape[1], device=logits.device)
     return losses_from_stats(stats_f, stats_i, cw, int(empty_idx), bool(focal), loss_weight)
+
+
+# ---------------------------------------------------------------------------------------------------- fused Lovasz-softmax
+class _Lovasz(torch.autograd.Function):
+    """the kernels of fb_bev_amd/csrc/occ_lovasz_kernels.h: logits, labels -> the mean of the per-class Lovasz terms over the present
+    classes; backward: one pass over the logits with the coefficients the forward left.  The logits, the labels and `coef`
+    (C, B, H, W, D) are kept for the backward; the reference takes the coefficients as constants (lovasz_softmax.py:203)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        from . import _capi
+        loss_c, fg_count, coef = _capi.occ_lovasz_fwd(logits, labels)
+        present = fg_count[:-1] > 0
+        n_present = present.to(loss_c.dtype).sum().clamp(min=1)
+        ctx.save_for_backward(logits, labels, coef, n_present)
+        return torch.where(present, loss_c, torch.zeros_like(loss_c)).sum() / n_present
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _capi
+        logits, labels, coef, n_present = ctx.saved_tensors
+        scale = (grad_out.to(torch.float32) / n_present).reshape(1)                     # on the device: nothing waits for the host
+        return _capi.occ_lovasz_grad(logits, labels, coef, scale), None
+
+
+def lovasz_softmax_fused(logits, target, ignore=255):
+    """lovasz_softmax(softmax(nan_to_num(logits, 0, 0, 0), 1), target, ignore=255) of logits (B, C, H, W, D) f32 in any strides and target
+    (B, H, W, D), from the segmented sort of fb_bev_amd/csrc/occ_lovasz_kernels.h: no full-size softmax, error matrix or permutation is
+    kept.  Each class term is the closed form sum e_(k) g_k in double (more accurate than the fp32 1 - I / U differences); the
+    gradient takes the coefficients as constants, as the reference's autograd does."""
+    if ignore != 255:
+        raise ValueError('lovasz_softmax_fused ignores label 255 (the label a uint8 target reserves); use lovasz_softmax')
+    labels = target.to(torch.uint8).contiguous()
+    return _Lovasz.apply(logits.float(), labels)

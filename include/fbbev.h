@@ -1206,6 +1206,41 @@ int fbbev_occ_loss_grad(const float* logits, long long stride_b, long long strid
                         const float* plane_weight, int empty_idx, int flags, float gamma, float alpha, const float* grad_stats,
                         float* grad_logits, fbbev_stream_t stream);
 
+/* Lovasz-softmax term of the occupancy head (classes = 'present', per_image = False; replaces lovasz_softmax.py:20-33,157-229) without
+ * a full-size softmax or a sort that autograd keeps alive.  With x = nan_to_num(logits, 0, 0, 0), p = softmax(x), and for class c over
+ * the voxels with t != 255: f = [t == c], e = |f - p[c]| (fp32), G = sum f; sorted by e descending, ties by ascending voxel index in
+ * (b, h, w, d) order, position k = 1..n_valid, F_k = fg elements among the first k, U_k = G + k - F_k:
+ *   g_k = 1 / U_k (fg)   g_k = (G - F_k) / (U_k (U_k - 1)) (bg)      = the reference's Jaccard differences, in closed form
+ * each evaluated in double and rounded once to float (IEEE operations only).  A voxel labelled 255 takes no rank.
+ *   logits, the strides, labels: as for fbbev_occ_loss_stats.
+ *   loss_c (C f32): sum_k e_(k) g_k, products exact in double, added in a fixed order, rounded once; 0 for a class with G == 0.
+ *   fg_count (C + 1 i32): G[c], then n_valid.
+ *   coef (C * B*H*W*D f32): class planes in (b, h, w, d) order, h = -g for an fg element, +g for a bg element, 0 for a voxel labelled
+ *   255 and for a class with G == 0.  Every element is written.  It is what fbbev_occ_lovasz_grad reads.
+ *   errors_out (C * B*H*W*D f32 or NULL): the e the device sorted, 0 for a voxel labelled 255; NULL skips the store.
+ *   ws: fbbev_occ_lovasz_ws_bytes(B, C, H, W, D) bytes, 16-byte aligned; its contents on entry do not matter.  The classes are sorted
+ *   in groups, so that it stays below ~0.3 GB at every supported shape.
+ * No float atomics, n_valid and G are read from device words: the bits depend on the inputs alone and nothing waits for the host.
+ * FBBEV_E_BADARG: a null logits / labels / loss_c / fg_count, a null coef / ws with B > 0, B < 0, a non-positive C / H / W / D.
+ * B == 0: 0, no launch, loss_c and fg_count zeroed.  FBBEV_E_UNSUPPORTED: C outside 2..32, or B*H*W*D >= 2^26 (U (U - 1) must stay
+ * below 2^53).  FBBEV_E_WORKSPACE: ws too small or not 16-byte aligned. */
+size_t fbbev_occ_lovasz_ws_bytes(int B, int C, int H, int W, int D);
+int fbbev_occ_lovasz_fwd(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                         long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, float* loss_c,
+                         int32_t* fg_count, float* coef, float* errors_out, void* ws, size_t ws_bytes, fbbev_stream_t stream);
+
+/* Backward of the Lovasz-softmax term (replaces the autograd pass of lovasz_softmax.py:20-33,157-229, which takes the Jaccard
+ * differences as constants: Variable(lovasz_grad(...)), :203).  With h = coef of fbbev_occ_lovasz_fwd and s = *scale, a float in DEVICE
+ * memory (upstream gradient / number of present classes):
+ *   grad x[j] = s p[j] (h[j] - sum_c h[c] p[c])
+ * and 0 where logits[j] was NaN or infinite.  grad_logits has the strides of logits; EVERY element of the (B, C, H, W, D) view is
+ * written, zeros for voxels labelled 255 included, and nothing else.
+ * FBBEV_E_BADARG: a null logits / labels / scale / grad_logits, a null coef with B > 0, B < 0, a non-positive C / H / W / D.
+ * B == 0: 0 and no launch.  FBBEV_E_UNSUPPORTED: as for fbbev_occ_lovasz_fwd. */
+int fbbev_occ_lovasz_grad(const float* logits, long long stride_b, long long stride_c, long long stride_h, long long stride_w,
+                          long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, const float* coef,
+                          const float* scale, float* grad_logits, fbbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
