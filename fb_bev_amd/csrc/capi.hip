@@ -2692,7 +2692,122 @@ extern "C" int fbbev_bev_pool_v2_dense_bwd_z(const float* out_grad, long long og
                                zgrad, zscale);
 }
 
-// ------------------------------------------------------------------------------ temporal history alignment
+// ------------------------------------------------------------------------------ temporal history fusion
+// The streaming detector's per-frame step: warp the ring of past frames into the current ego frame, store the current frame, run the
+// two fused 1x1x1 convolutions over the T + 1 frames.  Every entry fills a history_ring per ring operand and one of the records
+// below from its positional C arguments; everything under it works on those records.
+//   entry                          ring layout               arithmetic        kernels                                        knobs that route it
+//   fbbev_history_flow             -                         fp32              k_history_flow                                 -
+//   fbbev_history_stream_prologue  -                         fp32              k_history_stream_prologue, k_history_flow      -
+//   fbbev_history_warp[_e]         planes (B, CH, Z, Y, X)   fp32 taps         k_history_warp<ET> | k_history_warp_lds<ET>    FBBEV_HISTORY_WARP=lds
+//   fbbev_history_warp_vm          voxel-major (B, T, N, C)  fp32 taps         k_history_warp_vm<ET, 2 (fp16: 4), 1>          FBBEV_HISTORY_VM_YB, _VM_TU, _WARP_LDS_PAD_KB
+//   fbbev_history_warp_vm_src      voxel-major               fp32 taps         k_history_warp_vm_src<ET, 2 (fp16: 4), 1>      FBBEV_HISTORY_VM_YB
+//   fbbev_history_frame_vm         planes -> one ring slot   -                 k_history_frame_vm<ET>                         -
+//   fbbev_history_conv[_e]         planes (B, T1 * C, N)     fp32 MFMA         k_history_weight_fragments + k_history_conv_t  -
+//                                                                              (C = Cout in {16, 80} and a workspace), else k_history_conv
+//   fbbev_history_conv_vm          voxel-major               fp32 MFMA         k_history_weight_fragments + k_history_conv_t  -
+//   fbbev_history_conv_bf16        either (voxel_major)      bf16 MFMA         k_history_weight_fragments_bf16 +              FBBEV_HISTORY_CONV_LDS_PAD_KB
+//                                                                              k_history_conv_bf16
+//   fbbev_history_fused_vm         voxel-major, 16-bit       bf16 MFMA         k_history_weight_fragments_bf16 +              -
+//                                                                              k_history_fused_bf16 (warp + both convolutions)
+//   fbbev_history_conv_bf16x3      voxel-major, 16-bit       split bf16 MFMA   k_history_weight_fragments_bf16x3 +            FBBEV_HX3_WAVES
+//                                                                              k_history_conv_bf16x3
+//   fbbev_history_fused_x3_vm      voxel-major, 16-bit       split bf16 MFMA   k_history_weight_fragments_bf16x3 +            -
+//                                                                              k_history_fused_x3 (warp + both convolutions)
+//   fbbev_history_step_x3_vm       voxel-major, 16-bit       split bf16 MFMA   warp_vm's and conv_bf16x3's kernels, band by   FBBEV_HISTORY_STEP_WAVES, _STEP_PRIORITY,
+//                                                                              band on two streams                            and warp_vm's three
+
+// A ring operand: B samples `stride` elements apart, each `frames` frames of N voxels x C channels -- voxel-major rows [N][C] or
+// planes [C][N]; the rule below is the same for both.
+struct history_ring {
+    const void* p;
+    long long stride;                                       // as the caller passed it (0 = dense) until history_ring_operand resolves it
+    int frames, C;
+    long long N;
+    int et;                                                 // FBBEV_ELEM_*: 0 fp32, 1 bf16, 2 fp16
+};
+// The rule for a ring operand: a batch stride of 0 means dense (and becomes that), one below frames * frame is FBBEV_E_BADARG;
+// rows read VE elements (16 bytes) at a time -- VE = 0: planes, no row accesses -- off a 16-byte boundary or a stride that is no
+// multiple of VE are FBBEV_E_UNSUPPORTED; so is, where the kernels form 32-bit byte offsets inside a frame (limit32), a frame past
+// them.  Two rings side by side go through row_worse: either one's BADARG comes first.
+static inline int history_ring_operand(history_ring& r, int VE, bool limit32) {
+    const long long frame = r.N * r.C;
+    if (r.stride == 0) r.stride = r.frames * frame;
+    if (r.stride < r.frames * frame) return FBBEV_E_BADARG;
+    if (VE && (r.stride % VE != 0 || !aligned16(r.p))) return FBBEV_E_UNSUPPORTED;
+    if (limit32 && frame * (r.et == 0 ? 4 : 2) >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;
+    return 0;
+}
+static inline bool history_et_ok(int et) { return et >= 0 && et <= 2; }
+
+// The two convolutions over the frames of `feats`: out (B, Cout, N) = relu(bias2 + sum_t w2_t . relu(w1 . x_t + bias1_t))
+struct history_conv_args {
+    history_ring feats;                                     // frames = T1
+    const float* w1; const float* bias1; const float* w2; const float* bias2;
+    int B, Cout;
+    float* out;
+    void* ws; size_t ws_bytes;
+    fbbev_rt_stream stream;
+};
+// A warp: the frames of `src` sampled at rt_flow's coordinates into `dst`
+struct history_warp_args {
+    history_ring src, dst;
+    const float* rt_flow;
+    int B, Z, Y, X;
+    fbbev_rt_stream stream;
+};
+// A whole step: the warp of `history` into the slots 1.. of conv.feats (the next ring, whose slot 0 holds the current frame), then
+// the convolutions over that ring
+struct history_step_args {
+    history_ring history;
+    history_conv_args conv;
+    const float* rt_flow;
+    int Z, Y, X;
+};
+
+// The checks the entries share.  Their ORDER inside an entry is part of the ABI (it decides the code where two defects coincide),
+// so every entry strings them together itself.
+static inline bool history_conv_dims_ok(const history_conv_args& c) {
+    return c.B >= 0 && c.feats.frames > 0 && c.feats.C > 0 && c.Cout > 0 && c.feats.N >= 0 && history_et_ok(c.feats.et);
+}
+static inline bool history_conv_empty(const history_conv_args& c) { return c.B == 0 || c.feats.N == 0; }
+static inline bool history_conv_present(const history_conv_args& c) { return c.feats.p && c.w1 && c.bias1 && c.w2 && c.bias2 && c.out; }
+// the MFMA kernels with register-resident weights are built for these two channel counts
+static inline bool history_conv_square(const history_conv_args& c) { return c.feats.C == c.Cout && (c.Cout == 80 || c.Cout == 16); }
+// (no element type here: the step entries make it a matter of FBBEV_E_UNSUPPORTED)
+static inline bool history_step_dims_ok(const history_step_args& s) {
+    return s.conv.B >= 0 && s.history.frames > 0 && s.history.C > 0 && s.conv.Cout > 0 && s.Z > 0 && s.Y > 0 && s.X > 0;
+}
+static inline bool history_step_present(const history_step_args& s) { return s.history.p && s.rt_flow && history_conv_present(s.conv); }
+static inline bool history_step_16bit(const history_step_args& s) { return s.history.et == 1 || s.history.et == 2; }
+
+// The region's template ladders: the statement(s) after the value, once per candidate, with `constexpr int NAME` set to the
+// candidate the value equals (the last candidate where it equals none) -- a launch names its instantiation with it.  A `return`
+// inside (FBBEV_LAUNCH_DYN_LDS has one) leaves the enclosing function.
+#define FBBEV_HISTORY_WITH(NAME, v, A, B, ...)                                                                        \
+    do { if ((v) == (A)) { constexpr int NAME = A; __VA_ARGS__; } else { constexpr int NAME = B; __VA_ARGS__; } } while (0)
+// ET over the ring's element type: 16-bit rings only, or all three
+#define FBBEV_HISTORY_ET16(et, ...) FBBEV_HISTORY_WITH(ET, et, 1, 2, __VA_ARGS__)
+#define FBBEV_HISTORY_ET(et, ...) \
+    do { if ((et) == 0) { constexpr int ET = 0; __VA_ARGS__; } else FBBEV_HISTORY_ET16(et, __VA_ARGS__); } while (0)
+
+// Workgroups in XCD-contiguous order: the kernel maps workgroup w to block (w % 8) * per_xcd + w / 8 and skips what lies past
+// `blocks`, so neighbouring blocks share an XCD's L2.  Callers bound `blocks` first (FBBEV_HISTORY_XCD_BLOCKS where nothing else does).
+struct history_xcd_grid { int per_xcd; long long wgs; };
+static inline history_xcd_grid history_xcd(long long blocks) {
+    const int per_xcd = (int)((blocks + 7) / 8);
+    return {per_xcd, (long long)per_xcd * 8};
+}
+static const long long FBBEV_HISTORY_XCD_BLOCKS = (1ll << 31) - 8;
+// Bands of grid rows: YB rows of y (all z) make a slab of YB * Z workgroups per x chunk, 128 / Z rows unless the caller has another
+// number; clamped to the grid
+struct history_bands { int YB, nyb; };
+static inline history_bands history_band_geometry(int YB, int Y) {
+    if (YB < 1) YB = 1;
+    if (YB > Y) YB = Y;
+    return {YB, (Y + YB - 1) / YB};
+}
+
 extern "C" int fbbev_history_flow(const float* history_forward_augs, const float* curr_to_prev_ego_rt, const float* bda,
                                   const float* dx3, const float* lower3, int B, float* rt_flow, fbbev_stream_t stream_) {
     if (B < 0) return FBBEV_E_BADARG;
@@ -2728,19 +2843,19 @@ extern "C" int fbbev_history_stream_prologue(const int32_t* flags, const float* 
     return 0;
 }
 
+// ---- the warp on planes (the reference's layout): one "frame" of CH channel planes per sample
 extern "C" int fbbev_history_warp_e(const void* history, long long history_stride_b, const float* rt_flow, int B, int CH,
                                     int Z, int Y, int X, void* out, long long out_stride_b, int elem_type,
                                     fbbev_stream_t stream_) {
+    const long long zyx = (long long)Z * Y * X;
+    history_warp_args a = {{history, history_stride_b, 1, CH, zyx, elem_type}, {out, out_stride_b, 1, CH, zyx, elem_type},
+                           rt_flow, B, Z, Y, X, (fbbev_rt_stream)stream_};
     if (B < 0 || CH < 0 || Z < 2 || Y < 2 || X < 2) return FBBEV_E_BADARG;      // size-1 axes divide by zero in :208
-    if (elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
+    if (!history_et_ok(elem_type)) return FBBEV_E_BADARG;
     if (B == 0 || CH == 0) return 0;
     if (!history || !rt_flow || !out) return FBBEV_E_BADARG;
-    const long long zyx = (long long)Z * Y * X;
     if (zyx >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (history_stride_b == 0) history_stride_b = (long long)CH * zyx;
-    if (out_stride_b == 0) out_stride_b = (long long)CH * zyx;
-    if (history_stride_b < (long long)CH * zyx || out_stride_b < (long long)CH * zyx) return FBBEV_E_BADARG;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    if (const int e = row_worse(history_ring_operand(a.src, 0, false), history_ring_operand(a.dst, 0, false))) return e;
     // FBBEV_HISTORY_WARP=lds selects the LDS-staged brick kernel (k_history_warp_lds: bit-identical, but as built --
     // one 1024-thread workgroup per CU, staging and taps of a channel serialised by two barriers -- 3x SLOWER than the
     // gather kernel on MI355X, profiles/r02_time_history_lds_vs_gather.jsonl; kept for the next iteration, not the default)
@@ -2759,15 +2874,8 @@ extern "C" int fbbev_history_warp_e(const void* history, long long history_strid
         const int n_groups = (CH + cpb - 1) / cpb;
         const long long blocks = (long long)B * n_groups * ntz * nty * ntx;
         if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-        if (elem_type == 0)
-            FBBEV_LAUNCH(k_history_warp_lds<0>, blocks, 1024, 0, stream, history, history_stride_b, rt_flow, CH, Z, Y, X, BZ, TY,
-                         TX, ntz, nty, ntx, cpb, n_groups, out, out_stride_b);
-        else if (elem_type == 1)
-            FBBEV_LAUNCH(k_history_warp_lds<1>, blocks, 1024, 0, stream, history, history_stride_b, rt_flow, CH, Z, Y, X, BZ, TY,
-                         TX, ntz, nty, ntx, cpb, n_groups, out, out_stride_b);
-        else
-            FBBEV_LAUNCH(k_history_warp_lds<2>, blocks, 1024, 0, stream, history, history_stride_b, rt_flow, CH, Z, Y, X, BZ, TY,
-                         TX, ntz, nty, ntx, cpb, n_groups, out, out_stride_b);
+        FBBEV_HISTORY_ET(elem_type, FBBEV_LAUNCH(k_history_warp_lds<ET>, blocks, 1024, 0, a.stream, history, a.src.stride, rt_flow, CH,
+                                                 Z, Y, X, BZ, TY, TX, ntz, nty, ntx, cpb, n_groups, out, a.dst.stride));
         FBBEV_CHECK_LAUNCH();
         return 0;
     }
@@ -2777,17 +2885,10 @@ extern "C" int fbbev_history_warp_e(const void* history, long long history_strid
     while (cpb > 8 && (long long)B * n_chunks * ((CH + cpb - 1) / cpb) < 4096) cpb >>= 1;
     const int n_groups = (CH + cpb - 1) / cpb;
     const long long blocks = (long long)B * n_groups * n_chunks;
-    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int per_xcd = (int)((blocks + 7) / 8);
-    if (elem_type == 0)
-        FBBEV_LAUNCH(k_history_warp<0>, (long long)per_xcd * 8, 256, 0, stream, history, history_stride_b, rt_flow,
-                     CH, Z, Y, X, cpb, n_groups, n_chunks, per_xcd, (int)blocks, out, out_stride_b);
-    else if (elem_type == 1)
-        FBBEV_LAUNCH(k_history_warp<1>, (long long)per_xcd * 8, 256, 0, stream, history, history_stride_b, rt_flow,
-                     CH, Z, Y, X, cpb, n_groups, n_chunks, per_xcd, (int)blocks, out, out_stride_b);
-    else
-        FBBEV_LAUNCH(k_history_warp<2>, (long long)per_xcd * 8, 256, 0, stream, history, history_stride_b, rt_flow,
-                     CH, Z, Y, X, cpb, n_groups, n_chunks, per_xcd, (int)blocks, out, out_stride_b);
+    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;       // (this kernel's own bound: eight more than the others take)
+    const history_xcd_grid g = history_xcd(blocks);
+    FBBEV_HISTORY_ET(elem_type, FBBEV_LAUNCH(k_history_warp<ET>, g.wgs, 256, 0, a.stream, history, a.src.stride, rt_flow, CH, Z, Y, X,
+                                             cpb, n_groups, n_chunks, g.per_xcd, (int)blocks, out, a.dst.stride));
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2797,59 +2898,49 @@ extern "C" int fbbev_history_warp(const float* history, long long history_stride
     return fbbev_history_warp_e(history, history_stride_b, rt_flow, B, CH, Z, Y, X, out, out_stride_b, 0, stream_);
 }
 
-// voxel-major ring: frames [T][N][C] per sample (history_kernels.h)
+// ---- the warp on the voxel-major ring: frames [T][N][C] per sample (history_kernels.h)
 struct fbbev_warp_vm_plan { int groups, n_xc, YB, nyb; };
 
-static int history_warp_vm_plan(const void* history, long long& history_stride_b, const float* rt_flow, int B, int T, int C,
-                                int Z, int Y, int X, void* out, long long& out_stride_b, int elem_type, fbbev_warp_vm_plan& pl) {
-    if (B < 0 || T < 0 || C <= 0 || Z < 2 || Y < 2 || X < 2) return FBBEV_E_BADARG;
-    if (elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (B == 0 || T == 0) return 0;
-    if (!history || !rt_flow || !out) return FBBEV_E_BADARG;
-    const int VE = elem_type == 0 ? 4 : 8;
-    const long long zyx = (long long)Z * Y * X, frame = zyx * C;
-    if (zyx >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (history_stride_b == 0) history_stride_b = (long long)T * frame;
-    if (out_stride_b == 0) out_stride_b = (long long)T * frame;
-    if (history_stride_b < (long long)T * frame || out_stride_b < (long long)T * frame) return FBBEV_E_BADARG;
-    if (C % VE != 0 || history_stride_b % VE != 0 || out_stride_b % VE != 0 || !aligned16(history) || !aligned16(out))
-        return FBBEV_E_UNSUPPORTED;
+// the checks of a voxel-major warp (0 also for the empty call: B == 0 or no frames) and its grid
+static int history_warp_vm_plan(history_warp_args& a, fbbev_warp_vm_plan& pl) {
+    const int T = a.src.frames, C = a.src.C, et = a.src.et;
+    if (a.B < 0 || T < 0 || C <= 0 || a.Z < 2 || a.Y < 2 || a.X < 2) return FBBEV_E_BADARG;
+    if (!history_et_ok(et)) return FBBEV_E_BADARG;
+    if (a.B == 0 || T == 0) return 0;
+    if (!a.src.p || !a.rt_flow || !a.dst.p) return FBBEV_E_BADARG;
+    const int VE = et == 0 ? 4 : 8;
+    if (a.src.N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = row_worse(history_ring_operand(a.src, VE, true), history_ring_operand(a.dst, VE, true))) return e;
+    if (C % VE != 0) return FBBEV_E_UNSUPPORTED;
     pl.groups = C / VE;
-    if (frame * (elem_type == 0 ? 4 : 2) >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;      // 32-bit byte offsets inside a frame
-    pl.n_xc = (X * pl.groups + 255) / 256;                        // workgroups per grid row
-    int YB = 128 / Z;                                             // rows per band: a (z, y) slab of ~128 workgroups per x chunk
-    YB = fbbev_env_int("FBBEV_HISTORY_VM_YB", YB);                // tuning knob, read on every call (profiles/r02_time_history_bf16_voxel_major.jsonl)
-    if (YB < 1) YB = 1;
-    if (YB > Y) YB = Y;
-    pl.YB = YB;
-    pl.nyb = (Y + YB - 1) / YB;
+    pl.n_xc = (a.X * pl.groups + 255) / 256;                      // workgroups per grid row
+    // rows per band: a (z, y) slab of ~128 workgroups per x chunk; tuning knob, read on every call (profiles/r02_time_history_bf16_voxel_major.jsonl)
+    const history_bands bands = history_band_geometry(fbbev_env_int("FBBEV_HISTORY_VM_YB", 128 / a.Z), a.Y);
+    pl.YB = bands.YB;
+    pl.nyb = bands.nyb;
     return 0;
 }
 
 // the bands yb0 .. yb0 + nyb_c - 1 of every sample (all of them: the whole warp)
-static int history_warp_vm_bands(const void* history, long long history_stride_b, const float* rt_flow, int B, int T, int C,
-                                 int Z, int Y, int X, void* out, long long out_stride_b, int elem_type,
-                                 const fbbev_warp_vm_plan& pl, int yb0, int nyb_c, fbbev_rt_stream stream) {
-    constexpr int TU = 2;
-    const int groups = pl.groups, n_xc = pl.n_xc, YB = pl.YB;
-    const long long blocks = (long long)B * nyb_c * n_xc * YB * Z;
-    if (blocks >= (1ll << 31) - 8) return FBBEV_E_UNSUPPORTED;
+static int history_warp_vm_bands(const history_warp_args& a, const fbbev_warp_vm_plan& pl, int yb0, int nyb_c) {
+    const long long blocks = (long long)a.B * nyb_c * pl.n_xc * pl.YB * a.Z;
+    if (blocks >= FBBEV_HISTORY_XCD_BLOCKS) return FBBEV_E_UNSUPPORTED;
     if (blocks == 0) return 0;
-    const int per_xcd = (int)((blocks + 7) / 8);
+    const history_xcd_grid g = history_xcd(blocks);
     // occupancy experiment knob (round 3, profiles/r03_exp_history_occupancy.jsonl): dynamic LDS the kernel does not use, in KB
     static const size_t warp_pad = (size_t)fbbev_env_int("FBBEV_HISTORY_WARP_LDS_PAD_KB", 0) * 1024;
-#define FBBEV_HWVM(ET_, TU_, ST_)                                                                                                               \
-    FBBEV_LAUNCH_DYN_LDS((k_history_warp_vm<ET_, TU_, ST_>), (long long)per_xcd * 8, 256, warp_pad, stream, history, history_stride_b, rt_flow, \
-                         T, C, Z, Y, X, groups, n_xc, YB, nyb_c, per_xcd, (int)blocks, out, out_stride_b, yb0)
-    // ST = 1: non-temporal ring stores (A/B on one box: 4.0 vs 4.2 ms at 400x400x16, 0.56 vs 0.61 ms at 100x100x8 B=4)
-    // fp16 ring: four frames (32 taps) in flight per thread -- the widening rides in the multiply (v_fma_mix_f32), which left the
-    // registers for it (round 6: 3.45 -> 3.33 ms at 400x400x16); FBBEV_HISTORY_VM_TU=2 restores two
+    // template arguments: frames in flight per thread, then ST = 1: non-temporal ring stores (A/B on one box: 4.0 vs 4.2 ms at
+    // 400x400x16, 0.56 vs 0.61 ms at 100x100x8 B=4).  Two frames; an fp16 ring four (32 taps) -- the widening rides in the multiply
+    // (v_fma_mix_f32), which left the registers for it (round 6: 3.45 -> 3.33 ms at 400x400x16); FBBEV_HISTORY_VM_TU=2 restores two
     static const int tu2 = fbbev_env_int("FBBEV_HISTORY_VM_TU", 0) == 2 ? 1 : 0;
-    if (elem_type == 0) FBBEV_HWVM(0, TU, 1);
-    else if (elem_type == 1) FBBEV_HWVM(1, TU, 1);
-    else if (tu2) FBBEV_HWVM(2, TU, 1);
-    else FBBEV_HWVM(2, 4, 1);
-#undef FBBEV_HWVM
+    if (a.src.et == 2 && !tu2)
+        FBBEV_LAUNCH_DYN_LDS((k_history_warp_vm<2, 4, 1>), g.wgs, 256, warp_pad, a.stream, a.src.p, a.src.stride, a.rt_flow, a.src.frames,
+                             a.src.C, a.Z, a.Y, a.X, pl.groups, pl.n_xc, pl.YB, nyb_c, g.per_xcd, (int)blocks, const_cast<void*>(a.dst.p),
+                             a.dst.stride, yb0);
+    else
+        FBBEV_HISTORY_ET(a.src.et, FBBEV_LAUNCH_DYN_LDS((k_history_warp_vm<ET, 2, 1>), g.wgs, 256, warp_pad, a.stream, a.src.p, a.src.stride,
+                                                        a.rt_flow, a.src.frames, a.src.C, a.Z, a.Y, a.X, pl.groups, pl.n_xc, pl.YB, nyb_c,
+                                                        g.per_xcd, (int)blocks, const_cast<void*>(a.dst.p), a.dst.stride, yb0));
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2857,11 +2948,13 @@ static int history_warp_vm_bands(const void* history, long long history_stride_b
 extern "C" int fbbev_history_warp_vm(const void* history, long long history_stride_b, const float* rt_flow, int B, int T, int C,
                                      int Z, int Y, int X, void* out, long long out_stride_b, int elem_type,
                                      fbbev_stream_t stream_) {
+    const long long zyx = (long long)Z * Y * X;
+    history_warp_args a = {{history, history_stride_b, T, C, zyx, elem_type}, {out, out_stride_b, T, C, zyx, elem_type},
+                           rt_flow, B, Z, Y, X, (fbbev_rt_stream)stream_};
     fbbev_warp_vm_plan pl{};
-    const int e = history_warp_vm_plan(history, history_stride_b, rt_flow, B, T, C, Z, Y, X, out, out_stride_b, elem_type, pl);
+    const int e = history_warp_vm_plan(a, pl);
     if (e || B == 0 || T == 0) return e;
-    return history_warp_vm_bands(history, history_stride_b, rt_flow, B, T, C, Z, Y, X, out, out_stride_b, elem_type, pl, 0, pl.nyb,
-                                 (fbbev_rt_stream)stream_);
+    return history_warp_vm_bands(a, pl, 0, pl.nyb);
 }
 
 // fbbev_history_warp_vm with a per-sample source: where flags[b] != 0 the T frames of sample b are sampled from curr[b] (the current
@@ -2869,51 +2962,402 @@ extern "C" int fbbev_history_warp_vm(const void* history, long long history_stri
 extern "C" int fbbev_history_warp_vm_src(const void* history, long long history_stride_b, const void* curr, long long curr_stride_b,
                                          const int32_t* flags, const float* rt_flow, int B, int T, int C, int Z, int Y, int X,
                                          void* out, long long out_stride_b, int elem_type, fbbev_stream_t stream_) {
+    const long long zyx = (long long)Z * Y * X;
+    history_warp_args a = {{history, history_stride_b, T, C, zyx, elem_type}, {out, out_stride_b, T, C, zyx, elem_type},
+                           rt_flow, B, Z, Y, X, (fbbev_rt_stream)stream_};
+    history_ring cur = {curr, curr_stride_b, 1, C, zyx, elem_type};
     fbbev_warp_vm_plan pl{};
-    const int e = history_warp_vm_plan(history, history_stride_b, rt_flow, B, T, C, Z, Y, X, out, out_stride_b, elem_type, pl);
+    const int e = history_warp_vm_plan(a, pl);
     if (e || B == 0 || T == 0) return e;
     if (!curr || !flags) return FBBEV_E_BADARG;
-    const int VE = elem_type == 0 ? 4 : 8;
-    const long long frame = (long long)Z * Y * X * C;
-    if (curr_stride_b == 0) curr_stride_b = frame;
-    if (curr_stride_b < frame) return FBBEV_E_BADARG;
-    if (curr_stride_b % VE != 0 || !aligned16(curr)) return FBBEV_E_UNSUPPORTED;
-    constexpr int TU = 2;
+    if (const int ec = history_ring_operand(cur, elem_type == 0 ? 4 : 8, false)) return ec;
     const long long blocks = (long long)B * pl.nyb * pl.n_xc * pl.YB * Z;
-    if (blocks >= (1ll << 31) - 8) return FBBEV_E_UNSUPPORTED;
-    const int per_xcd = (int)((blocks + 7) / 8);
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-#define FBBEV_HWVMS(ET_, TU_)                                                                                                          \
-    FBBEV_LAUNCH((k_history_warp_vm_src<ET_, TU_, 1>), (long long)per_xcd * 8, 256, 0, stream, history, history_stride_b, curr,       \
-                 curr_stride_b, flags, rt_flow, T, C, Z, Y, X, pl.groups, pl.n_xc, pl.YB, pl.nyb, per_xcd, (int)blocks, out, out_stride_b)
+    if (blocks >= FBBEV_HISTORY_XCD_BLOCKS) return FBBEV_E_UNSUPPORTED;
+    const history_xcd_grid g = history_xcd(blocks);
     // the instantiations fbbev_history_warp_vm launches by default: two frames in flight, four for an fp16 ring
-    if (elem_type == 0) FBBEV_HWVMS(0, TU);
-    else if (elem_type == 1) FBBEV_HWVMS(1, TU);
-    else FBBEV_HWVMS(2, 4);
-#undef FBBEV_HWVMS
+    FBBEV_HISTORY_ET(elem_type, FBBEV_LAUNCH((k_history_warp_vm_src<ET, ET == 2 ? 4 : 2, 1>), g.wgs, 256, 0, a.stream, history, a.src.stride,
+                                             curr, cur.stride, flags, rt_flow, T, C, Z, Y, X, pl.groups, pl.n_xc, pl.YB, pl.nyb, g.per_xcd,
+                                             (int)blocks, out, a.dst.stride));
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int fbbev_history_frame_vm(const float* curr, int B, int C, int N, int inner, void* out, long long out_stride_b,
                                       int elem_type, fbbev_stream_t stream_) {
-    if (B < 0 || C <= 0 || N < 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
+    history_ring slot = {out, out_stride_b, 1, C, N, elem_type};
+    if (B < 0 || C <= 0 || N < 0 || !history_et_ok(elem_type)) return FBBEV_E_BADARG;
     if (inner < 1 || N % inner != 0) return FBBEV_E_BADARG;
     if (B == 0 || N == 0) return 0;
     if (!curr || !out) return FBBEV_E_BADARG;
     const int VE = elem_type == 0 ? 4 : 8;
-    if (out_stride_b == 0) out_stride_b = (long long)N * C;
-    if (out_stride_b < (long long)N * C) return FBBEV_E_BADARG;
-    if (C % VE != 0 || C > 512 || out_stride_b % VE != 0 || !aligned16(out)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = history_ring_operand(slot, VE, false)) return e;
+    if (C % VE != 0 || C > 512) return FBBEV_E_UNSUPPORTED;
     const int tiles_per_b = (N + 63) / 64;
     const long long blocks = (long long)B * tiles_per_b;
     if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)C * 65 * sizeof(float);
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    if (elem_type == 0) FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<0>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
-    else if (elem_type == 1) FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<1>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
-    else FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<2>, blocks, 256, lds, stream, curr, C, N, inner, tiles_per_b, out, out_stride_b);
+    FBBEV_HISTORY_ET(elem_type, FBBEV_LAUNCH_DYN_LDS(k_history_frame_vm<ET>, blocks, 256, lds, (fbbev_rt_stream)stream_, curr, C, N, inner,
+                                                     tiles_per_b, out, slot.stride));
     FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the convolutions in fp32 (FP32 MFMA), planes or voxel-major (vm)
+// Each weight-workspace layout below: where the pieces lie, how many bytes they take, and the one launch that fills them.
+// fp32: fragment-ordered copies of the two weight matrices (tiny: (1 + T1) * C * C floats)
+struct history_weights_f32 { const float* w1f; const float* w2f; size_t need; };
+static int history_weights_f32_prepare(const history_conv_args& c, bool vm, history_weights_f32& w) {
+    const int T1 = c.feats.frames, MT1 = c.feats.C / 16, MT2 = c.Cout / 16, KS = c.feats.C / 4;
+    w.need = ((size_t)MT1 * KS + (size_t)T1 * MT2 * KS) * 64 * sizeof(float);
+    if (c.ws_bytes < w.need) return FBBEV_E_WORKSPACE;
+    float* w1f = static_cast<float*>(c.ws);
+    w.w1f = w1f;
+    w.w2f = w1f + (size_t)MT1 * KS * 64;
+    const int nfrag = (MT1 * KS + T1 * MT2 * KS) * 64;
+    FBBEV_LAUNCH(k_history_weight_fragments, (nfrag + 255) / 256, 256, 0, c.stream, c.w1, c.w2, MT1, MT2, KS, T1, vm ? 1 : 0, w1f);
+    return 0;
+}
+
+static int history_conv_launch(const history_conv_args& c, bool vm) {
+    const int T1 = c.feats.frames, C = c.feats.C, N = (int)c.feats.N;
+    const int tiles_per_b = (N + 63) / 64;
+    const long long blocks = (long long)c.B * tiles_per_b;
+    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    const size_t lds = (size_t)4 * C * 16 * sizeof(float);
+    if (c.ws && history_conv_square(c)) {                          // the register-resident kernel
+        history_weights_f32 w{};
+        if (const int e = history_weights_f32_prepare(c, vm, w)) return e;
+        FBBEV_HISTORY_WITH(VM, vm ? 1 : 0, 1, 0, FBBEV_HISTORY_WITH(MT, C / 16, 5, 1, FBBEV_HISTORY_ET(c.feats.et,
+            FBBEV_LAUNCH((k_history_conv_t<MT, MT, ET, VM != 0>), blocks, 256, lds, c.stream, c.feats.p, c.feats.stride, w.w1f,
+                         c.bias1, w.w2f, c.bias2, T1, N, tiles_per_b, c.out))));
+    } else if (vm)
+        return FBBEV_E_UNSUPPORTED;
+    else
+        FBBEV_HISTORY_ET(c.feats.et, FBBEV_LAUNCH(k_history_conv<ET>, blocks, 256, lds, c.stream, c.feats.p, c.feats.stride, c.w1, c.bias1,
+                                                  c.w2, c.bias2, T1, C, c.Cout, N, tiles_per_b, c.out));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_history_conv_e(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
+                                    const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
+                                    float* out, void* workspace, size_t workspace_bytes, int elem_type,
+                                    fbbev_stream_t stream_) {
+    history_conv_args c = {{feats, feats_stride_b, T1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_};
+    if (!history_conv_dims_ok(c)) return FBBEV_E_BADARG;
+    if (history_conv_empty(c)) return 0;
+    if (!history_conv_present(c)) return FBBEV_E_BADARG;
+    if (C % 16 != 0 || Cout % 16 != 0 || C > 16 * FBBEV_HC_MAX_TILES || Cout > 16 * FBBEV_HC_MAX_TILES)
+        return FBBEV_E_UNSUPPORTED;
+    if (const int e = history_ring_operand(c.feats, 0, false)) return e;
+    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;                                  // 16-byte bias loads
+    return history_conv_launch(c, false);
+}
+
+extern "C" int fbbev_history_conv(const float* feats, long long feats_stride_b, const float* w1, const float* bias1,
+                                  const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
+                                  float* out, void* workspace, size_t workspace_bytes, fbbev_stream_t stream_) {
+    return fbbev_history_conv_e(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace,
+                                workspace_bytes, 0, stream_);
+}
+
+// the fp32-MFMA convolutions on a voxel-major ring (feats (B, T1, N, C)); C = Cout in {16, 80}, workspace required
+extern "C" int fbbev_history_conv_vm(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
+                                     const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
+                                     float* out, void* workspace, size_t workspace_bytes, int elem_type,
+                                     fbbev_stream_t stream_) {
+    history_conv_args c = {{feats, feats_stride_b, T1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_};
+    if (!history_conv_dims_ok(c)) return FBBEV_E_BADARG;
+    if (history_conv_empty(c)) return 0;
+    if (!history_conv_present(c)) return FBBEV_E_BADARG;
+    if (!history_conv_square(c)) return FBBEV_E_UNSUPPORTED;
+    if (!workspace) return FBBEV_E_WORKSPACE;
+    if (const int e = history_ring_operand(c.feats, 8, true)) return e;                 // 8- / 16-byte row pieces
+    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;
+    return history_conv_launch(c, true);
+}
+
+// ---- the convolutions on the bf16 MFMAs (operands rounded to bf16, fp32 accumulate): C = Cout = 80 or 16
+// bf16: the two weight matrices in fragment order, 8 elements per lane
+struct history_weights_bf16 {
+    const unsigned short* w1f; const unsigned short* w2f;
+    int MT, KS;                                             // 16-row tiles of the output channels, 32-deep slices of the input channels
+    size_t part1;                                           // elements of W1's fragments (= of one frame's W2)
+    size_t a2s;                                             // ... padded to the 256 lanes that stage it
+    size_t need;
+};
+static int history_weights_bf16_prepare(const history_conv_args& c, history_weights_bf16& w) {
+    const int T1 = c.feats.frames, C = c.feats.C;
+    w.MT = C / 16;
+    w.KS = (C + 31) / 32;
+    w.part1 = (size_t)w.MT * w.KS * 64 * 8;
+    w.a2s = (size_t)((w.MT * w.KS * 64 + 255) / 256) * 256 * 8;
+    w.need = (size_t)(1 + T1) * w.part1 * sizeof(unsigned short);
+    if (!c.ws || !aligned16(c.ws) || c.ws_bytes < w.need) return FBBEV_E_WORKSPACE;
+    unsigned short* w1f = static_cast<unsigned short*>(c.ws);
+    w.w1f = w1f;
+    w.w2f = w1f + w.part1;
+    const int nfrag = (w.MT * w.KS + T1 * w.MT * w.KS) * 64;
+    FBBEV_LAUNCH(k_history_weight_fragments_bf16, (nfrag + 255) / 256, 256, 0, c.stream, c.w1, c.w2, w.MT, w.MT, C, T1, w1f);
+    return 0;
+}
+
+static int history_conv_bf16_launch(const history_conv_args& c, bool vm) {
+    const int T1 = c.feats.frames, N = (int)c.feats.N;
+    const int tiles_per_b = (N + 63) / 64;
+    const long long blocks = (long long)c.B * tiles_per_b;
+    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    history_weights_bf16 w{};
+    if (const int e = history_weights_bf16_prepare(c, w)) return e;
+    size_t lds = (2 * w.a2s + (size_t)4 * 16 * (w.KS * 32 + 8)) * sizeof(unsigned short);           // W2_t x 2 + Y rows
+    static const size_t conv_pad = (size_t)fbbev_env_int("FBBEV_HISTORY_CONV_LDS_PAD_KB", 0) * 1024;   // occupancy experiment knob
+    if (conv_pad > lds) lds = conv_pad;
+    if (c.feats.C == 80)
+        FBBEV_HISTORY_WITH(VM, vm ? 1 : 0, 1, 0, FBBEV_HISTORY_ET(c.feats.et,
+            FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16<5, 5, ET, VM != 0>), blocks, 256, lds, c.stream, c.feats.p, c.feats.stride, w.w1f,
+                                 c.bias1, w.w2f, c.bias2, T1, N, tiles_per_b, c.out)));
+    else
+        FBBEV_HISTORY_WITH(VM, vm ? 1 : 0, 1, 0, FBBEV_HISTORY_ET(c.feats.et,
+            FBBEV_LAUNCH((k_history_conv_bf16<1, 1, ET, VM != 0>), blocks, 256, lds, c.stream, c.feats.p, c.feats.stride, w.w1f, c.bias1,
+                         w.w2f, c.bias2, T1, N, tiles_per_b, c.out)));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_history_conv_bf16(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
+                                       const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
+                                       float* out, void* workspace, size_t workspace_bytes, int voxel_major, int elem_type,
+                                       fbbev_stream_t stream_) {
+    history_conv_args c = {{feats, feats_stride_b, T1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_};
+    if (!history_conv_dims_ok(c)) return FBBEV_E_BADARG;
+    if (voxel_major != 0 && voxel_major != 1) return FBBEV_E_BADARG;
+    if (history_conv_empty(c)) return 0;
+    if (!history_conv_present(c)) return FBBEV_E_BADARG;
+    if (!history_conv_square(c)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = history_ring_operand(c.feats, voxel_major ? 8 : 0, voxel_major != 0)) return e;   // 16-byte row pieces
+    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;                                              // 16-byte bias loads
+    return history_conv_bf16_launch(c, voxel_major != 0);
+}
+
+// Warp + new ring + both convolutions in ONE kernel (k_history_fused_bf16): history (B,T,N,C) -> next ring slots 1..T of
+// `next` (B,T+1,N,C) (slot 0 = the current frame, stored by the caller with fbbev_history_frame_vm BEFORE this call) and
+// out (B,Cout,N) = relu(bias2 + sum_t w2_t . relu(w1 . x_t + bias1_t)) over the T+1 frames of `next`, bf16 MFMA.
+extern "C" int fbbev_history_fused_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
+                                      const float* rt_flow, const float* w1, const float* bias1, const float* w2,
+                                      const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
+                                      void* workspace, size_t workspace_bytes, int elem_type, fbbev_stream_t stream_) {
+    const long long N = (long long)Z * Y * X;
+    history_step_args s = {{history, history_stride_b, T, C, N, elem_type},
+                           {{next, next_stride_b, T + 1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                            (fbbev_rt_stream)stream_}, rt_flow, Z, Y, X};
+    if (!history_step_dims_ok(s)) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    if (!history_step_present(s)) return FBBEV_E_BADARG;
+    if (C != 80 || Cout != 80 || !history_step_16bit(s) || Z < 2 || Y < 2 || X < 2) return FBBEV_E_UNSUPPORTED;
+    if (const int e = row_worse(history_ring_operand(s.history, 8, true), history_ring_operand(s.conv.feats, 8, true))) return e;
+    if (!aligned16(bias1) || N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    history_weights_bf16 w{};
+    if (const int e = history_weights_bf16_prepare(s.conv, w)) return e;
+    FBBEV_CHECK_LAUNCH();
+    const int n_xc = (X + 63) / 64;                               // 64-voxel tiles per grid row
+    // (z, y) slabs per x chunk, as the warp kernel orders its workgroups (its default: FBBEV_HISTORY_VM_YB is not read here)
+    const history_bands bands = history_band_geometry(128 / Z, Y);
+    const long long blocks = (long long)B * bands.nyb * n_xc * bands.YB * Z;
+    if (blocks >= FBBEV_HISTORY_XCD_BLOCKS) return FBBEV_E_UNSUPPORTED;
+    const history_xcd_grid g = history_xcd(blocks);
+    // 4 W2 buffers + the W1 fragments + the Y rows + 4 operand tiles: 137 KB (one 1024-thread workgroup per CU)
+    const size_t lds = ((size_t)4 * w.a2s + w.part1 + (size_t)4 * 16 * (w.KS * 32 + 8) + (size_t)4 * 64 * FBBEV_HF_XP) *
+                       sizeof(unsigned short) + (size_t)4 * 80 * sizeof(float);
+    FBBEV_HISTORY_ET16(elem_type, FBBEV_LAUNCH_DYN_LDS((k_history_fused_bf16<ET>), g.wgs, 1024, lds, s.conv.stream, history,
+                                                       s.history.stride, next, s.conv.feats.stride, rt_flow, w.w1f, bias1, w.w2f, bias2,
+                                                       T + 1, Z, Y, X, n_xc, bands.YB, bands.nyb, g.per_xcd, (int)blocks, out));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- fp32-grade convolutions on the 16-bit MFMAs (split operands, history_conv_x3_kernels.h): voxel-major 16-bit ring
+// split-operand: W1 (hi | lo) and every frame's W2 (hi | lo) in fragment order, then B * T1 * C biases scaled for the ring's type
+struct history_weights_x3 { const unsigned short* w1x; const unsigned short* w2x; const float* biasx; size_t pieces, part1, need; };
+static int history_weights_x3_prepare(const history_conv_args& c, history_weights_x3& w) {
+    const int T1 = c.feats.frames, C = c.feats.C, MT = C / 16, KS = (C + 31) / 32;
+    w.part1 = (size_t)MT * KS * 64 * 8;
+    const size_t wbytes = (size_t)(1 + T1) * 2 * w.part1 * sizeof(unsigned short);
+    w.need = wbytes + (size_t)c.B * T1 * C * sizeof(float);
+    if (!c.ws || !aligned16(c.ws) || c.ws_bytes < w.need) return FBBEV_E_WORKSPACE;
+    unsigned short* w1x = static_cast<unsigned short*>(c.ws);
+    float* biasx = reinterpret_cast<float*>(static_cast<char*>(c.ws) + wbytes);
+    w.w1x = w1x;
+    w.w2x = w1x + 2 * w.part1;
+    w.biasx = biasx;
+    w.pieces = 2 * w.part1 / 8 + C / 4;                           // 16-byte pieces of a frame's W2 (hi | lo) and its bias row
+    const long long nprep = (long long)(MT * KS + T1 * MT * KS) * 64 + (long long)c.B * T1 * C;
+    if (nprep >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    FBBEV_HISTORY_ET16(c.feats.et, FBBEV_LAUNCH(k_history_weight_fragments_bf16x3<ET>, (nprep + 255) / 256, 256, 0, c.stream, c.w1, c.w2,
+                                                c.bias1, MT, MT, C, T1, c.B * T1, w1x, biasx));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// the checks of the split-operand convolutions (0 also for the empty call: B == 0 or N == 0), then their workspace
+static int history_conv_x3_prepare(history_conv_args& c, history_weights_x3& w) {
+    if (!history_conv_dims_ok(c)) return FBBEV_E_BADARG;
+    if (history_conv_empty(c)) return 0;
+    if (!history_conv_present(c)) return FBBEV_E_BADARG;
+    if (!history_conv_square(c) || c.feats.et == 0) return FBBEV_E_UNSUPPORTED;
+    if (const int e = history_ring_operand(c.feats, 8, true)) return e;
+    if (!aligned16(c.bias1)) return FBBEV_E_UNSUPPORTED;
+    return history_weights_x3_prepare(c, w);
+}
+
+// n segments of len voxels, stride apart from voxel seg0 on, in every sample (one segment of N voxels: the whole volume)
+struct history_segments { int seg0, stride, len, n; };
+
+// nw waves per workgroup -- 8: a workgroup fills a CU's registers; 4: half of them (the pipelined step)
+static int history_conv_x3_segments(const history_conv_args& c, const history_weights_x3& w, history_segments sg, int nw,
+                                    fbbev_rt_stream stream) {
+    if (sg.len <= 0 || sg.n <= 0) return 0;
+    const int T1 = c.feats.frames, N = (int)c.feats.N;
+    const int nt = 64 * nw;
+    const int tile_voxels = 16 * nw * FBBEV_HX3_NV;
+    const int tiles_per_seg = (sg.len + tile_voxels - 1) / tile_voxels;
+    const long long tiles_per_b = (long long)tiles_per_seg * sg.n;
+    const long long blocks = (long long)c.B * tiles_per_b;
+    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    // one frame per workgroup barrier (FPB = 2, four W2 buffers: measured 2 % slower, profiles/r06_exp_history_step.md)
+    const size_t lds = ((size_t)2 * ((w.pieces + nt - 1) / nt) * nt * 8 + 2 * w.part1) * sizeof(unsigned short);
+    // template arguments after ET: two frames of X in flight (three spill: 256 registers at 2 waves / SIMD), the waves, one frame per barrier
+    FBBEV_HISTORY_WITH(MT, c.feats.C / 16, 5, 1, FBBEV_HISTORY_WITH(NW, nw, 4, 8, FBBEV_HISTORY_ET16(c.feats.et,
+        FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16x3<MT, MT, ET, 2, NW, 1>), blocks, 64 * NW, lds, stream, c.feats.p, c.feats.stride,
+                             w.w1x, w.biasx, w.w2x, c.bias2, T1, N, (int)tiles_per_b, c.out, sg.seg0, sg.stride, sg.len, tiles_per_seg))));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_history_conv_bf16x3(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
+                                         const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
+                                         float* out, void* workspace, size_t workspace_bytes, int elem_type,
+                                         fbbev_stream_t stream_) {
+    history_conv_args c = {{feats, feats_stride_b, T1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_};
+    history_weights_x3 w{};
+    const int e = history_conv_x3_prepare(c, w);
+    if (e || B <= 0 || N <= 0) return e;
+    static const int nw = fbbev_env_int("FBBEV_HX3_WAVES", 8) == 4 ? 4 : 8;     // tuning: 256-thread workgroups
+    return history_conv_x3_segments(c, w, {0, 0, N, 1}, nw, c.stream);
+}
+
+// One history step on a 16-bit voxel-major ring as ONE kernel (history_fused_x3_kernels.h): every MFMA wave warps its own operands.
+// next[:, 0] must hold the current frame; writes next[:, 1:] (== fbbev_history_warp_vm) and out (== fbbev_history_conv_bf16x3).
+extern "C" int fbbev_history_fused_x3_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
+                                         const float* rt_flow, const float* w1, const float* bias1, const float* w2,
+                                         const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
+                                         void* workspace, size_t workspace_bytes, int elem_type, fbbev_stream_t stream_) {
+    const long long N = (long long)Z * Y * X;
+    history_step_args s = {{history, history_stride_b, T, C, N, elem_type},
+                           {{next, next_stride_b, T + 1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                            (fbbev_rt_stream)stream_}, rt_flow, Z, Y, X};
+    if (!history_step_dims_ok(s)) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    if (!history_step_present(s)) return FBBEV_E_BADARG;
+    if (C != 80 || Cout != 80 || !history_step_16bit(s) || Z < 2 || Y < 2 || X < 2) return FBBEV_E_UNSUPPORTED;
+    if (const int e = row_worse(history_ring_operand(s.history, 8, true), history_ring_operand(s.conv.feats, 8, true))) return e;
+    if (N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (workspace_bytes < 64) return FBBEV_E_WORKSPACE;
+    s.conv.ws_bytes -= 64;                                                                      // the tail of the workspace: see `dump`
+    history_weights_x3 w{};
+    if (const int e = history_conv_x3_prepare(s.conv, w)) return e;
+    void* dump = static_cast<char*>(workspace) + (s.conv.ws_bytes & ~(size_t)15);              // 16 bytes nobody reads
+    const int n_xt = (X + 15) / 16, n_yt = (Y + 7) / 8;           // bricks of 16 x 8 voxels of one z plane, z fastest
+    const long long blocks = (long long)B * n_yt * n_xt * Z;
+    if (blocks >= FBBEV_HISTORY_XCD_BLOCKS) return FBBEV_E_UNSUPPORTED;
+    const history_xcd_grid g = history_xcd(blocks);
+    // two W2 / bias blocks + W1 (hi | lo) + two operand tiles [128 voxels][FBBEV_HFX_PITCH] + the voxel table [128][16 dwords]: 154 KB
+    const size_t lds = ((size_t)2 * ((w.pieces + 511) / 512) * 512 * 8 + 2 * w.part1 + (size_t)2 * 128 * FBBEV_HFX_PITCH) * sizeof(unsigned short) +
+                       (size_t)128 * 16 * sizeof(unsigned int);
+    FBBEV_HISTORY_ET16(elem_type, FBBEV_LAUNCH_DYN_LDS((k_history_fused_x3<ET>), g.wgs, 512, lds, s.conv.stream, history, s.history.stride,
+                                                       next, s.conv.feats.stride, rt_flow, w.w1x, w.biasx, w.w2x, bias2, T + 1, Z, Y, X,
+                                                       n_xt, n_yt, g.per_xcd, (int)blocks, out, dump));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// One history step on a 16-bit voxel-major ring as a two-stream pipeline: the warp of a band of grid rows into next[:, 1:] on the
+// caller's stream, the split-operand convolutions of the band before it on a second stream -- a bandwidth-bound gather kernel and
+// an MFMA-bound one that leave each other's resource idle when they run back to back.  next[:, 0] must hold the current frame.
+// The same kernels, operands and results as fbbev_history_warp_vm + fbbev_history_conv_bf16x3, bit for bit.
+struct fbbev_side_stream { fbbev_rt_stream stream; fbbev_rt_event ev[2 + 64]; bool ok; };
+
+static fbbev_side_stream* history_side_stream() {
+    static fbbev_side_stream table[16];
+    static bool made[16];
+    const int d = fbbev_rt_device();
+    if (d < 0 || d >= 16) return nullptr;
+    static std::mutex mu;                                    // (first use from two host threads; the stream and its events are per DEVICE:
+    std::lock_guard<std::mutex> lock(mu);                    //  callers serialise their calls per device, as with any stream-ordered workspace)
+    if (!made[d]) {
+        made[d] = true;
+        // the convolutions' stream is created at the device's highest priority: built to let their workgroups in ahead of the thousands
+        // of queued warp workgroups -- measured: no effect on the dispatch (profiles/r06_exp_history_step.md).
+        // FBBEV_HISTORY_STEP_PRIORITY=0: equal priorities
+        table[d].ok = fbbev_rt_stream_create(&table[d].stream, fbbev_env_int("FBBEV_HISTORY_STEP_PRIORITY", 1) == 0 ? 0 : 1) == 0;
+        for (int i = 0; i < 2 + 64 && table[d].ok; ++i) table[d].ok = fbbev_rt_event_create(&table[d].ev[i]) == 0;
+    }
+    return table[d].ok ? &table[d] : nullptr;
+}
+
+extern "C" int fbbev_history_step_x3_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
+                                        const float* rt_flow, const float* w1, const float* bias1, const float* w2,
+                                        const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
+                                        void* workspace, size_t workspace_bytes, int elem_type, int chunks,
+                                        fbbev_stream_t stream_) {
+    const long long N = (long long)Z * Y * X;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    history_step_args s = {{history, history_stride_b, T, C, N, elem_type},
+                           {{next, next_stride_b, T + 1, C, N, elem_type}, w1, bias1, w2, bias2, B, Cout, out, workspace, workspace_bytes,
+                            stream}, rt_flow, Z, Y, X};
+    if (!history_step_dims_ok(s) || chunks < 0 || chunks > 64) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    if (!history_step_present(s)) return FBBEV_E_BADARG;
+    if (!history_step_16bit(s)) return FBBEV_E_UNSUPPORTED;
+    if (N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (const int e = history_ring_operand(s.conv.feats, 0, false)) return e;                   // the history's stride: the warp's plan
+    void* warped = static_cast<char*>(next) + N * C * 2;                                         // next[:, 1:]
+    history_warp_args wa = {s.history, {warped, s.conv.feats.stride, T, C, N, elem_type}, rt_flow, B, Z, Y, X, stream};
+    fbbev_warp_vm_plan wp{};
+    int e = history_warp_vm_plan(wa, wp);
+    if (e) return e;
+    history_weights_x3 w{};
+    e = history_conv_x3_prepare(s.conv, w);
+    if (e) return e;
+    if (chunks == 0) chunks = 10;
+    // the convolutions of the pipeline in 256-thread workgroups: half a CU's registers, so that warp waves share the CU with them
+    static const int step_nw = fbbev_env_int("FBBEV_HISTORY_STEP_WAVES", 4) == 8 ? 8 : 4;
+    if (chunks > wp.nyb) chunks = wp.nyb;
+    fbbev_side_stream* side = chunks > 1 ? history_side_stream() : nullptr;
+    if (!side) {                                                                                  // one chunk: the two kernels back to back
+        e = history_warp_vm_bands(wa, wp, 0, wp.nyb);
+        if (e) return e;
+        return history_conv_x3_segments(s.conv, w, {0, 0, (int)N, 1}, 8, stream);
+    }
+#define FBBEV_RT(x) do { const int e_ = (x); if (e_) return e_; } while (0)
+    FBBEV_RT(fbbev_rt_event_record(side->ev[0], stream));
+    FBBEV_RT(fbbev_rt_stream_wait(side->stream, side->ev[0]));
+    for (int i = 0; i < chunks; ++i) {
+        const int yb0 = (int)((long long)wp.nyb * i / chunks), yb1 = (int)((long long)wp.nyb * (i + 1) / chunks);
+        e = history_warp_vm_bands(wa, wp, yb0, yb1 - yb0);
+        if (e) return e;
+        FBBEV_RT(fbbev_rt_event_record(side->ev[2 + i], stream));
+        FBBEV_RT(fbbev_rt_stream_wait(side->stream, side->ev[2 + i]));
+        const int y0 = yb0 * wp.YB, y1 = yb1 * wp.YB < Y ? yb1 * wp.YB : Y;
+        e = history_conv_x3_segments(s.conv, w, {y0 * X, Y * X, (y1 - y0) * X, Z}, step_nw, side->stream);
+        if (e) return e;
+    }
+    FBBEV_RT(fbbev_rt_event_record(side->ev[1], side->stream));
+    FBBEV_RT(fbbev_rt_stream_wait(stream, side->ev[1]));
+#undef FBBEV_RT
     return 0;
 }
 
@@ -2950,299 +3394,6 @@ extern "C" int fbbev_layernorm_bwd(const float* x, const float* grad_out, const 
     const int wgs = fbbev_layernorm_bwd_partials(rows);
     FBBEV_LAUNCH(k_layernorm_rows_bwd, wgs, 256, 0, (fbbev_rt_stream)stream_, x, grad_out, weight, eps, rows, C, grad_x, partial);
     FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-template <int ET, bool VM = false>
-static int history_conv_launch(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                               const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                               float* out, void* workspace, size_t workspace_bytes, fbbev_rt_stream stream) {
-    const int tiles_per_b = (N + 63) / 64;
-    const long long blocks = (long long)B * tiles_per_b;
-    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const size_t lds = (size_t)4 * C * 16 * sizeof(float);
-    if (workspace && ((C == 80 && Cout == 80) || (C == 16 && Cout == 16))) {
-        // fragment-ordered copies of the two weight matrices (tiny: (1 + T1) * C * C floats), then the register-resident kernel
-        const int MT1 = C / 16, MT2 = Cout / 16, KS = C / 4;
-        const size_t need = ((size_t)MT1 * KS + (size_t)T1 * MT2 * KS) * 64 * sizeof(float);
-        if (workspace_bytes < need) return FBBEV_E_WORKSPACE;
-        float* w1f = static_cast<float*>(workspace);
-        float* w2f = w1f + (size_t)MT1 * KS * 64;
-        const int nfrag = (MT1 * KS + T1 * MT2 * KS) * 64;
-        FBBEV_LAUNCH(k_history_weight_fragments, (nfrag + 255) / 256, 256, 0, stream, w1, w2, MT1, MT2, KS, T1, VM ? 1 : 0, w1f);
-        if (C == 80)
-            FBBEV_LAUNCH((k_history_conv_t<5, 5, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
-                         (const float*)w1f, bias1, (const float*)w2f, bias2, T1, N, tiles_per_b, out);
-        else
-            FBBEV_LAUNCH((k_history_conv_t<1, 1, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
-                         (const float*)w1f, bias1, (const float*)w2f, bias2, T1, N, tiles_per_b, out);
-    } else if (VM)
-        return FBBEV_E_UNSUPPORTED;
-    else
-        FBBEV_LAUNCH(k_history_conv<ET>, blocks, 256, lds, stream, feats, feats_stride_b, w1, bias1, w2, bias2,
-                     T1, C, Cout, N, tiles_per_b, out);
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int fbbev_history_conv_e(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                    const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                    float* out, void* workspace, size_t workspace_bytes, int elem_type,
-                                    fbbev_stream_t stream_) {
-    if (B < 0 || T1 <= 0 || C <= 0 || Cout <= 0 || N < 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (B == 0 || N == 0) return 0;
-    if (!feats || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (C % 16 != 0 || Cout % 16 != 0 || C > 16 * FBBEV_HC_MAX_TILES || Cout > 16 * FBBEV_HC_MAX_TILES)
-        return FBBEV_E_UNSUPPORTED;
-    if (feats_stride_b == 0) feats_stride_b = (long long)T1 * C * N;
-    if (feats_stride_b < (long long)T1 * C * N) return FBBEV_E_BADARG;
-    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;                                  // 16-byte bias loads
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    if (elem_type == 0) return history_conv_launch<0>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-    if (elem_type == 1) return history_conv_launch<1>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-    return history_conv_launch<2>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-}
-
-// bf16-MFMA variant of the two fused convolutions (operands rounded to bf16, fp32 accumulate): C = Cout = 80 or 16
-template <int ET, bool VM>
-static int history_conv_bf16_launch(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                    const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                    float* out, void* workspace, size_t workspace_bytes, fbbev_rt_stream stream) {
-    const int tiles_per_b = (N + 63) / 64;
-    const long long blocks = (long long)B * tiles_per_b;
-    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int MT1 = C / 16, MT2 = Cout / 16, KS = (C + 31) / 32;
-    const size_t need = ((size_t)MT1 * KS + (size_t)T1 * MT2 * KS) * 64 * 8 * sizeof(unsigned short);
-    if (!workspace || !aligned16(workspace) || workspace_bytes < need) return FBBEV_E_WORKSPACE;
-    unsigned short* w1f = static_cast<unsigned short*>(workspace);
-    unsigned short* w2f = w1f + (size_t)MT1 * KS * 64 * 8;
-    const int nfrag = (MT1 * KS + T1 * MT2 * KS) * 64;
-    FBBEV_LAUNCH(k_history_weight_fragments_bf16, (nfrag + 255) / 256, 256, 0, stream, w1, w2, MT1, MT2, C, T1, w1f);
-    const size_t a2s = (size_t)((MT2 * KS * 64 + 255) / 256) * 256 * 8;                                 // padded staging buffer
-    size_t lds = (2 * a2s + (size_t)4 * 16 * (KS * 32 + 8)) * sizeof(unsigned short);           // W2_t x 2 + Y rows
-    static const size_t conv_pad = (size_t)fbbev_env_int("FBBEV_HISTORY_CONV_LDS_PAD_KB", 0) * 1024;   // occupancy experiment knob
-    if (conv_pad > lds) lds = conv_pad;
-    if (C == 80)
-        FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16<5, 5, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
-                             (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, T1, N, tiles_per_b, out);
-    else
-        FBBEV_LAUNCH((k_history_conv_bf16<1, 1, ET, VM>), blocks, 256, lds, stream, feats, feats_stride_b,
-                     (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, T1, N, tiles_per_b, out);
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int fbbev_history_conv_bf16(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                       const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                       float* out, void* workspace, size_t workspace_bytes, int voxel_major, int elem_type,
-                                       fbbev_stream_t stream_) {
-    if (B < 0 || T1 <= 0 || C <= 0 || Cout <= 0 || N < 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (voxel_major != 0 && voxel_major != 1) return FBBEV_E_BADARG;
-    if (B == 0 || N == 0) return 0;
-    if (!feats || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (!((C == 80 && Cout == 80) || (C == 16 && Cout == 16))) return FBBEV_E_UNSUPPORTED;
-    if (feats_stride_b == 0) feats_stride_b = (long long)T1 * C * N;
-    if (feats_stride_b < (long long)T1 * C * N) return FBBEV_E_BADARG;
-    if (voxel_major && (!aligned16(feats) || feats_stride_b % 8 != 0)) return FBBEV_E_UNSUPPORTED;   // 16-byte row pieces
-    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;                                              // 16-byte bias loads
-    if (voxel_major && (long long)N * C * (elem_type == 0 ? 4 : 2) >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;   // 32-bit byte offsets in a frame
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-#define FBBEV_HCB(ET_, VM_) history_conv_bf16_launch<ET_, VM_>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream)
-    if (voxel_major) return elem_type == 0 ? FBBEV_HCB(0, true) : elem_type == 1 ? FBBEV_HCB(1, true) : FBBEV_HCB(2, true);
-    return elem_type == 0 ? FBBEV_HCB(0, false) : elem_type == 1 ? FBBEV_HCB(1, false) : FBBEV_HCB(2, false);
-#undef FBBEV_HCB
-}
-
-// fp32-grade convolutions on the 16-bit MFMAs (split operands, history_conv_x3_kernels.h): voxel-major 16-bit ring
-struct fbbev_conv_x3_plan { unsigned short* w1x; unsigned short* w2x; float* biasx; size_t pieces, part1; };
-
-static int history_conv_x3_prepare(const void* feats, long long& feats_stride_b, const float* w1, const float* bias1, const float* w2,
-                                   const float* bias2, int B, int T1, int C, int Cout, int N, float* out, void* workspace,
-                                   size_t workspace_bytes, int elem_type, fbbev_rt_stream stream, fbbev_conv_x3_plan& pl) {
-    if (B < 0 || T1 <= 0 || C <= 0 || Cout <= 0 || N < 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (B == 0 || N == 0) return 0;
-    if (!feats || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (!((C == 80 && Cout == 80) || (C == 16 && Cout == 16)) || elem_type == 0) return FBBEV_E_UNSUPPORTED;
-    if (feats_stride_b == 0) feats_stride_b = (long long)T1 * C * N;
-    if (feats_stride_b < (long long)T1 * C * N) return FBBEV_E_BADARG;
-    if (!aligned16(feats) || feats_stride_b % 8 != 0 || !aligned16(bias1)) return FBBEV_E_UNSUPPORTED;
-    if ((long long)N * C * 2 >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;                          // 32-bit byte offsets in a frame
-    const int MT = C / 16, KS = (C + 31) / 32;
-    const size_t part1 = (size_t)MT * KS * 64 * 8, part2 = part1;
-    const size_t wbytes = (2 * part1 + (size_t)T1 * 2 * part2) * sizeof(unsigned short);
-    const size_t need = wbytes + (size_t)B * T1 * C * sizeof(float);
-    if (!workspace || !aligned16(workspace) || workspace_bytes < need) return FBBEV_E_WORKSPACE;
-    pl.w1x = static_cast<unsigned short*>(workspace);
-    pl.w2x = pl.w1x + 2 * part1;
-    pl.biasx = reinterpret_cast<float*>(static_cast<char*>(workspace) + wbytes);
-    const long long nprep = (long long)(MT * KS + T1 * MT * KS) * 64 + (long long)B * T1 * C;
-    if (nprep >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (elem_type == 1)
-        FBBEV_LAUNCH(k_history_weight_fragments_bf16x3<1>, (nprep + 255) / 256, 256, 0, stream, w1, w2, bias1, MT, MT, C, T1, B * T1, pl.w1x, pl.biasx);
-    else
-        FBBEV_LAUNCH(k_history_weight_fragments_bf16x3<2>, (nprep + 255) / 256, 256, 0, stream, w1, w2, bias1, MT, MT, C, T1, B * T1, pl.w1x, pl.biasx);
-    FBBEV_CHECK_LAUNCH();
-    pl.pieces = 2 * part2 / 8 + C / 4;
-    pl.part1 = part1;
-    return 0;
-}
-
-// n_seg segments of seg_len voxels, seg_stride apart from voxel seg0 on, in every sample (one segment of N voxels: the whole volume)
-static int history_conv_x3_segments(const void* feats, long long feats_stride_b, const float* bias2, int B, int T1, int C, int N,
-                                    float* out, int elem_type, const fbbev_conv_x3_plan& pl, int seg0, int seg_stride, int seg_len,
-                                    int n_seg, int nw, fbbev_rt_stream stream) {
-    if (seg_len <= 0 || n_seg <= 0) return 0;
-    const int nt = 64 * nw;                                       // nw = 8: a workgroup fills a CU's registers; 4: half of them (the pipelined step)
-    const int tile_voxels = 16 * nw * FBBEV_HX3_NV;
-    const int tiles_per_seg = (seg_len + tile_voxels - 1) / tile_voxels;
-    const long long tiles_per_b = (long long)tiles_per_seg * n_seg;
-    const long long blocks = (long long)B * tiles_per_b;
-    if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    // one frame per workgroup barrier (FPB = 2, four W2 buffers: measured 2 % slower, profiles/r06_exp_history_step.md)
-    const size_t lds = ((size_t)2 * ((pl.pieces + nt - 1) / nt) * nt * 8 + 2 * pl.part1) * sizeof(unsigned short);
-#define FBBEV_HX3(MT_, ET_, PF_, NW_, FPB_)                                                                                            \
-    FBBEV_LAUNCH_DYN_LDS((k_history_conv_bf16x3<MT_, MT_, ET_, PF_, NW_, FPB_>), blocks, 64 * NW_, lds, stream, feats, feats_stride_b, \
-                         (const unsigned short*)pl.w1x, (const float*)pl.biasx, (const unsigned short*)pl.w2x, bias2, T1, N,           \
-                         (int)tiles_per_b, out, seg0, seg_stride, seg_len, tiles_per_seg)
-    /* two frames of X in flight: three spill (256 registers at 2 waves / SIMD) */
-#define FBBEV_HX3P(MT_, ET_) do { if (nw == 4) FBBEV_HX3(MT_, ET_, 2, 4, 1); else FBBEV_HX3(MT_, ET_, 2, 8, 1); } while (0)
-    if (C == 80) { if (elem_type == 1) FBBEV_HX3P(5, 1); else FBBEV_HX3P(5, 2); }
-    else { if (elem_type == 1) FBBEV_HX3P(1, 1); else FBBEV_HX3P(1, 2); }
-#undef FBBEV_HX3P
-#undef FBBEV_HX3
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int fbbev_history_conv_bf16x3(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                         const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                         float* out, void* workspace, size_t workspace_bytes, int elem_type,
-                                         fbbev_stream_t stream_) {
-    fbbev_conv_x3_plan pl{};
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    const int e = history_conv_x3_prepare(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace,
-                                          workspace_bytes, elem_type, stream, pl);
-    if (e || B <= 0 || N <= 0) return e;
-    static const int nw = fbbev_env_int("FBBEV_HX3_WAVES", 8) == 4 ? 4 : 8;     // tuning: 256-thread workgroups
-    return history_conv_x3_segments(feats, feats_stride_b, bias2, B, T1, C, N, out, elem_type, pl, 0, 0, N, 1, nw, stream);
-}
-
-// One history step on a 16-bit voxel-major ring as ONE kernel (history_fused_x3_kernels.h): every MFMA wave warps its own operands.
-// next[:, 0] must hold the current frame; writes next[:, 1:] (== fbbev_history_warp_vm) and out (== fbbev_history_conv_bf16x3).
-extern "C" int fbbev_history_fused_x3_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
-                                         const float* rt_flow, const float* w1, const float* bias1, const float* w2,
-                                         const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
-                                         void* workspace, size_t workspace_bytes, int elem_type, fbbev_stream_t stream_) {
-    if (B < 0 || T <= 0 || C <= 0 || Cout <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
-    if (B == 0) return 0;
-    if (!history || !next || !rt_flow || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (C != 80 || Cout != 80 || (elem_type != 1 && elem_type != 2) || Z < 2 || Y < 2 || X < 2) return FBBEV_E_UNSUPPORTED;
-    const long long N = (long long)Z * Y * X, frame = N * C;
-    const int T1 = T + 1;
-    if (history_stride_b == 0) history_stride_b = (long long)T * frame;
-    if (next_stride_b == 0) next_stride_b = (long long)T1 * frame;
-    if (history_stride_b < (long long)T * frame || next_stride_b < (long long)T1 * frame) return FBBEV_E_BADARG;
-    if (history_stride_b % 8 != 0 || next_stride_b % 8 != 0 || !aligned16(history) || !aligned16(next)) return FBBEV_E_UNSUPPORTED;
-    if (frame * 2 >= (1ll << 32) || N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;              // 32-bit byte offsets inside a frame
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    fbbev_conv_x3_plan cp{};
-    long long fs = next_stride_b;
-    if (workspace_bytes < 64) return FBBEV_E_WORKSPACE;
-    int e = history_conv_x3_prepare(next, fs, w1, bias1, w2, bias2, B, T1, C, Cout, (int)N, out, workspace, workspace_bytes - 64, elem_type, stream, cp);
-    if (e) return e;
-    void* dump = static_cast<char*>(workspace) + ((workspace_bytes - 64) & ~(size_t)15);       // 16 bytes nobody reads (the tail of the workspace)
-    const int n_xt = (X + 15) / 16, n_yt = (Y + 7) / 8;           // bricks of 16 x 8 voxels of one z plane, z fastest
-    const long long blocks = (long long)B * n_yt * n_xt * Z;
-    if (blocks >= (1ll << 31) - 8) return FBBEV_E_UNSUPPORTED;
-    const int per_xcd = (int)((blocks + 7) / 8);
-    // two W2 / bias blocks + W1 (hi | lo) + two operand tiles [128 voxels][FBBEV_HFX_PITCH] + the voxel table [128][16 dwords]: 154 KB
-    const size_t lds = ((size_t)2 * ((cp.pieces + 511) / 512) * 512 * 8 + 2 * cp.part1 + (size_t)2 * 128 * FBBEV_HFX_PITCH) * sizeof(unsigned short) +
-                       (size_t)128 * 16 * sizeof(unsigned int);
-#define FBBEV_HFX(ET_)                                                                                                   \
-    FBBEV_LAUNCH_DYN_LDS((k_history_fused_x3<ET_>), (long long)per_xcd * 8, 512, lds, stream, history, history_stride_b, \
-                         next, next_stride_b, rt_flow, (const unsigned short*)cp.w1x, (const float*)cp.biasx,            \
-                         (const unsigned short*)cp.w2x, bias2, T1, Z, Y, X, n_xt, n_yt, per_xcd, (int)blocks, out, dump)
-    if (elem_type == 1) FBBEV_HFX(1); else FBBEV_HFX(2);
-#undef FBBEV_HFX
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-// One history step on a 16-bit voxel-major ring as a two-stream pipeline: the warp of a band of grid rows into next[:, 1:] on the
-// caller's stream, the split-operand convolutions of the band before it on a second stream -- a bandwidth-bound gather kernel and
-// an MFMA-bound one that leave each other's resource idle when they run back to back.  next[:, 0] must hold the current frame.
-// The same kernels, operands and results as fbbev_history_warp_vm + fbbev_history_conv_bf16x3, bit for bit.
-struct fbbev_side_stream { fbbev_rt_stream stream; fbbev_rt_event ev[2 + 64]; bool ok; };
-
-static fbbev_side_stream* history_side_stream() {
-    static fbbev_side_stream table[16];
-    static bool made[16];
-    const int d = fbbev_rt_device();
-    if (d < 0 || d >= 16) return nullptr;
-    static std::mutex mu;                                    // (first use from two host threads; the stream and its events are per DEVICE:
-    std::lock_guard<std::mutex> lock(mu);                    //  callers serialise their calls per device, as with any stream-ordered workspace)
-    if (!made[d]) {
-        made[d] = true;
-        // the convolutions' stream is created at the device's highest priority: built to let their workgroups in ahead of the thousands
-        // of queued warp workgroups -- measured: no effect on the dispatch (profiles/r06_exp_history_step.md).
-        // FBBEV_HISTORY_STEP_PRIORITY=0: equal priorities
-        table[d].ok = fbbev_rt_stream_create(&table[d].stream, fbbev_env_int("FBBEV_HISTORY_STEP_PRIORITY", 1) == 0 ? 0 : 1) == 0;
-        for (int i = 0; i < 2 + 64 && table[d].ok; ++i) table[d].ok = fbbev_rt_event_create(&table[d].ev[i]) == 0;
-    }
-    return table[d].ok ? &table[d] : nullptr;
-}
-
-extern "C" int fbbev_history_step_x3_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
-                                        const float* rt_flow, const float* w1, const float* bias1, const float* w2,
-                                        const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
-                                        void* workspace, size_t workspace_bytes, int elem_type, int chunks,
-                                        fbbev_stream_t stream_) {
-    if (B < 0 || T <= 0 || C <= 0 || Cout <= 0 || Z <= 0 || Y <= 0 || X <= 0 || chunks < 0 || chunks > 64) return FBBEV_E_BADARG;
-    if (B == 0) return 0;
-    if (!history || !next || !rt_flow || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (elem_type != 1 && elem_type != 2) return FBBEV_E_UNSUPPORTED;
-    const long long N = (long long)Z * Y * X, frame = N * C;
-    if (N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int T1 = T + 1;
-    if (next_stride_b == 0) next_stride_b = (long long)T1 * frame;
-    if (next_stride_b < (long long)T1 * frame) return FBBEV_E_BADARG;
-    const int esz = 2;
-    void* warped = static_cast<char*>(next) + frame * esz;                                       // next[:, 1:]
-    fbbev_warp_vm_plan wp{};
-    long long hs = history_stride_b, ns = next_stride_b;
-    int e = history_warp_vm_plan(history, hs, rt_flow, B, T, C, Z, Y, X, warped, ns, elem_type, wp);
-    if (e) return e;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    fbbev_conv_x3_plan cp{};
-    long long fs = next_stride_b;
-    e = history_conv_x3_prepare(next, fs, w1, bias1, w2, bias2, B, T1, C, Cout, (int)N, out, workspace, workspace_bytes, elem_type, stream, cp);
-    if (e) return e;
-    if (chunks == 0) chunks = 10;
-    // the convolutions of the pipeline in 256-thread workgroups: half a CU's registers, so that warp waves share the CU with them
-    static const int step_nw = fbbev_env_int("FBBEV_HISTORY_STEP_WAVES", 4) == 8 ? 8 : 4;
-    if (chunks > wp.nyb) chunks = wp.nyb;
-    fbbev_side_stream* side = chunks > 1 ? history_side_stream() : nullptr;
-    if (!side) {                                                                                  // one chunk: the two kernels back to back
-        e = history_warp_vm_bands(history, hs, rt_flow, B, T, C, Z, Y, X, warped, ns, elem_type, wp, 0, wp.nyb, stream);
-        if (e) return e;
-        return history_conv_x3_segments(next, fs, bias2, B, T1, C, (int)N, out, elem_type, cp, 0, 0, (int)N, 1, 8, stream);
-    }
-#define FBBEV_RT(x) do { const int e_ = (x); if (e_) return e_; } while (0)
-    FBBEV_RT(fbbev_rt_event_record(side->ev[0], stream));
-    FBBEV_RT(fbbev_rt_stream_wait(side->stream, side->ev[0]));
-    for (int i = 0; i < chunks; ++i) {
-        const int yb0 = (int)((long long)wp.nyb * i / chunks), yb1 = (int)((long long)wp.nyb * (i + 1) / chunks);
-        e = history_warp_vm_bands(history, hs, rt_flow, B, T, C, Z, Y, X, warped, ns, elem_type, wp, yb0, yb1 - yb0, stream);
-        if (e) return e;
-        FBBEV_RT(fbbev_rt_event_record(side->ev[2 + i], stream));
-        FBBEV_RT(fbbev_rt_stream_wait(side->stream, side->ev[2 + i]));
-        const int y0 = yb0 * wp.YB, y1 = yb1 * wp.YB < Y ? yb1 * wp.YB : Y;
-        e = history_conv_x3_segments(next, fs, bias2, B, T1, C, (int)N, out, elem_type, cp, y0 * X, Y * X, (y1 - y0) * X, Z, step_nw, side->stream);
-        if (e) return e;
-    }
-    FBBEV_RT(fbbev_rt_event_record(side->ev[1], side->stream));
-    FBBEV_RT(fbbev_rt_stream_wait(stream, side->ev[1]));
-#undef FBBEV_RT
     return 0;
 }
 
@@ -3623,84 +3774,6 @@ extern "C" int fbbev_rows_tail_ffn_x3_planes(const float* x, long long x_row_str
     return rows_tail_ffn_x3_impl(x, x_row_stride, w0_fragments, b0, residual0, residual0_row_stride, ln0_weight, ln0_bias, ln0_eps,
                                  w1_fragments, b1, w2_fragments, b2, rows, embed, hidden, ln1_weight, ln1_bias, ln1_eps, out, 0,
                                  tokens_per_image, stream_);
-}
-
-// Warp + new ring + both convolutions in ONE kernel (k_history_fused_bf16): history (B,T,N,C) -> next ring slots 1..T of
-// `next` (B,T+1,N,C) (slot 0 = the current frame, stored by the caller with fbbev_history_frame_vm BEFORE this call) and
-// out (B,Cout,N) = relu(bias2 + sum_t w2_t . relu(w1 . x_t + bias1_t)) over the T+1 frames of `next`, bf16 MFMA.
-extern "C" int fbbev_history_fused_vm(const void* history, long long history_stride_b, void* next, long long next_stride_b,
-                                      const float* rt_flow, const float* w1, const float* bias1, const float* w2,
-                                      const float* bias2, int B, int T, int C, int Cout, int Z, int Y, int X, float* out,
-                                      void* workspace, size_t workspace_bytes, int elem_type, fbbev_stream_t stream_) {
-    if (B < 0 || T <= 0 || C <= 0 || Cout <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
-    if (B == 0) return 0;
-    if (!history || !next || !rt_flow || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (C != 80 || Cout != 80 || (elem_type != 1 && elem_type != 2) || Z < 2 || Y < 2 || X < 2) return FBBEV_E_UNSUPPORTED;
-    const long long N = (long long)Z * Y * X, frame = N * C;
-    const int T1 = T + 1;
-    if (history_stride_b == 0) history_stride_b = (long long)T * frame;
-    if (next_stride_b == 0) next_stride_b = (long long)T1 * frame;
-    if (history_stride_b < (long long)T * frame || next_stride_b < (long long)T1 * frame) return FBBEV_E_BADARG;
-    if (history_stride_b % 8 != 0 || next_stride_b % 8 != 0 || !aligned16(history) || !aligned16(next) || !aligned16(bias1))
-        return FBBEV_E_UNSUPPORTED;
-    if (frame * 2 >= (1ll << 32) || N >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;              // 32-bit byte offsets inside a frame
-    constexpr int MT = 5, KS = 3;
-    const size_t need = ((size_t)MT * KS + (size_t)T1 * MT * KS) * 64 * 8 * sizeof(unsigned short);
-    if (!workspace || !aligned16(workspace) || workspace_bytes < need) return FBBEV_E_WORKSPACE;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    unsigned short* w1f = static_cast<unsigned short*>(workspace);
-    unsigned short* w2f = w1f + (size_t)MT * KS * 64 * 8;
-    const int nfrag = (MT * KS + T1 * MT * KS) * 64;
-    FBBEV_LAUNCH(k_history_weight_fragments_bf16, (nfrag + 255) / 256, 256, 0, stream, w1, w2, MT, MT, C, T1, w1f);
-    FBBEV_CHECK_LAUNCH();
-    const int n_xc = (X + 63) / 64;                               // 64-voxel tiles per grid row
-    int YB = 128 / Z;                                             // (z, y) slabs per x chunk, as the warp kernel orders its workgroups
-    if (YB < 1) YB = 1;
-    if (YB > Y) YB = Y;
-    const int nyb = (Y + YB - 1) / YB;
-    const long long blocks = (long long)B * nyb * n_xc * YB * Z;
-    if (blocks >= (1ll << 31) - 8) return FBBEV_E_UNSUPPORTED;
-    const int per_xcd = (int)((blocks + 7) / 8);
-    constexpr int A2S = ((MT * KS * 64 + 255) / 256) * 256 * 8;
-    // 4 W2 buffers + the W1 fragments + the Y rows + 4 operand tiles: 137 KB (one 1024-thread workgroup per CU)
-    const size_t lds = ((size_t)4 * A2S + (size_t)MT * KS * 64 * 8 + (size_t)4 * 16 * (KS * 32 + 8) + (size_t)4 * 64 * FBBEV_HF_XP) *
-                       sizeof(unsigned short) + (size_t)4 * 80 * sizeof(float);
-#define FBBEV_HF(ET_)                                                                                                        \
-    FBBEV_LAUNCH_DYN_LDS((k_history_fused_bf16<ET_>), (long long)per_xcd * 8, 1024, lds, stream, history, history_stride_b,  \
-                         next, next_stride_b, rt_flow, (const unsigned short*)w1f, bias1, (const unsigned short*)w2f, bias2, \
-                         T1, Z, Y, X, n_xc, YB, nyb, per_xcd, (int)blocks, out)
-    if (elem_type == 1) FBBEV_HF(1); else FBBEV_HF(2);
-#undef FBBEV_HF
-    FBBEV_CHECK_LAUNCH();
-    return 0;
-}
-
-// the fp32-MFMA convolutions on a voxel-major ring (feats (B, T1, N, C)); C = Cout in {16, 80}, workspace required
-extern "C" int fbbev_history_conv_vm(const void* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                     const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                     float* out, void* workspace, size_t workspace_bytes, int elem_type,
-                                     fbbev_stream_t stream_) {
-    if (B < 0 || T1 <= 0 || C <= 0 || Cout <= 0 || N < 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (B == 0 || N == 0) return 0;
-    if (!feats || !w1 || !bias1 || !w2 || !bias2 || !out) return FBBEV_E_BADARG;
-    if (!((C == 80 && Cout == 80) || (C == 16 && Cout == 16))) return FBBEV_E_UNSUPPORTED;
-    if (!workspace) return FBBEV_E_WORKSPACE;
-    if (feats_stride_b == 0) feats_stride_b = (long long)T1 * C * N;
-    if (feats_stride_b < (long long)T1 * C * N) return FBBEV_E_BADARG;
-    if (!aligned16(feats) || feats_stride_b % 8 != 0) return FBBEV_E_UNSUPPORTED;                      // 8- / 16-byte row pieces
-    if ((long long)N * C * (elem_type == 0 ? 4 : 2) >= (1ll << 32)) return FBBEV_E_UNSUPPORTED;        // 32-bit byte offsets in a frame
-    if (!aligned16(bias1)) return FBBEV_E_UNSUPPORTED;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    if (elem_type == 0) return history_conv_launch<0, true>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-    if (elem_type == 1) return history_conv_launch<1, true>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-    return history_conv_launch<2, true>(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace, workspace_bytes, stream);
-}
-
-extern "C" int fbbev_history_conv(const float* feats, long long feats_stride_b, const float* w1, const float* bias1,
-                                  const float* w2, const float* bias2, int B, int T1, int C, int Cout, int N,
-                                  float* out, void* workspace, size_t workspace_bytes, fbbev_stream_t stream_) {
-    return fbbev_history_conv_e(feats, feats_stride_b, w1, bias1, w2, bias2, B, T1, C, Cout, N, out, workspace,
-                                workspace_bytes, 0, stream_);
 }
 
 static int conv3d_launch(const float* x, const float* weight_fragments, const float* bias, const float* residual, int B,

@@ -531,3 +531,527 @@ def test_da_cross_attn_entries_keep_their_error_codes_and_plan_sizes():
     s = shapes['configs2']
     assert lib.fbbev_da_cross_attn_fwd_zt_fuses_softmax(*(s[k] for k in functions['fwd_zt_fuses_softmax'][:9]), 1, 12) == 0
     assert lib.fbbev_da_cross_attn_fwd_zt_fuses_softmax(*(s[k] for k in functions['fwd_zt_fuses_softmax'][:9]), 5, 0) == 0
+
+
+# ---- the temporal-history family (and the three LayerNorm entries that share its region): one table per entry, recorded on the
+# launchers before they shared a ring record
+H_RING = ['history', 'history_stride_b', 'rt_flow', 'B']
+H_CONV = ['feats', 'feats_stride_b', 'w1', 'bias1', 'w2', 'bias2', 'B', 'T1', 'C', 'Cout', 'N', 'out', 'workspace', 'workspace_bytes']
+H_STEP = ['history', 'history_stride_b', 'next', 'next_stride_b', 'rt_flow', 'w1', 'bias1', 'w2', 'bias2', 'B', 'T', 'C', 'Cout',
+          'Z', 'Y', 'X', 'out', 'workspace', 'workspace_bytes', 'elem_type']
+H_PARAMS = {
+    'history_flow': ['history_forward_augs', 'curr_to_prev_ego_rt', 'bda', 'dx3', 'lower3', 'B', 'rt_flow', 'stream'],
+    'history_stream_prologue': ['flags', 'curr_to_prev_ego_rt', 'bda', 'b1', 'wt', 'dx3', 'lower3', 'freq', 'B', 'T', 'C',
+                                'history_forward_augs', 'sweep_time', 'flow_augs', 'rt_flow', 'bias1', 'stream'],
+    'history_warp': H_RING + ['CH', 'Z', 'Y', 'X', 'out', 'out_stride_b', 'stream'],
+    'history_warp_e': H_RING + ['CH', 'Z', 'Y', 'X', 'out', 'out_stride_b', 'elem_type', 'stream'],
+    'history_warp_vm': H_RING + ['T', 'C', 'Z', 'Y', 'X', 'out', 'out_stride_b', 'elem_type', 'stream'],
+    'history_warp_vm_src': ['history', 'history_stride_b', 'curr', 'curr_stride_b', 'flags', 'rt_flow', 'B', 'T', 'C', 'Z', 'Y', 'X',
+                            'out', 'out_stride_b', 'elem_type', 'stream'],
+    'history_frame_vm': ['curr', 'B', 'C', 'N', 'inner', 'out', 'out_stride_b', 'elem_type', 'stream'],
+    'history_conv': H_CONV + ['stream'],
+    'history_conv_e': H_CONV + ['elem_type', 'stream'],
+    'history_conv_vm': H_CONV + ['elem_type', 'stream'],
+    'history_conv_bf16': H_CONV + ['voxel_major', 'elem_type', 'stream'],
+    'history_conv_bf16x3': H_CONV + ['elem_type', 'stream'],
+    'history_fused_x3_vm': H_STEP + ['stream'],
+    'history_step_x3_vm': H_STEP + ['chunks', 'stream'],
+    'history_fused_vm': H_STEP + ['stream'],
+    'layernorm': ['x', 'residual', 'weight', 'bias', 'eps', 'rows', 'C', 'out', 'stream'],
+    'layernorm_bwd': ['x', 'grad_out', 'weight', 'eps', 'rows', 'C', 'grad_x', 'partial', 'stream'],
+}
+# a call that would LAUNCH (so no row below is this alone): one sample, a bf16 ring of 16 frames (17 with the current one) of 80
+# channels on an 8 x 8 x 8 grid, dense strides, a workspace of any size; every pointer non-null and 16-byte aligned
+H_BASE = dict(B=1, T=16, T1=17, C=80, Cout=80, CH=80, Z=8, Y=8, X=8, N=512, inner=1, elem_type=1, voxel_major=1, chunks=0,
+              history_stride_b=0, next_stride_b=0, out_stride_b=0, curr_stride_b=0, feats_stride_b=0, workspace_bytes=1 << 40,
+              freq=0.5, eps=1e-5, rows=256, stream=DA_NULL)
+H_FRAME = 512 * 80                                                   # elements of a frame of H_BASE
+# grids at the limits of the 32-bit offsets (no pointer is dereferenced in these rows, so the sizes are free)
+H_2G_VOXELS = dict(Z=2048, Y=1024, X=1024)                           # 2^31 voxels
+H_BELOW_2G = dict(Z=2047, Y=1024, X=1024)
+H_C80_AT_4G = dict(Z=2, Y=2, X=6710887)                              # 16-bit frames of 80 channels: 2^32 bytes lie between these two
+H_C80_BELOW_4G = dict(Z=2, Y=2, X=6710886)
+H_C8_AT_4G = dict(C=8, Z=16, Y=4096, X=4096)                         # 16-bit frames of 8 channels: exactly 2^32 bytes
+H_C8_BELOW_4G = dict(C=8, Z=16, Y=4096, X=4095)
+H_C8_F32_AT_4G = dict(C=8, elem_type=0, Z=8, Y=4096, X=4096)         # fp32 frames of 8 channels: exactly 2^32 bytes
+H_C8_F32_BELOW_4G = dict(C=8, elem_type=0, Z=8, Y=4096, X=4095)
+
+
+def h_call(lib, entry, case):
+    """`entry` with H_BASE's operands, `case` on top of them; 'null': every pointer the entry takes is null unless `case` names it"""
+    case = dict(case)
+    null = case.pop('null', False)
+    args = []
+    for name in H_PARAMS[entry]:
+        if name in case:
+            args.append(case.pop(name))
+        elif name in H_BASE:
+            args.append(H_BASE[name])
+        else:
+            args.append(DA_NULL if null else DA_P16)
+    assert not case, (entry, 'operands the entry does not take', case)
+    return getattr(lib, 'fbbev_' + entry)(*args)
+
+
+def test_history_entries_keep_their_error_codes():
+    """Every entry of the temporal-history family: the code of each argument check, and which code wins where two defects
+    coincide (the order of an entry's checks is part of the ABI).  Every row returns BEFORE any runtime call, so this runs
+    without a GPU.  Checks behind a launch (the workgroup counts of the x3 convolutions' segments and of the one-kernel steps)
+    are not here."""
+    lib = _capi.declare(ctypes.CDLL(_capi.LIB_PATH))
+    NULL, P16, P8 = DA_NULL, DA_P16, DA_P8
+    F = H_FRAME
+    dx3 = (ctypes.c_float * 3)(0.4, 0.4, 0.4)                       # flow / stream_prologue read dx3 on the host
+    dx3_zero = (ctypes.c_float * 3)(0.4, 0.0, 0.4)
+    dx3_nan = (ctypes.c_float * 3)(0.4, 0.4, float('nan'))
+    many_wgs = dict(B=1 << 26, N=2048)                               # 2^31 workgroups of 64 voxels
+    table = [
+        # ---- fbbev_history_flow: B, empty (0), pointers, voxel sizes
+        ('history_flow', dict(dx3=dx3, B=-1), -1),
+        ('history_flow', dict(B=0, null=True), 0),
+        ('history_flow', dict(B=-1, null=True), -1),
+        ('history_flow', dict(dx3=dx3, rt_flow=NULL), -1),
+        ('history_flow', dict(dx3=dx3, bda=NULL), -1),
+        ('history_flow', dict(dx3=dx3, lower3=NULL), -1),
+        ('history_flow', dict(dx3=NULL), -1),
+        ('history_flow', dict(dx3=dx3_zero), -1),
+        ('history_flow', dict(dx3=dx3_nan), -1),
+        ('history_flow', dict(dx3=dx3_zero, B=0), 0),
+        # ---- fbbev_history_stream_prologue: dimensions, empty (0), pointers (sweep_time only with frames), voxel sizes, T > 8192 (-2)
+        ('history_stream_prologue', dict(dx3=dx3, B=-1), -1),
+        ('history_stream_prologue', dict(dx3=dx3, T=-1), -1),
+        ('history_stream_prologue', dict(dx3=dx3, C=0), -1),
+        ('history_stream_prologue', dict(B=0, null=True), 0),
+        ('history_stream_prologue', dict(B=0, C=0, null=True), -1),
+        ('history_stream_prologue', dict(dx3=dx3, flags=NULL), -1),
+        ('history_stream_prologue', dict(dx3=dx3, bias1=NULL), -1),
+        ('history_stream_prologue', dict(dx3=dx3, wt=NULL), -1),
+        ('history_stream_prologue', dict(dx3=dx3, sweep_time=NULL), -1),
+        ('history_stream_prologue', dict(dx3=NULL), -1),
+        ('history_stream_prologue', dict(dx3=dx3_zero), -1),
+        ('history_stream_prologue', dict(dx3=dx3, T=8193), -2),
+        ('history_stream_prologue', dict(dx3=dx3_zero, T=8193), -1),
+        ('history_stream_prologue', dict(dx3=dx3, T=8193, sweep_time=NULL), -1),
+        ('history_stream_prologue', dict(dx3=dx3_nan, T=0, sweep_time=NULL), -1),
+        # ---- fbbev_history_warp_e / _warp: planes (B, CH, Z, Y, X); axes < 2 are BADARG here; no alignment rule
+        ('history_warp_e', dict(B=-1), -1),
+        ('history_warp_e', dict(CH=-1), -1),
+        ('history_warp_e', dict(Z=1), -1),
+        ('history_warp_e', dict(Y=1), -1),
+        ('history_warp_e', dict(X=1), -1),
+        ('history_warp_e', dict(elem_type=3), -1),
+        ('history_warp_e', dict(elem_type=-1), -1),
+        ('history_warp_e', dict(B=0, null=True), 0),
+        ('history_warp_e', dict(CH=0, null=True), 0),
+        ('history_warp_e', dict(B=0, elem_type=3), -1),
+        ('history_warp_e', dict(CH=0, Z=1), -1),
+        ('history_warp_e', dict(history=NULL), -1),
+        ('history_warp_e', dict(rt_flow=NULL), -1),
+        ('history_warp_e', dict(out=NULL), -1),
+        ('history_warp_e', H_2G_VOXELS, -2),
+        ('history_warp_e', dict(H_2G_VOXELS, history=NULL), -1),
+        ('history_warp_e', dict(H_2G_VOXELS, history_stride_b=1), -2),
+        ('history_warp_e', dict(H_BELOW_2G, history_stride_b=1), -1),
+        ('history_warp_e', dict(history_stride_b=F - 1), -1),
+        ('history_warp_e', dict(out_stride_b=F - 1), -1),
+        ('history_warp_e', dict(out_stride_b=F - 1, elem_type=0), -1),
+        ('history_warp_e', dict(H_BELOW_2G, B=256), -2),                       # stride 0 is dense; more workgroups than a grid holds
+        ('history_warp_e', dict(H_BELOW_2G, B=256, out_stride_b=80 * (2047 << 20) - 1), -1),
+        ('history_warp_e', dict(H_BELOW_2G, B=256, history=P8, out_stride_b=80 * (2047 << 20)), -2),
+        ('history_warp', dict(Z=1), -1),
+        ('history_warp', dict(B=0, null=True), 0),
+        ('history_warp', dict(history=NULL), -1),
+        ('history_warp', dict(history_stride_b=F - 1), -1),
+        ('history_warp', H_2G_VOXELS, -2),
+        ('history_warp', dict(H_BELOW_2G, B=256), -2),
+        # ---- fbbev_history_warp_vm: the voxel-major ring (B, T, N, C), rows of 4 (fp32) or 8 (16-bit) elements
+        ('history_warp_vm', dict(B=-1), -1),
+        ('history_warp_vm', dict(T=-1), -1),
+        ('history_warp_vm', dict(C=0), -1),
+        ('history_warp_vm', dict(Z=1), -1),
+        ('history_warp_vm', dict(Y=1), -1),
+        ('history_warp_vm', dict(X=1), -1),
+        ('history_warp_vm', dict(elem_type=3), -1),
+        ('history_warp_vm', dict(elem_type=3, T=0), -1),
+        ('history_warp_vm', dict(B=0, null=True), 0),
+        ('history_warp_vm', dict(T=0, null=True), 0),
+        ('history_warp_vm', dict(history=NULL), -1),
+        ('history_warp_vm', dict(rt_flow=NULL), -1),
+        ('history_warp_vm', dict(out=NULL), -1),
+        ('history_warp_vm', H_2G_VOXELS, -2),
+        ('history_warp_vm', dict(H_2G_VOXELS, out=NULL), -1),
+        ('history_warp_vm', dict(H_2G_VOXELS, history_stride_b=1), -2),
+        ('history_warp_vm', dict(H_BELOW_2G, history_stride_b=1), -1),
+        ('history_warp_vm', dict(history_stride_b=16 * F - 1), -1),
+        ('history_warp_vm', dict(out_stride_b=16 * F - 1), -1),
+        ('history_warp_vm', dict(history_stride_b=16 * F - 1, out=P8), -1),
+        ('history_warp_vm', dict(history=P8, out_stride_b=16 * F - 1), -1),
+        ('history_warp_vm', dict(C=84), -2),
+        ('history_warp_vm', dict(C=84, history_stride_b=1), -1),
+        ('history_warp_vm', dict(C=82, elem_type=0), -2),
+        ('history_warp_vm', dict(history_stride_b=16 * F + 4), -2),
+        ('history_warp_vm', dict(out_stride_b=16 * F + 4, elem_type=2), -2),
+        ('history_warp_vm', dict(history_stride_b=16 * F + 2, elem_type=0), -2),
+        ('history_warp_vm', dict(history=P8), -2),
+        ('history_warp_vm', dict(out=P8), -2),
+        ('history_warp_vm', H_C8_AT_4G, -2),
+        ('history_warp_vm', H_C8_F32_AT_4G, -2),
+        ('history_warp_vm', dict(H_C80_AT_4G, elem_type=2), -2),
+        ('history_warp_vm', dict(B=1 << 25), -2),                              # 2^31 workgroups
+        ('history_warp_vm', dict(B=1 << 25, history_stride_b=16 * F - 1), -1),
+        # ---- fbbev_history_warp_vm_src: warp_vm's checks, then its own operands (the frame past 32-bit offsets is pinned here:
+        # just below it the null `curr` is reached)
+        ('history_warp_vm_src', dict(Z=1), -1),
+        ('history_warp_vm_src', dict(elem_type=3), -1),
+        ('history_warp_vm_src', dict(B=0, null=True), 0),
+        ('history_warp_vm_src', dict(T=0, curr=NULL, flags=NULL), 0),
+        ('history_warp_vm_src', dict(out=NULL), -1),
+        ('history_warp_vm_src', dict(curr=NULL), -1),
+        ('history_warp_vm_src', dict(flags=NULL), -1),
+        ('history_warp_vm_src', dict(curr=NULL, history=P8), -2),
+        ('history_warp_vm_src', dict(curr=NULL, C=84), -2),
+        ('history_warp_vm_src', dict(curr=NULL, history_stride_b=16 * F - 1), -1),
+        ('history_warp_vm_src', dict(H_C8_AT_4G, curr=NULL), -2),
+        ('history_warp_vm_src', dict(H_C8_BELOW_4G, curr=NULL), -1),
+        ('history_warp_vm_src', dict(H_C8_F32_AT_4G, curr=NULL), -2),
+        ('history_warp_vm_src', dict(H_C8_F32_BELOW_4G, curr=NULL), -1),
+        ('history_warp_vm_src', dict(H_C80_AT_4G, flags=NULL), -2),
+        ('history_warp_vm_src', dict(H_C80_BELOW_4G, flags=NULL), -1),
+        ('history_warp_vm_src', dict(H_2G_VOXELS, curr=NULL), -2),
+        ('history_warp_vm_src', dict(curr_stride_b=F - 1), -1),
+        ('history_warp_vm_src', dict(curr_stride_b=F + 4), -2),
+        ('history_warp_vm_src', dict(curr_stride_b=F + 2, elem_type=0), -2),
+        ('history_warp_vm_src', dict(curr=P8), -2),
+        ('history_warp_vm_src', dict(curr=P8, curr_stride_b=F - 1), -1),
+        ('history_warp_vm_src', dict(curr=P8, flags=NULL), -1),
+        ('history_warp_vm_src', dict(B=1 << 25), -2),                          # stride 0 is dense; 2^31 workgroups
+        ('history_warp_vm_src', dict(B=1 << 25, curr_stride_b=F - 1), -1),
+        ('history_warp_vm_src', dict(B=1 << 25, flags=NULL), -1),
+        # ---- fbbev_history_frame_vm: one frame into a ring slot
+        ('history_frame_vm', dict(B=-1), -1),
+        ('history_frame_vm', dict(C=0), -1),
+        ('history_frame_vm', dict(N=-1), -1),
+        ('history_frame_vm', dict(elem_type=3), -1),
+        ('history_frame_vm', dict(inner=0), -1),
+        ('history_frame_vm', dict(inner=3), -1),
+        ('history_frame_vm', dict(B=0, null=True), 0),
+        ('history_frame_vm', dict(N=0, null=True), 0),
+        ('history_frame_vm', dict(N=0, inner=0), -1),
+        ('history_frame_vm', dict(B=0, elem_type=3), -1),
+        ('history_frame_vm', dict(curr=NULL), -1),
+        ('history_frame_vm', dict(out=NULL), -1),
+        ('history_frame_vm', dict(out_stride_b=F - 1), -1),
+        ('history_frame_vm', dict(out_stride_b=F - 1, out=P8), -1),
+        ('history_frame_vm', dict(out_stride_b=F - 1, curr=NULL), -1),
+        ('history_frame_vm', dict(C=84), -2),
+        ('history_frame_vm', dict(C=84, out_stride_b=1), -1),
+        ('history_frame_vm', dict(C=82, elem_type=0), -2),
+        ('history_frame_vm', dict(C=520), -2),
+        ('history_frame_vm', dict(out_stride_b=F + 4), -2),
+        ('history_frame_vm', dict(out_stride_b=F + 2, elem_type=0), -2),
+        ('history_frame_vm', dict(out=P8), -2),
+        ('history_frame_vm', many_wgs, -2),                                    # stride 0 is dense
+        ('history_frame_vm', dict(many_wgs, out_stride_b=2048 * 80 - 1), -1),
+        # ---- fbbev_history_conv_e / _conv: planes (B, T1 * C, N); channels in 16s up to 128; bias1's alignment LAST; the
+        # workspace only where the register-resident kernel runs (C = Cout in {16, 80})
+        ('history_conv_e', dict(B=-1), -1),
+        ('history_conv_e', dict(T1=0), -1),
+        ('history_conv_e', dict(C=0), -1),
+        ('history_conv_e', dict(Cout=0), -1),
+        ('history_conv_e', dict(N=-1), -1),
+        ('history_conv_e', dict(elem_type=3), -1),
+        ('history_conv_e', dict(B=0, null=True), 0),
+        ('history_conv_e', dict(N=0, null=True), 0),
+        ('history_conv_e', dict(B=0, T1=0), -1),
+        ('history_conv_e', dict(feats=NULL), -1),
+        ('history_conv_e', dict(w1=NULL), -1),
+        ('history_conv_e', dict(bias1=NULL), -1),
+        ('history_conv_e', dict(w2=NULL), -1),
+        ('history_conv_e', dict(bias2=NULL), -1),
+        ('history_conv_e', dict(out=NULL), -1),
+        ('history_conv_e', dict(C=40), -2),
+        ('history_conv_e', dict(Cout=40), -2),
+        ('history_conv_e', dict(C=144, Cout=144), -2),
+        ('history_conv_e', dict(C=40, w1=NULL), -1),
+        ('history_conv_e', dict(C=40, feats_stride_b=1), -2),
+        ('history_conv_e', dict(feats_stride_b=17 * F - 1), -1),
+        ('history_conv_e', dict(feats_stride_b=17 * F - 1, bias1=P8), -1),
+        ('history_conv_e', dict(bias1=P8), -2),
+        ('history_conv_e', dict(bias1=P8, workspace_bytes=16), -2),
+        ('history_conv_e', dict(workspace_bytes=16), -3),                      # stride 0 is dense
+        ('history_conv_e', dict(workspace_bytes=16, feats=P8, feats_stride_b=17 * F + 1), -3),   # planes: no alignment rule
+        ('history_conv_e', dict(workspace_bytes=460799), -3),
+        ('history_conv_e', dict(workspace_bytes=18431, C=16, Cout=16, elem_type=0), -3),
+        ('history_conv_e', many_wgs, -2),
+        ('history_conv_e', dict(many_wgs, workspace_bytes=16), -2),
+        ('history_conv', dict(N=-1), -1),
+        ('history_conv', dict(B=0, null=True), 0),
+        ('history_conv', dict(C=40), -2),
+        ('history_conv', dict(feats_stride_b=17 * F - 1), -1),
+        ('history_conv', dict(bias1=P8), -2),
+        ('history_conv', dict(workspace_bytes=16), -3),
+        # ---- fbbev_history_conv_vm: the same arithmetic on a voxel-major ring; the workspace is required and asked for BEFORE the stride
+        ('history_conv_vm', dict(B=-1), -1),
+        ('history_conv_vm', dict(T1=0), -1),
+        ('history_conv_vm', dict(elem_type=3), -1),
+        ('history_conv_vm', dict(B=0, null=True), 0),
+        ('history_conv_vm', dict(N=0, null=True), 0),
+        ('history_conv_vm', dict(N=0, elem_type=3), -1),
+        ('history_conv_vm', dict(out=NULL), -1),
+        ('history_conv_vm', dict(bias2=NULL), -1),
+        ('history_conv_vm', dict(C=32, Cout=32), -2),
+        ('history_conv_vm', dict(Cout=16), -2),
+        ('history_conv_vm', dict(C=32, Cout=32, feats=NULL), -1),
+        ('history_conv_vm', dict(workspace=NULL), -3),
+        ('history_conv_vm', dict(workspace=NULL, C=32, Cout=32), -2),
+        ('history_conv_vm', dict(workspace=NULL, w2=NULL), -1),
+        ('history_conv_vm', dict(workspace=NULL, feats_stride_b=17 * F - 1), -3),
+        ('history_conv_vm', dict(feats_stride_b=17 * F - 1), -1),
+        ('history_conv_vm', dict(feats_stride_b=17 * F - 1, feats=P8), -1),
+        ('history_conv_vm', dict(feats=P8), -2),
+        ('history_conv_vm', dict(feats_stride_b=17 * F + 4), -2),
+        ('history_conv_vm', dict(feats_stride_b=17 * F + 4, elem_type=0), -2),  # rows of 8 elements whatever the type
+        ('history_conv_vm', dict(C=16, Cout=16, N=1 << 27), -2),
+        ('history_conv_vm', dict(C=16, Cout=16, N=(1 << 27) - 1, workspace_bytes=16), -3),
+        ('history_conv_vm', dict(C=16, Cout=16, N=1 << 26, elem_type=0), -2),
+        ('history_conv_vm', dict(C=16, Cout=16, N=(1 << 26) - 1, elem_type=0, workspace_bytes=16), -3),
+        ('history_conv_vm', dict(bias1=P8), -2),
+        ('history_conv_vm', dict(bias1=P8, workspace_bytes=16), -2),
+        ('history_conv_vm', dict(bias1=P8, feats_stride_b=1), -1),
+        ('history_conv_vm', dict(workspace_bytes=16), -3),                     # stride 0 is dense
+        ('history_conv_vm', dict(workspace_bytes=460799), -3),
+        ('history_conv_vm', dict(workspace=P8, workspace_bytes=16), -3),
+        ('history_conv_vm', many_wgs, -2),
+        ('history_conv_vm', dict(many_wgs, workspace_bytes=16), -2),
+        # ---- fbbev_history_conv_bf16: either layout (the flag right after the dimensions); row and 32-bit rules only voxel-major
+        ('history_conv_bf16', dict(B=-1), -1),
+        ('history_conv_bf16', dict(Cout=0), -1),
+        ('history_conv_bf16', dict(elem_type=-1), -1),
+        ('history_conv_bf16', dict(voxel_major=2), -1),
+        ('history_conv_bf16', dict(voxel_major=-1, B=0), -1),
+        ('history_conv_bf16', dict(B=0, null=True), 0),
+        ('history_conv_bf16', dict(N=0, null=True), 0),
+        ('history_conv_bf16', dict(w1=NULL), -1),
+        ('history_conv_bf16', dict(out=NULL), -1),
+        ('history_conv_bf16', dict(C=32, Cout=32), -2),
+        ('history_conv_bf16', dict(C=16), -2),
+        ('history_conv_bf16', dict(C=32, Cout=32, bias2=NULL), -1),
+        ('history_conv_bf16', dict(C=32, Cout=32, feats_stride_b=1), -2),
+        ('history_conv_bf16', dict(feats_stride_b=17 * F - 1), -1),
+        ('history_conv_bf16', dict(feats_stride_b=17 * F - 1, voxel_major=0), -1),
+        ('history_conv_bf16', dict(feats_stride_b=17 * F - 1, feats=P8), -1),
+        ('history_conv_bf16', dict(feats=P8), -2),
+        ('history_conv_bf16', dict(feats_stride_b=17 * F + 4), -2),
+        ('history_conv_bf16', dict(feats_stride_b=17 * F + 4, elem_type=0), -2),
+        ('history_conv_bf16', dict(feats=P8, feats_stride_b=17 * F + 1, voxel_major=0, workspace=NULL), -3),
+        ('history_conv_bf16', dict(bias1=P8), -2),
+        ('history_conv_bf16', dict(bias1=P8, voxel_major=0), -2),
+        ('history_conv_bf16', dict(bias1=P8, workspace=NULL), -2),
+        ('history_conv_bf16', dict(bias1=P8, feats_stride_b=1), -1),
+        ('history_conv_bf16', dict(C=16, Cout=16, N=1 << 27), -2),
+        ('history_conv_bf16', dict(C=16, Cout=16, N=(1 << 27) - 1, workspace=NULL), -3),
+        ('history_conv_bf16', dict(C=16, Cout=16, N=1 << 27, voxel_major=0, workspace=NULL), -3),
+        ('history_conv_bf16', dict(C=16, Cout=16, N=1 << 26, elem_type=0), -2),
+        ('history_conv_bf16', dict(C=16, Cout=16, N=(1 << 26) - 1, elem_type=0, workspace=NULL), -3),
+        ('history_conv_bf16', dict(workspace=NULL), -3),                       # stride 0 is dense
+        ('history_conv_bf16', dict(workspace=P8), -3),
+        ('history_conv_bf16', dict(workspace_bytes=276479), -3),
+        ('history_conv_bf16', dict(workspace_bytes=276479, voxel_major=0, elem_type=2), -3),
+        ('history_conv_bf16', many_wgs, -2),
+        ('history_conv_bf16', dict(many_wgs, workspace=NULL), -2),
+        # ---- fbbev_history_conv_bf16x3: 16-bit voxel-major rings only (fp32: -2, with the channel counts); the workspace also
+        # holds B * T1 * C scaled biases; the preparation launch covers fewer than 2^31 items
+        ('history_conv_bf16x3', dict(B=-1), -1),
+        ('history_conv_bf16x3', dict(N=-1), -1),
+        ('history_conv_bf16x3', dict(elem_type=3), -1),
+        ('history_conv_bf16x3', dict(B=0, null=True), 0),
+        ('history_conv_bf16x3', dict(N=0, null=True), 0),
+        ('history_conv_bf16x3', dict(B=0, elem_type=3), -1),
+        ('history_conv_bf16x3', dict(feats=NULL), -1),
+        ('history_conv_bf16x3', dict(bias1=NULL), -1),
+        ('history_conv_bf16x3', dict(C=32, Cout=32), -2),
+        ('history_conv_bf16x3', dict(elem_type=0), -2),
+        ('history_conv_bf16x3', dict(elem_type=0, out=NULL), -1),
+        ('history_conv_bf16x3', dict(elem_type=0, feats_stride_b=1), -2),
+        ('history_conv_bf16x3', dict(feats_stride_b=17 * F - 1), -1),
+        ('history_conv_bf16x3', dict(feats_stride_b=17 * F - 1, bias1=P8), -1),
+        ('history_conv_bf16x3', dict(feats=P8), -2),
+        ('history_conv_bf16x3', dict(feats_stride_b=17 * F + 4), -2),
+        ('history_conv_bf16x3', dict(bias1=P8), -2),
+        ('history_conv_bf16x3', dict(bias1=P8, workspace=NULL), -2),
+        ('history_conv_bf16x3', dict(C=16, Cout=16, N=1 << 27), -2),
+        ('history_conv_bf16x3', dict(C=16, Cout=16, N=(1 << 27) - 1, workspace=NULL), -3),
+        ('history_conv_bf16x3', dict(workspace=NULL), -3),                     # stride 0 is dense
+        ('history_conv_bf16x3', dict(workspace=P8), -3),
+        ('history_conv_bf16x3', dict(workspace_bytes=558399), -3),
+        ('history_conv_bf16x3', dict(B=1 << 26), -2),
+        ('history_conv_bf16x3', dict(B=1 << 26, workspace_bytes=16), -3),
+        # ---- fbbev_history_fused_x3_vm: axes <= 0 are BADARG, < 2 UNSUPPORTED (with the channel counts and the type); both rings;
+        # the workspace's 64 spare bytes BEFORE the convolutions' own checks (bias1, workspace, preparation launch)
+        ('history_fused_x3_vm', dict(B=-1), -1),
+        ('history_fused_x3_vm', dict(T=0), -1),
+        ('history_fused_x3_vm', dict(C=0), -1),
+        ('history_fused_x3_vm', dict(Cout=0), -1),
+        ('history_fused_x3_vm', dict(Z=0), -1),
+        ('history_fused_x3_vm', dict(Y=0), -1),
+        ('history_fused_x3_vm', dict(X=0), -1),
+        ('history_fused_x3_vm', dict(B=0, null=True), 0),
+        ('history_fused_x3_vm', dict(B=0, T=0), -1),
+        ('history_fused_x3_vm', dict(B=0, elem_type=7, Z=1), 0),
+        ('history_fused_x3_vm', dict(history=NULL), -1),
+        ('history_fused_x3_vm', dict(next=NULL), -1),
+        ('history_fused_x3_vm', dict(rt_flow=NULL), -1),
+        ('history_fused_x3_vm', dict(w1=NULL), -1),
+        ('history_fused_x3_vm', dict(bias1=NULL), -1),
+        ('history_fused_x3_vm', dict(w2=NULL), -1),
+        ('history_fused_x3_vm', dict(bias2=NULL), -1),
+        ('history_fused_x3_vm', dict(out=NULL), -1),
+        ('history_fused_x3_vm', dict(C=16, Cout=16), -2),
+        ('history_fused_x3_vm', dict(Cout=16), -2),
+        ('history_fused_x3_vm', dict(elem_type=0), -2),
+        ('history_fused_x3_vm', dict(elem_type=3), -2),
+        ('history_fused_x3_vm', dict(Z=1), -2),
+        ('history_fused_x3_vm', dict(Y=1), -2),
+        ('history_fused_x3_vm', dict(X=1), -2),
+        ('history_fused_x3_vm', dict(Z=1, out=NULL), -1),
+        ('history_fused_x3_vm', dict(elem_type=3, history_stride_b=1), -2),
+        ('history_fused_x3_vm', dict(history_stride_b=16 * F - 1), -1),
+        ('history_fused_x3_vm', dict(next_stride_b=17 * F - 1), -1),
+        ('history_fused_x3_vm', dict(history_stride_b=16 * F - 1, next=P8), -1),
+        ('history_fused_x3_vm', dict(history=P8, next_stride_b=16 * F), -1),
+        ('history_fused_x3_vm', dict(history=P8), -2),
+        ('history_fused_x3_vm', dict(next=P8), -2),
+        ('history_fused_x3_vm', dict(history_stride_b=16 * F + 4), -2),
+        ('history_fused_x3_vm', dict(next_stride_b=17 * F + 4), -2),
+        ('history_fused_x3_vm', dict(next=P8, workspace_bytes=32), -2),
+        ('history_fused_x3_vm', dict(H_C80_AT_4G, workspace_bytes=32), -2),
+        ('history_fused_x3_vm', dict(H_C80_BELOW_4G, workspace_bytes=32), -3),
+        ('history_fused_x3_vm', dict(workspace_bytes=63), -3),                 # stride 0 is dense
+        ('history_fused_x3_vm', dict(workspace_bytes=63, bias1=P8), -3),
+        ('history_fused_x3_vm', dict(workspace_bytes=64, bias1=P8), -2),
+        ('history_fused_x3_vm', dict(bias1=P8), -2),
+        ('history_fused_x3_vm', dict(bias1=P8, workspace=NULL), -2),
+        ('history_fused_x3_vm', dict(workspace=NULL), -3),
+        ('history_fused_x3_vm', dict(workspace=P8), -3),
+        ('history_fused_x3_vm', dict(workspace_bytes=558400 + 63), -3),
+        ('history_fused_x3_vm', dict(B=1 << 26), -2),
+        ('history_fused_x3_vm', dict(B=1 << 26, workspace=NULL), -3),
+        # ---- fbbev_history_step_x3_vm: `chunks` with the dimensions; `next`'s stride here, the history's left to the warp's plan
+        # (where an axis < 2 is BADARG), then the convolutions' checks (where the channel counts are looked at)
+        ('history_step_x3_vm', dict(B=-1), -1),
+        ('history_step_x3_vm', dict(T=0), -1),
+        ('history_step_x3_vm', dict(Cout=0), -1),
+        ('history_step_x3_vm', dict(X=0), -1),
+        ('history_step_x3_vm', dict(chunks=-1), -1),
+        ('history_step_x3_vm', dict(chunks=65), -1),
+        ('history_step_x3_vm', dict(chunks=64, workspace=NULL), -3),
+        ('history_step_x3_vm', dict(B=0, null=True), 0),
+        ('history_step_x3_vm', dict(B=0, chunks=65), -1),
+        ('history_step_x3_vm', dict(history=NULL), -1),
+        ('history_step_x3_vm', dict(next=NULL), -1),
+        ('history_step_x3_vm', dict(rt_flow=NULL), -1),
+        ('history_step_x3_vm', dict(bias2=NULL), -1),
+        ('history_step_x3_vm', dict(out=NULL), -1),
+        ('history_step_x3_vm', dict(elem_type=0), -2),
+        ('history_step_x3_vm', dict(elem_type=3), -2),
+        ('history_step_x3_vm', dict(elem_type=3, w1=NULL), -1),
+        ('history_step_x3_vm', dict(elem_type=3, next_stride_b=1), -2),
+        ('history_step_x3_vm', H_2G_VOXELS, -2),
+        ('history_step_x3_vm', dict(H_2G_VOXELS, next_stride_b=1), -2),
+        ('history_step_x3_vm', dict(H_BELOW_2G, next_stride_b=1), -1),
+        ('history_step_x3_vm', dict(next_stride_b=17 * F - 1), -1),
+        ('history_step_x3_vm', dict(next_stride_b=17 * F - 1, history=P8), -1),
+        ('history_step_x3_vm', dict(Z=1), -1),
+        ('history_step_x3_vm', dict(Y=1), -1),
+        ('history_step_x3_vm', dict(Z=1, elem_type=3), -2),
+        ('history_step_x3_vm', dict(Z=1, history=P8), -1),
+        ('history_step_x3_vm', dict(history_stride_b=16 * F - 1), -1),
+        ('history_step_x3_vm', dict(history_stride_b=16 * F - 1, next=P8), -1),
+        ('history_step_x3_vm', dict(history_stride_b=16 * F - 1, C=84, Cout=84), -1),
+        ('history_step_x3_vm', dict(history=P8), -2),
+        ('history_step_x3_vm', dict(next=P8), -2),
+        ('history_step_x3_vm', dict(history_stride_b=16 * F + 4), -2),
+        ('history_step_x3_vm', dict(next_stride_b=17 * F + 4), -2),
+        ('history_step_x3_vm', dict(C=84, Cout=84), -2),
+        ('history_step_x3_vm', dict(C=32, Cout=32), -2),
+        ('history_step_x3_vm', dict(C=32, Cout=32, workspace=NULL), -2),
+        ('history_step_x3_vm', dict(Cout=16, workspace=NULL), -2),
+        ('history_step_x3_vm', dict(C=16, Cout=16, workspace=NULL), -3),
+        ('history_step_x3_vm', dict(H_C80_AT_4G, workspace=NULL), -2),
+        ('history_step_x3_vm', dict(H_C80_BELOW_4G, workspace=NULL), -3),
+        ('history_step_x3_vm', dict(bias1=P8), -2),
+        ('history_step_x3_vm', dict(bias1=P8, workspace=NULL), -2),
+        ('history_step_x3_vm', dict(workspace=NULL), -3),                      # stride 0 is dense
+        ('history_step_x3_vm', dict(workspace=P8), -3),
+        ('history_step_x3_vm', dict(workspace_bytes=558399), -3),
+        ('history_step_x3_vm', dict(B=1 << 26), -2),
+        ('history_step_x3_vm', dict(B=1 << 26, workspace=NULL), -3),
+        # ---- fbbev_history_fused_vm: fused_x3_vm's order with bias1 among the row alignments and the bf16 fragments' workspace
+        ('history_fused_vm', dict(B=-1), -1),
+        ('history_fused_vm', dict(T=0), -1),
+        ('history_fused_vm', dict(C=0), -1),
+        ('history_fused_vm', dict(Z=0), -1),
+        ('history_fused_vm', dict(B=0, null=True), 0),
+        ('history_fused_vm', dict(B=0, Y=0), -1),
+        ('history_fused_vm', dict(history=NULL), -1),
+        ('history_fused_vm', dict(next=NULL), -1),
+        ('history_fused_vm', dict(w2=NULL), -1),
+        ('history_fused_vm', dict(out=NULL), -1),
+        ('history_fused_vm', dict(C=16, Cout=16), -2),
+        ('history_fused_vm', dict(C=96), -2),
+        ('history_fused_vm', dict(elem_type=0), -2),
+        ('history_fused_vm', dict(elem_type=3), -2),
+        ('history_fused_vm', dict(Z=1), -2),
+        ('history_fused_vm', dict(X=1), -2),
+        ('history_fused_vm', dict(Z=1, rt_flow=NULL), -1),
+        ('history_fused_vm', dict(Z=1, history_stride_b=1), -2),
+        ('history_fused_vm', dict(history_stride_b=16 * F - 1), -1),
+        ('history_fused_vm', dict(next_stride_b=17 * F - 1), -1),
+        ('history_fused_vm', dict(next_stride_b=17 * F - 1, history=P8), -1),
+        ('history_fused_vm', dict(history_stride_b=16 * F - 1, bias1=P8), -1),
+        ('history_fused_vm', dict(history=P8), -2),
+        ('history_fused_vm', dict(next=P8), -2),
+        ('history_fused_vm', dict(bias1=P8), -2),
+        ('history_fused_vm', dict(bias1=P8, workspace=NULL), -2),
+        ('history_fused_vm', dict(history_stride_b=16 * F + 4), -2),
+        ('history_fused_vm', dict(next_stride_b=17 * F + 4), -2),
+        ('history_fused_vm', dict(H_C80_AT_4G, workspace=NULL), -2),
+        ('history_fused_vm', dict(H_C80_BELOW_4G, workspace=NULL), -3),
+        ('history_fused_vm', dict(H_2G_VOXELS, workspace=NULL), -2),
+        ('history_fused_vm', dict(workspace=NULL), -3),                        # stride 0 is dense
+        ('history_fused_vm', dict(workspace=P8), -3),
+        ('history_fused_vm', dict(workspace_bytes=276479), -3),
+        # ---- the LayerNorm entries between the two halves of the family
+        ('layernorm', dict(rows=-1), -1),
+        ('layernorm', dict(C=0), -1),
+        ('layernorm', dict(eps=-1.0), -1),
+        ('layernorm', dict(eps=float('nan')), -1),
+        ('layernorm', dict(rows=0, null=True), 0),
+        ('layernorm', dict(rows=0, C=0), -1),
+        ('layernorm', dict(x=NULL), -1),
+        ('layernorm', dict(out=NULL), -1),
+        ('layernorm', dict(C=82), -2),
+        ('layernorm', dict(C=132), -2),
+        ('layernorm', dict(C=82, weight=NULL), -1),
+        ('layernorm', dict(x=P8), -2),
+        ('layernorm', dict(residual=P8), -2),
+        ('layernorm', dict(residual=NULL, bias=P8), -2),
+        ('layernorm', dict(rows=1 << 34), -2),
+        ('layernorm_bwd', dict(rows=-1), -1),
+        ('layernorm_bwd', dict(eps=-1.0), -1),
+        ('layernorm_bwd', dict(partial=NULL), -1),
+        ('layernorm_bwd', dict(rows=0, partial=NULL), -1),
+        ('layernorm_bwd', dict(grad_out=NULL), -1),
+        ('layernorm_bwd', dict(grad_x=NULL, C=82), -1),
+        ('layernorm_bwd', dict(C=82), -2),
+        ('layernorm_bwd', dict(C=132), -2),
+        ('layernorm_bwd', dict(grad_x=P8), -2),
+        ('layernorm_bwd', dict(rows=0, C=82, null=True, partial=P16), -2),
+    ]
+    shown = lambda case: {k: (v.value if isinstance(v, ctypes.c_void_p) else repr(v[:]) if isinstance(v, ctypes.Array) else v)   # noqa: E731
+                          for k, v in case.items()}
+    got = [(entry, shown(case), h_call(lib, entry, case)) for entry, case, _ in table]
+    want = [(entry, shown(case), code) for entry, case, code in table]
+    assert got == want, [(g, w[2]) for g, w in zip(got, want) if g != w]
+    assert {entry for entry, _, _ in table} == set(H_PARAMS)
+    assert [lib.fbbev_layernorm_bwd_partials(r) for r in (-1, 0, 1, 8, 9, 16384, 16385, 1 << 40)] == [1, 1, 1, 1, 2, 2048, 2048, 2048]

@@ -182,6 +182,22 @@ def test_argument_errors_of_both_entries():
     assert src(NULL, 0, NULL, 0, NULL, NULL, 0, 16, 80, 8, 8, 8, NULL, 0, 2, None) == 0              # empty batch: no-op
 
 
+def test_workgroup_limit_of_the_one_kernel_step_behind_its_weight_launch():
+    """fbbev_history_fused_vm counts its workgroups after it has laid the weight fragments out: 2^29 samples of a 2 x 2 x 2 grid
+    are 2^31 workgroups, -2, with the fragments written and neither ring touched (dummy pointers do for them)."""
+    lib = E.lib()
+    P16 = c_void_p(0x1000)
+    T, C = 1, 80
+    w1, w2 = torch.randn(C, C), torch.randn(C, (T + 1) * C)
+    need = (1 + T + 1) * 5 * 3 * 64 * 8 * 2                                                     # W1 and T + 1 W2 as bf16 fragments
+    ws = torch.zeros(need // 2 + 8, dtype=torch.int16)
+    args = lambda B, nbytes: (P16, 0, P16, 0, P16, c_void_p(w1.data_ptr()), P16, c_void_p(w2.data_ptr()), P16, B, T, C, C,   # noqa: E731
+                              2, 2, 2, P16, c_void_p(ws.data_ptr()), nbytes, 2, None)
+    assert lib.fbbev_history_fused_vm(*args(1 << 29, need - 1)) == -3 and not ws.any()          # the workspace comes first
+    assert lib.fbbev_history_fused_vm(*args(1 << 29, need)) == -2
+    assert ws[:need // 2].any() and not ws[need // 2:].any()
+
+
 @pytest.mark.parametrize('dt', [torch.float32, torch.float16])
 def test_module_stream_state_on_emulated_kernels_equals_the_default_route(monkeypatch, dt):
     """fb_bev_amd.history_fusion's host code for stream_state=True driving the emulated kernels, against the same module on the
