@@ -756,7 +756,8 @@ def test_layernorm_training_route_equals_torch_autograd(rows, C):
 def test_msda_backward_band_binned_route_on_the_gpu():
     """MultiScaleDeformableAttnFunction_fp32 backward at the configs[2] self-attention shape (200 x 200 BEV, raster queries
     sampling around their own cell): the atomic-free kernels are taken (grad_value starts uninitialised), equal the fp32
-    global-atomic kernel to rounding, and two runs give the SAME bits (the atomic kernel does not promise that)."""
+    global-atomic kernel to rounding, and two runs give the SAME bits (the atomic kernel does not promise that).  Other shapes,
+    band edges and the element-wise pin against float64 are in tests/msda_kernel_cases.py (tests/test_gpu_msda_kernels.py)."""
     from fb_bev_amd import _capi
     from fb_bev_amd.backward_projection import const_tensor
     from fb_bev_amd.ms_deform_attn import MultiScaleDeformableAttnFunction_fp32 as F32

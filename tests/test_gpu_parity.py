@@ -471,6 +471,7 @@ def _msda_cases():
 
 @pytest.mark.parametrize('ci', range(8))
 def test_msda_forward_backward(dev, ci):
+    """The element-wise pin of every MSDA route against float64 is tests/msda_kernel_cases.py (tests/test_gpu_msda_kernels.py)."""
     from test_oracle_msda import make_case
     from fb_bev_amd.ms_deform_attn import MultiScaleDeformableAttnFunction_fp32 as F32
     O = _oracle()
