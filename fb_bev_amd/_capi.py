@@ -6,7 +6,7 @@ tensor is not on a GPU the call raises.
 """
 import ctypes
 import os
-from ctypes import c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -184,6 +184,7 @@ SIGNATURES = {
     'fbbev_occ_lovasz_ws_bytes': (c_size_t, [c_int] * 5),
     'fbbev_occ_lovasz_fwd': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 6 + [c_size_t, c_void_p]),
     'fbbev_occ_lovasz_grad': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 5),
+    'fbbev_occ_fscore_counts': (c_int, [c_void_p] * 8 + [c_int, c_int, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1935,6 +1936,40 @@ def occ_classes(logits, c0=0, gt=None, mask=None, column_mask=None, hist=None, o
                                        _dev(out, U8, 'out'), opt(gt, U8, 'gt'), opt(mask, U8, 'mask'),
                                        opt(column_mask, U8, 'column_mask'), opt(hist, I32, 'hist'), _stream()), 'fbbev_occ_classes')
     return out
+
+
+def occ_fscore_counts(classes, gt, mask, void_bits, sq_x, sq_y, sq_z, offsets, R, T_acc, T_cmpl, counts=None):
+    """fbbev_occ_fscore_counts: the F-score's four counts (n_gt, n_pred, n_cmpl, n_acc) per frame, ADDED to counts (B, 4) int32 (a
+    zeroed one is made when none is given).  classes, gt (B, X, Y, Z) uint8 contiguous, mask the same or None; void_bits a ctypes
+    array of 8 uint32 on the host (bit id set: class id is void); sq_x / sq_y / sq_z (X / Y / Z, 2R + 1) float64 and offsets
+    (n, 3) int32 on the device, T_acc / T_cmpl floats: the tables occ_metrics.Metric_FScore builds."""
+    require_gpu(classes, 'classes')
+    if classes.dim() != 4:
+        raise FbbevError(f'classes must be (B, X, Y, Z), got {tuple(classes.shape)}')
+    B, X, Y, Z = classes.shape
+    for t, name in ((gt, 'gt'), (mask, 'mask')):
+        if t is not None and tuple(t.shape) != (B, X, Y, Z):
+            raise FbbevError(f'{name} must be {(B, X, Y, Z)}, got {tuple(t.shape)}')
+    W = 2 * int(R) + 1
+    for t, name, n in ((sq_x, 'sq_x', X), (sq_y, 'sq_y', Y), (sq_z, 'sq_z', Z)):
+        if tuple(t.shape) != (n, W):
+            raise FbbevError(f'{name} must be {(n, W)}, got {tuple(t.shape)}')
+    if offsets.dim() != 2 or offsets.shape[1] != 3:
+        raise FbbevError(f'offsets must be (n, 3), got {tuple(offsets.shape)}')
+    if len(void_bits) != 8:
+        raise FbbevError('void_bits must hold 8 words')
+    if counts is None:
+        counts = torch.zeros((B, 4), dtype=I32, device=classes.device)
+    elif tuple(counts.shape) != (B, 4):
+        raise FbbevError(f'counts must be {(B, 4)}, got {tuple(counts.shape)}')
+    with _on(classes):
+        _check(lib().fbbev_occ_fscore_counts(_dev(classes, U8, 'classes'), _dev(gt, U8, 'gt'),
+                                             None if mask is None else _dev(mask, U8, 'mask'), ctypes.cast(void_bits, c_void_p),
+                                             _dev(sq_x, torch.float64, 'sq_x'), _dev(sq_y, torch.float64, 'sq_y'),
+                                             _dev(sq_z, torch.float64, 'sq_z'), _dev(offsets, I32, 'offsets'), offsets.shape[0], int(R),
+                                             float(T_acc), float(T_cmpl), B, X, Y, Z, _dev(counts, I32, 'counts'), _stream()),
+               'fbbev_occ_fscore_counts')
+    return counts
 
 
 OCC_LOSS_FOCAL = 1                # include/fbbev.h FBBEV_OCC_LOSS_FOCAL

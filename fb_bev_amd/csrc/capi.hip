@@ -26,6 +26,7 @@
 #include "det_kernels.h"
 #include "occ_kernels.h"
 #include "occ_loss_kernels.h"
+#include "occ_fscore_kernels.h"
 #include "../../include/fbbev.h"
 
 #include "capi_common.h"
@@ -4022,6 +4023,37 @@ extern "C" int fbbev_occ_classes(const float* logits, long long stride_b, long l
     else if (vec4) FBBEV_OCC_LAUNCH(false, true);
     else FBBEV_OCC_LAUNCH(false, false);
 #undef FBBEV_OCC_LAUNCH
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ occupancy F-score: the four counts of a frame
+extern "C" int fbbev_occ_fscore_counts(const uint8_t* classes, const uint8_t* gt, const uint8_t* mask, const uint32_t* void_bits,
+                                       const double* sq_x, const double* sq_y, const double* sq_z, const int32_t* offsets, int n_off,
+                                       int R, double T_acc, double T_cmpl, int B, int X, int Y, int Z, int32_t* counts,
+                                       fbbev_stream_t stream_) {
+    if (!classes || !gt || !void_bits || !sq_x || !sq_y || !sq_z || !offsets || !counts) return FBBEV_E_BADARG;
+    if (B < 0 || X <= 0 || Y <= 0 || Z <= 0 || R < 0 || n_off <= 0) return FBBEV_E_BADARG;
+    if (B == 0) return 0;
+    if (Z > FBBEV_OCCF_MAX_Z || R > FBBEV_OCCF_MAX_R || X > (1 << 30) || Y > (1 << 30)) return FBBEV_E_UNSUPPORTED;
+    long long nvox = B;                                  // factor by factor: each is below 2^31, so no product leaves 64 bits
+    for (const int f : {X, Y, Z}) {
+        nvox *= f;
+        if (nvox >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    }
+    fbbev_occf_void vb;
+    for (int i = 0; i < 8; ++i) vb.w[i] = void_bits[i];
+    const int ntx = (X + FBBEV_OCCF_TILE - 1) / FBBEV_OCCF_TILE, nty = (Y + FBBEV_OCCF_TILE - 1) / FBBEV_OCCF_TILE;
+    const long long blocks = (long long)B * ntx * nty;
+    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
+    const int vec4 = (Z % 4 == 0 && aligned4(classes) && aligned4(gt) && aligned4(mask)) ? 1 : 0;
+    const size_t lds = fbbev_occf_lds_bytes(R, Z);
+#define FBBEV_OCCF_LAUNCH(V)                                                                                                          \
+    FBBEV_LAUNCH((k_occ_fscore<V>), blocks, FBBEV_OCCF_THREADS, lds, (fbbev_rt_stream)stream_, classes, gt, mask, vb, sq_x, sq_y, sq_z, \
+                 offsets, n_off, R, T_acc, T_cmpl, X, Y, Z, ntx, nty, counts)
+    if (vec4) FBBEV_OCCF_LAUNCH(true);
+    else FBBEV_OCCF_LAUNCH(false);
+#undef FBBEV_OCCF_LAUNCH
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

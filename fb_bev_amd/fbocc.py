@@ -328,10 +328,11 @@ class FBOCC(nn.Module):
         x = x.permute(0, 3, 4, 2, 1)                                                    # (B,H',W',D,c)
         return x if return_raw_occ else x[..., 0]
 
-    def predict_occupancy_classes(self, img_inputs, img_metas, gt_occupancy=None, mask_camera=None, metric=None, **kwargs):
+    def predict_occupancy_classes(self, img_inputs, img_metas, gt_occupancy=None, mask_camera=None, metric=None, fscore=None, **kwargs):
         """predict_occupancy's class ids as uint8 (B, X', Y', Z), with the slice / softmax / argmax / axis shuffle done by ONE kernel
         (fbbev_occ_classes) on whichever layout the head route returned.  With `metric` (occ_metrics.Metric_mIoU) the same launch
-        scores the batch against gt_occupancy / mask_camera (B, X', Y', Z) into it."""
+        scores the batch against gt_occupancy / mask_camera (B, X', Y', Z) into it.  With `fscore` (occ_metrics.Metric_FScore) the
+        class map is scored into it on the device (fbbev_occ_fscore_counts), with or without `metric`."""
         from . import _capi
         results = self.extract_feat(None, img=img_inputs, img_metas=img_metas, **kwargs)
         if 'img_bev_feat_ndhwc' in results:
@@ -340,8 +341,12 @@ class FBOCC(nn.Module):
             occ = self.occupancy_head(results['img_bev_feat'], results=results)['output_voxels'][0]   # (B,cls,H,W,D) class planes
         c0 = 1 if self.fix_void else 0
         if metric is not None:
-            return metric.add_logits(occ.float(), gt_occupancy, mask_camera, c0=c0)
-        return _capi.occ_classes(occ.float(), c0=c0)
+            classes = metric.add_logits(occ.float(), gt_occupancy, mask_camera, c0=c0)
+        else:
+            classes = _capi.occ_classes(occ.float(), c0=c0)
+        if fscore is not None:
+            fscore.add_batch(classes, gt_occupancy, None, mask_camera)
+        return classes
 
     def simple_test(self, points, img_metas, img=None, rescale=False, visible_mask=(None,), return_raw_occ=False, **kwargs):
         assert len(img_metas) == 1                                                      # :591

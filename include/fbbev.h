@@ -1241,6 +1241,26 @@ int fbbev_occ_lovasz_grad(const float* logits, long long stride_b, long long str
                           long long stride_d, int B, int C, int H, int W, int D, const uint8_t* labels, const float* coef,
                           const float* scale, float* grad_logits, fbbev_stream_t stream);
 
+/* The four integer counts of the occupancy F-score of a frame (replaces the two KDTree builds and queries of occ_metrics.py:222-275
+ * Metric_FScore.add_batch): the voxel centres lie on a regular grid, so "nearest neighbour closer than the threshold" is a bounded
+ * stencil over two occupancy bitmaps.
+ *   classes, gt (B, X, Y, Z) bytes, contiguous; mask (same shape) or NULL.  A voxel's effective id is its id where the mask byte is
+ *   non-zero and 255 elsewhere; it is occupied iff bit `id` of void_bits is clear.  void_bits: 8 words (256 bits) in HOST memory, read
+ *   before the launch.  P = the occupied voxels of classes, G = those of gt.
+ *   sq_x (X, 2R+1), sq_y (Y, 2R+1), sq_z (Z, 2R+1) float64 in DEVICE memory: sq_a[i][o + R] = (c_a[i] - c_a[i + o])^2 with c_a the
+ *   centre coordinates the caller uses, +inf where i + o leaves the grid.  offsets (n_off, 3) int32 in DEVICE memory: the (ox, oy, oz)
+ *   to visit, each within -R..R (one outside is skipped).  q hits a set S within T iff for some listed offset o, q + o is in S and
+ *   (sq_x[qx][ox + R] + sq_y[qy][oy + R]) + sq_z[qz][oz + R] <= T: two float64 adds in that order, no multiply, no square root (T is
+ *   the largest float64 whose root is below the metric's threshold; the host finds it).
+ *   counts (B, 4) int32, ADDED to: n_gt = |G|, n_pred = |P|, n_cmpl = #{g in G : g hits P within T_cmpl},
+ *   n_acc = #{p in P : p hits G within T_acc}.  Integer atomics only: exact and identical run to run.
+ * Checked in this order.  FBBEV_E_BADARG: a null classes / gt / void_bits / sq_x / sq_y / sq_z / offsets / counts, B < 0, a
+ * non-positive X / Y / Z / n_off, R < 0.  B == 0: 0 and no launch.  FBBEV_E_UNSUPPORTED: Z > 32, R > 4, X or Y above 2^30, or
+ * B*X*Y*Z >= 2^31 (which also keeps a count within int32). */
+int fbbev_occ_fscore_counts(const uint8_t* classes, const uint8_t* gt, const uint8_t* mask, const uint32_t* void_bits,
+                            const double* sq_x, const double* sq_y, const double* sq_z, const int32_t* offsets, int n_off, int R,
+                            double T_acc, double T_cmpl, int B, int X, int Y, int Z, int32_t* counts, fbbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
