@@ -231,7 +231,7 @@ static fbbev_fastdiv make_fastdiv(unsigned int d) {
 }
 
 struct rank_ws_layout {
-    size_t keys_a, keys_t, vals_t, matrix, ctot, chunk_info, total;
+    size_t keys_a, keys_t, vals_t, matrix, ctot, chunk_info, boff, hb, total;
     int v0, wgs0;          // pass 0 (keys + scatter over all n points)
     int v1, wgs1;          // later passes (over the P kept pairs; P is only known on the device: sized for about n/2,
                            // the grid covers the worst case P = n and surplus workgroups leave at once)
@@ -265,7 +265,12 @@ static rank_ws_layout rank_layout(long long n) {
     L.matrix = off; off = align_up(off + mbytes, 256);
     L.ctot = off; off = align_up(off + seg_rows * 4, 256);
     L.chunk_info = off; off = align_up(off + (size_t)L.wgsi * 8, 256);
-    L.total = off;                                         // no per-build state: nothing to clear, no kernel waits for another
+    // the high-digit-first route (FBBEV_RANK_FINISH): bucket offsets (+ the closing P) and run heads per bucket, at most
+    // 2^10 buckets for each of min(n, 256) samples
+    const size_t fin_buckets = (size_t)(n < 256 ? n : 256) * FBBEV_SEG_NB;
+    L.boff = off; off = align_up(off + (fin_buckets + 1) * 4, 256);
+    L.hb = off; off = align_up(off + fin_buckets * 4, 256);
+    L.total = off;                                        // no per-build state: nothing to clear, no kernel waits for another
     return L;
 }
 
@@ -289,6 +294,18 @@ extern "C" size_t fbbev_rank_workspace_bytes(int64_t n_points) {
 }
 
 static int rank_seg_mode() { FBBEV_KNOB_ONCE(int, m, fbbev_env_int("FBBEV_RANK_SEG", -1)); return m; }
+static int rank_finish_mode() { FBBEV_KNOB_ONCE(int, m, fbbev_env_int("FBBEV_RANK_FINISH", -1)); return m; }
+// auto rule of the high-digit-first route, on what the host knows (key bits of a sample, frustum points per sample, samples): on
+// where it measured faster than the two-pass route beyond that route's own spread, whole build, eager, p50 of 60
+// (profiles/r19_rank_finish.md) --
+//   20 key bits (10 + 10; the 200 x 200 x 16 grid), 249 k points per sample: B = 16  0.143 -> 0.122 ms, B = 4  0.108 -> 0.088 ms
+//   17 key bits (10 + 7; the shipped 100 x 100 x 8 grid), 338 k points per sample, B = 16: 0.176 -> 0.170 ms, inside the spread: off
+// Nothing between 17 and 20 bits has been measured, so only full 10-bit low digits take the route; B and the points per sample
+// are already bounded by the segmented route's own rule (at least 96 chunks, at most 64 per sample).
+static bool rank_finish_auto(int lbits, long long npb, int B) {
+    (void)npb; (void)B;
+    return lbits >= 2 * FBBEV_SEG_RB;
+}
 
 static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const float* frustum, int B, int N, int D,
                            int H, int W,
@@ -356,11 +373,48 @@ static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const 
         fbbev_geom_src gs;
         if (cams) { gs.cam = *cams; gs.frustum = frustum; gs.gp = gp; }
         else { gs.cam = fbbev_cam_ptrs(); gs.frustum = nullptr; gs.gp = gp; }
+        // High digit first (FBBEV_RANK_FINISH, two-digit plans only): ONE scatter by (key - b V) >> low_bits, then every bucket is
+        // finished by one wave (k_bucket_finish) and the intervals follow from the buckets' head counts (k_bucket_intervals):
+        // 4 launches instead of 6, the same index tensors bit for bit (sort_kernels.h).  0 = never, 1 = wherever legal (tests),
+        // unset = auto: see rank_finish_auto.
+        const int fin_mode = rank_finish_mode();
+        const bool finish = passes == 2 && fin_mode != 0 && (fin_mode == 1 || rank_finish_auto(lbits, npb, B));
+        const int high_bits = FBBEV_SEG_RB, low_bits = lbits - FBBEV_SEG_RB;        // passes == 2: 1 <= low_bits <= 10
+        const int rb0 = finish ? high_bits : srb, dshift0 = finish ? low_bits : 0;
         if (cams) FBBEV_LAUNCH((k_keys_hist_seg<true>), wgs, FBBEV_SEG_NT, 0, stream, gs, (const float*)nullptr, gp, (const float*)nullptr, 0.f,
-                               sg, srb, skip, keys_a, matrix, ctot);
-        else FBBEV_LAUNCH((k_keys_hist_seg<false>), wgs, FBBEV_SEG_NT, 0, stream, gs, coor, gp, point_depth, depth_thr, sg, srb, skip, keys_a,
-                          matrix, ctot);
+                               sg, rb0, dshift0, skip, keys_a, matrix, ctot);
+        else FBBEV_LAUNCH((k_keys_hist_seg<false>), wgs, FBBEV_SEG_NT, 0, stream, gs, coor, gp, point_depth, depth_thr, sg, rb0, dshift0, skip,
+                          keys_a, matrix, ctot);
         FBBEV_CHECK_LAUNCH();
+        if (finish) {
+            int* boff = reinterpret_cast<int*>(ws + L.boff);
+            int* hb = reinterpret_cast<int*>(ws + L.hb);
+            const int nbk = (int)((vps + (1ll << low_bits) - 1) >> low_bits);       // buckets a sample can fill (<= 2^high_bits)
+            const int buckets = B * nbk;
+            static const int swz = fbbev_env_int("FBBEV_RANK_XCD_SWIZZLE", 1);   // as the two-pass route below
+            const int sw = (swz && B >= 8) ? 1 : 0;
+            // the compacted (key, point id) pairs in keys_t | vals_t (adjacent: one array of pairs), bucket after bucket
+            FBBEV_LAUNCH(k_sort_scatter_seg, sw ? (wgs + 7) / 8 * 8 : wgs, FBBEV_SEG_NT, 0, stream, (const unsigned int*)keys_a,
+                         (const unsigned int*)nullptr, (const int*)matrix, (const int*)ctot, sg, 0, high_bits, skip, keys_t, vals_t, counts, sw, 2,
+                         low_bits, boff, nbk);
+            FBBEV_CHECK_LAUNCH();
+            const fbbev_fastdiv div_dhw = make_fastdiv((unsigned int)((long long)D * H * W)), div_hw = make_fastdiv((unsigned int)(H * W));
+            // short buckets: one wave per bucket while they fit the part (8 four-wave workgroups per CU), then a wave walks several;
+            // long buckets: two workgroups per CU in front of them, each looking at every 512th bucket
+            int short_wgs = (buckets + FBBEV_FIN_WAVES - 1) / FBBEV_FIN_WAVES;
+            if (short_wgs > 2048) short_wgs = 2048;
+            const int long_wgs = buckets < 512 ? buckets : 512;
+            FBBEV_LAUNCH(k_bucket_finish, long_wgs + short_wgs, FBBEV_FIN_WAVES * 64, 0, stream, reinterpret_cast<const uint2*>(keys_t),
+                         (const int*)boff, buckets, nbk, sg.vps, low_bits, long_wgs, div_dhw, div_hw, skip,
+                         reinterpret_cast<unsigned int*>(ranks_bev), reinterpret_cast<unsigned int*>(ranks_depth), ranks_feat, hb);
+            FBBEV_CHECK_LAUNCH();
+            const int per_wg = (buckets + 255) / 256;                               // one round of 1024-thread workgroups on the part
+            FBBEV_LAUNCH((k_bucket_intervals<16, 4>), (buckets + per_wg - 1) / per_wg, 1024, (size_t)2 * 4 * 1024 * 4, stream,
+                         reinterpret_cast<const unsigned int*>(ranks_bev), (const int*)boff, (const int*)hb, buckets, per_wg, skip,
+                         interval_starts, interval_lengths, interval_rank, counts);
+            FBBEV_CHECK_LAUNCH();
+            return 0;
+        }
         const unsigned int* kin = keys_a;
         const unsigned int* vin = nullptr;
         static const int pairs = fbbev_env_int("FBBEV_RANK_PAIRS", 1);   // A/B knob, read once
@@ -381,7 +435,7 @@ static int rank_build_impl(const float* coor, const fbbev_cam_ptrs* cams, const 
             // (BL2 B = 4: 0.123 vs 0.129) -- profiles/r04_time_rank_swizzle.jsonl
             const int sw = (swz && B >= 8) ? 1 : 0;
             FBBEV_LAUNCH(k_sort_scatter_seg, sw ? (wgs + 7) / 8 * 8 : wgs, FBBEV_SEG_NT, 0, stream, kin, vin, (const int*)matrix,
-                         (const int*)ctot, sg, p, srb, skip, ko, vo, counts, sw, pm);
+                         (const int*)ctot, sg, p, srb, skip, ko, vo, counts, sw, pm, -1, (int*)nullptr, 0);
             FBBEV_CHECK_LAUNCH();
             kin = ko; vin = vo;
         }

@@ -261,3 +261,90 @@ k_interval_write(const unsigned int* __restrict__ keys, const unsigned int* __re
         counts[1] = I;
     }
 }
+
+// ---------------------------------------------------------------- run detection behind the bucket-local sort: one launch
+// The high-digit-first route (sort_kernels.h, k_bucket_finish) leaves boff[] (where every bucket starts; boff[buckets] = P)
+// and hb[] (run heads per bucket) behind, so nothing has to be counted first:
+//   * a workgroup owns the buckets [g0, g0 + per_wg): elements [boff[g0], boff[g1]), walked in tiles of WAVES*64*ITEMS;
+//   * its first interval index is the plain sum of hb[0 .. g0) (L2-resident, the idea of k_interval_write's chunk_info read);
+//   * the first element of a bucket is always a run head, so the element at boff[g1] is the head that closes this
+//     workgroup's last interval (or P does): no position has to come from another workgroup.
+// Heads are found by neighbour compare as in k_interval_write.  ranks_feat is written by k_bucket_finish.
+template <int WAVES, int ITEMS>
+__global__ void __launch_bounds__(WAVES * 64)
+k_bucket_intervals(const unsigned int* __restrict__ keys, const int* __restrict__ boff, const int* __restrict__ hb, int buckets,
+                   int per_wg, const int* __restrict__ skip, int* __restrict__ interval_starts, int* __restrict__ interval_lengths,
+                   int* __restrict__ interval_rank, int* __restrict__ counts) {
+    if (skip != nullptr && *skip != 0) return;
+    constexpr int NT = WAVES * 64;
+    constexpr int TILE = NT * ITEMS;
+    __shared__ int ldsw[WAVES];
+    const int tid = threadIdx.x;
+    const int g0 = (int)blockIdx.x * per_wg;
+    if (g0 >= buckets) return;
+    const int g1 = g0 + per_wg < buckets ? g0 + per_wg : buckets;
+    const int r0 = boff[g0], r1 = boff[g1];
+    // hb[0 .. g0) as 16-byte words, four requested per thread before the first is added (one load per loop trip is up to ten
+    // round trips in a row at the bench shape; measured 15.4 -> 15.2 us there, profiles/r19_rank_finish.md)
+    int h = 0;
+    {
+        constexpr int U = 4;
+        const int nq = g0 >> 2;
+        const fbbev_v4i* hb4 = reinterpret_cast<const fbbev_v4i*>(hb);             // 16-byte aligned (workspace layout)
+        for (int q0 = tid; q0 < nq; q0 += NT * U) {
+            fbbev_v4i t[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int qi = q0 + u * NT;
+                t[u] = hb4[qi < nq ? qi : nq - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (q0 + u * NT < nq) h += t[u][0] + t[u][1] + t[u][2] + t[u][3];
+        }
+        if (tid < (g0 & 3)) h += hb[4 * nq + tid];
+    }
+    int hbase;
+    (void)fbbev_block_excl_scan_w<WAVES, false>(h, ldsw, &hbase);
+    int* hpos = reinterpret_cast<int*>(fbbev_dyn_lds_f32());        // [TILE] head positions, then [TILE] voxel ranks
+    int* hkey = hpos + TILE;
+    int lastpos = r0;                                     // position of the latest head (r0 is one whenever r1 > r0)
+    for (int t0 = r0; t0 < r1; t0 += TILE) {
+        const long long base = (long long)t0 + (long long)tid * ITEMS;
+        bool head[ITEMS];
+        unsigned int key[ITEMS];
+        int local = 0;
+        unsigned int prevk = (base > r0 && base <= r1) ? keys[base - 1] : 0u;
+        fbbev_ld_run<ITEMS>(keys, base, r1, 0u, key);
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const long long i = base + j;
+            head[j] = false;
+            if (i < r1) {
+                head[j] = (i == r0 || prevk != key[j]);
+                prevk = key[j];
+                if (head[j]) ++local;
+            }
+        }
+        int tot;
+        int o = fbbev_block_excl_scan_w<WAVES, false>(local, ldsw, &tot);
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j)
+            if (head[j]) { hpos[o] = (int)(base + j); hkey[o] = (int)key[j]; ++o; }
+        __syncthreads();
+        for (int q = tid; q < tot; q += NT) {
+            const int pos = hpos[q], j0 = hbase + q;
+            interval_starts[j0] = pos;
+            if (interval_rank) interval_rank[j0] = hkey[q];
+            if (q > 0) interval_lengths[j0 - 1] = pos - hpos[q - 1];
+            else if (t0 > r0) interval_lengths[j0 - 1] = pos - lastpos;
+        }
+        if (tot > 0) lastpos = hpos[tot - 1];
+        hbase += tot;
+        __syncthreads();                                  // the next tile overwrites the compacted heads
+    }
+    if (tid == 0) {
+        if (r1 > r0) interval_lengths[hbase - 1] = r1 - lastpos;
+        if (g1 == buckets) counts[1] = hbase;             // I; the last workgroup runs even without an element (P = 0: I = 0)
+    }
+}

@@ -325,10 +325,12 @@ __device__ __forceinline__ void fbbev_seg_prefix2(const int* __restrict__ ctot, 
 }
 
 // keys + pass-0 count matrix + ctot, sample-aligned chunks.  GEOM: keys from the camera geometry, else from `coor`.
+// The pass-0 digit is ((key - b V) >> dshift) & (2^rb - 1): dshift = 0 for the LSD order, the low-digit width for the
+// high-digit-first route (k_bucket_finish below).
 template <bool GEOM>
 __global__ void __launch_bounds__(FBBEV_SEG_NT)
 k_keys_hist_seg(fbbev_geom_src g, const float* __restrict__ coor, fbbev_grid_params gp, const float* __restrict__ depth,
-                float depth_thr, fbbev_seg sg, int rb, const int* __restrict__ skip, unsigned int* __restrict__ keys_out,
+                float depth_thr, fbbev_seg sg, int rb, int dshift, const int* __restrict__ skip, unsigned int* __restrict__ keys_out,
                 int* __restrict__ matrix, int* __restrict__ ctot) {
     if (fbbev_skip(skip)) return;
     constexpr int NT = FBBEV_SEG_NT, PER = FBBEV_SEG_ROUNDS;
@@ -367,7 +369,7 @@ k_keys_hist_seg(fbbev_geom_src g, const float* __restrict__ coor, fbbev_grid_par
                     const int pid = base + (int)threadIdx.x + (r0 + r) * NT;
                     if (pid >= lo && pid < hi) {
                         keys_out[pid] = key[r];
-                        if (key[r] != FBBEV_DROP_KEY) { atomicAdd(&cnt[(key[r] - kbase) & dmask], 1); ++mine; }
+                        if (key[r] != FBBEV_DROP_KEY) { atomicAdd(&cnt[((key[r] - kbase) >> dshift) & dmask], 1); ++mine; }
                     }
                 }
             }
@@ -382,7 +384,7 @@ k_keys_hist_seg(fbbev_geom_src g, const float* __restrict__ coor, fbbev_grid_par
                                                   (float)b, FBBEV_DROP_KEY);
                 if (depth && !(depth[pid] > depth_thr)) key = FBBEV_DROP_KEY;
                 keys_out[pid] = key;
-                if (key != FBBEV_DROP_KEY) { atomicAdd(&cnt[(key - kbase) & dmask], 1); ++mine; }
+                if (key != FBBEV_DROP_KEY) { atomicAdd(&cnt[((key - kbase) >> dshift) & dmask], 1); ++mine; }
             }
         }
     }
@@ -429,7 +431,8 @@ k_sort_hist_seg(const unsigned int* __restrict__ keys, const int* __restrict__ c
 __global__ void __launch_bounds__(FBBEV_SEG_NT)
 k_sort_scatter_seg(const unsigned int* __restrict__ keys_in, const unsigned int* __restrict__ vals_in, const int* __restrict__ matrix,
                    const int* __restrict__ ctot, fbbev_seg sg, int pass, int rb, const int* __restrict__ skip,
-                   unsigned int* __restrict__ keys_out, unsigned int* __restrict__ vals_out, int* __restrict__ counts, int xcd_swizzle, int pair_mode) {
+                   unsigned int* __restrict__ keys_out, unsigned int* __restrict__ vals_out, int* __restrict__ counts, int xcd_swizzle, int pair_mode,
+                   int dshift, int* __restrict__ boff, int nbk) {
     if (fbbev_skip(skip)) return;
     constexpr int WAVES = FBBEV_SEG_WAVES, ROUNDS = FBBEV_SEG_ROUNDS, NT = FBBEV_SEG_NT, NBM = FBBEV_SEG_NB;
     // chunk id of this workgroup.  xcd_swizzle (grid = 8 * ceil(chunks / 8)): workgroups are dealt to the 8 XCDs round-robin, so
@@ -448,7 +451,7 @@ k_sort_scatter_seg(const unsigned int* __restrict__ keys_in, const unsigned int*
     __shared__ int red[2 * WAVES];
     __shared__ int ldsw[WAVES];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nb = 1 << rb, shift = pass * rb;
+    const int nb = 1 << rb, shift = dshift >= 0 ? dshift : pass * rb;       // dshift >= 0: the high-digit-first route's pass 0
     const unsigned int dmask = (unsigned int)nb - 1u;
     const int b = chunk_id / sg.cps, c = chunk_id - b * sg.cps;
     const unsigned int kbase = (unsigned int)b * sg.vps;
@@ -458,7 +461,7 @@ k_sort_scatter_seg(const unsigned int* __restrict__ keys_in, const unsigned int*
     if (pass == 0 && chunk_id == 0) {                    // P = all kept points
         int p0, pall;
         fbbev_seg_prefix2<WAVES>(ctot, 0, sg.nseg * sg.cps, red, p0, pall);
-        if (tid == 0) counts[0] = pall;
+        if (tid == 0) { counts[0] = pall; if (boff) boff[sg.nseg * nbk] = pall; }
     }
     const long long in0 = pass == 0 ? (long long)b * sg.npb : (long long)s0;                 // the sample's input range
     const long long in1 = pass == 0 ? (long long)(b + 1) * sg.npb : (long long)s1;
@@ -522,6 +525,12 @@ k_sort_scatter_seg(const unsigned int* __restrict__ keys_in, const unsigned int*
         const int ex = fbbev_block_excl_scan_w<WAVES, false>(a0 + a1, ldsw, &total);
         if (d0 < nb) pos0[d0] = p0 + s0 + ex;
         if (d1 < nb) pos0[d1] = p1 + s0 + ex + a0;
+        // high-digit-first route: the digit scan of a sample's chunk 0 (no earlier chunk: p0 = p1 = 0) is where its buckets start;
+        // bucket (b, d) ends where the next one starts -- boff[nseg * nbk] = P closes the last (stored with counts[0] above)
+        if (boff && c == 0) {
+            if (d0 < nbk) boff[b * nbk + d0] = s0 + ex;
+            if (d1 < nbk) boff[b * nbk + d1] = s0 + ex + a0;
+        }
     }
     __syncthreads();                                      // every partial has been read
     for (int i = tid; i < WAVES * NBM; i += NT) (&cnt[0][0])[i] = 0;
@@ -564,6 +573,190 @@ k_sort_scatter_seg(const unsigned int* __restrict__ keys_in, const unsigned int*
             // (the scattered stores are a third of the pass: profiles/r04_rank_scatter_probes.txt)
             if (pair_mode & 2) reinterpret_cast<uint2*>(keys_out)[pos] = make_uint2(k[r], v[r]);
             else { keys_out[pos] = k[r]; vals_out[pos] = v[r]; }
+        }
+    }
+}
+
+// ================================================================ high digit first: one scatter, then bucket-local finish
+// With pass 0 scattering by the HIGH digit ((key - b V) >> low_bits), bucket (b, d) is a contiguous range
+// [boff[b nbk + d], boff[b nbk + d + 1]) of the compacted pair array, in point-id order, and its sorted result occupies the
+// same range of the outputs.  Sorting a bucket by its low digit is local: no count matrix, no column-sum prologue, nothing
+// to hear from another workgroup, and any bucket length.
+//   sweep A : count the low digit in cnt[2^low_bits] (LDS adds: order does not matter), exclusive scan over the counters; the
+//             non-zero counters are the bucket's run heads -> hb[bucket]
+//   sweep B : the same rounds of 64 pairs in order, each ranked stably with the ballot match of k_sort_scatter_seg on top of
+//             the running counters; key -> ranks_bev, point id -> ranks_depth, its feature pixel -> ranks_feat
+// A bucket of up to FBBEV_FIN_STAGE rounds belongs to ONE WAVE, which keeps its pairs in registers between the sweeps and never
+// meets a barrier.  A longer bucket (up to ~40 rounds at the bench grid: one wave would be the whole kernel's tail) belongs to one
+// of the first `long_wgs` workgroups (dispatched first: the long work starts first): the four waves take a quarter each, count
+// into their own counters, and the per-wave first positions of a digit are formed in place as in k_sort_scatter_seg.
+#define FBBEV_FIN_WAVES 4
+#define FBBEV_FIN_STAGE 8
+// counter d lives at word d + d / 16: the scan gives a lane 2^low_bits / 64 CONSECUTIVE counters, and 64 lanes 16 words apart
+// would meet in 4 LDS banks
+#define FBBEV_FIN_SLOT(d) ((d) + ((d) >> 4))
+#define FBBEV_FIN_WORDS (FBBEV_SEG_NB + (FBBEV_SEG_NB >> 4))
+
+__global__ void __launch_bounds__(FBBEV_FIN_WAVES * 64)
+k_bucket_finish(const uint2* __restrict__ pairs, const int* __restrict__ boff, int buckets, int nbk, unsigned int vps, int low_bits,
+                int long_wgs, fbbev_fastdiv div_dhw, fbbev_fastdiv div_hw, const int* __restrict__ skip,
+                unsigned int* __restrict__ ranks_bev, unsigned int* __restrict__ ranks_depth, int* __restrict__ ranks_feat,
+                int* __restrict__ hb) {
+    if (fbbev_skip(skip)) return;
+    constexpr int WAVES = FBBEV_FIN_WAVES, ST = FBBEV_FIN_STAGE, NT = FBBEV_FIN_WAVES * 64;
+    __shared__ int cntw[WAVES][FBBEV_FIN_WORDS];
+    __shared__ int lds4[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nlow = 1 << low_bits;
+    const unsigned int lmask = (unsigned int)nlow - 1u;
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint2 kv[ST];
+    // ST rounds of the range [g0, end) into kv[] (all loads first: one memory round trip)
+    auto load = [&](int g0, int end) {
+#pragma unroll
+        for (int r = 0; r < ST; ++r) {
+            const int idx = g0 + r * 64 + lane;
+            kv[r] = make_uint2(FBBEV_DROP_KEY, 0u);
+            if (idx < end) kv[r] = pairs[idx];
+        }
+    };
+    auto count = [&](unsigned int kbase) {
+#pragma unroll
+        for (int r = 0; r < ST; ++r)
+            if (kv[r].x != FBBEV_DROP_KEY) atomicAdd(&cntw[wave][FBBEV_FIN_SLOT((int)((kv[r].x - kbase) & lmask))], 1);
+    };
+    // the rounds of kv[] that start below `end`, ranked in order on the wave's running counters (positions inside the bucket)
+    auto rank = [&](int g0, int end, int start, unsigned int kbase) {
+#pragma unroll
+        for (int r = 0; r < ST; ++r) {
+            if (g0 + r * 64 < end) {                      // wave-uniform
+                const bool valid = kv[r].x != FBBEV_DROP_KEY;
+                const unsigned int d = (kv[r].x - kbase) & lmask;
+                unsigned long long mm = __ballot(valid ? 1 : 0);
+#pragma unroll
+                for (int bit = 0; bit < FBBEV_SEG_RB; ++bit) {         // bits at or above low_bits are 0 in every valid lane: no-ops
+                    const unsigned long long bb = __ballot((int)((d >> bit) & 1u));
+                    mm &= ((d >> bit) & 1u) ? bb : ~bb;
+                }
+                const int leader = valid ? (__ffsll((long long)mm) - 1) : lane;
+                int prev = 0;
+                if (valid && lane == leader) {
+                    prev = cntw[wave][FBBEV_FIN_SLOT((int)d)];
+                    cntw[wave][FBBEV_FIN_SLOT((int)d)] = prev + __popcll(mm);
+                }
+                prev = __shfl(prev, leader, 64);
+                if (valid) {
+                    const int pos = start + prev + __popcll(mm & lt);
+                    const unsigned int pid = kv[r].y;
+                    // view_transformer.py:563-568: feature pixel of point ((b*N+n)*D+d)*HW + hw
+                    const unsigned int cam = fbbev_div(pid, div_dhw), hw = pid - fbbev_div(pid, div_hw) * div_hw.d;
+                    ranks_bev[pos] = kv[r].x;
+                    ranks_depth[pos] = pid;
+                    ranks_feat[pos] = (int)(cam * div_hw.d + hw);
+                }
+                fbbev_sched_fence();                      // one round's ballot masks at a time (the rounds chain through cnt anyway)
+            }
+        }
+    };
+
+    if ((int)blockIdx.x >= long_wgs) {
+        const int short_wgs = (int)gridDim.x - long_wgs, sw = (int)blockIdx.x - long_wgs;
+        // ---- one wave, one bucket of at most ST rounds
+        const int per = nlow >= 64 ? nlow >> 6 : 1;      // counters per lane of the scan (lanes at or beyond nlow / per idle)
+        for (int g = sw * WAVES + wave; g < buckets; g += short_wgs * WAVES) {       // wave-uniform
+            const int start = boff[g], end = boff[g + 1];
+            if (end <= start) {
+                if (lane == 0) hb[g] = 0;
+                continue;
+            }
+            if (end - start > 64 * ST) continue;         // a long bucket: the other workgroups
+            const unsigned int kbase = (unsigned int)(g / nbk) * vps;
+            load(start, end);
+            for (int d = lane; d < nlow; d += 64) cntw[wave][FBBEV_FIN_SLOT(d)] = 0;
+            fbbev_wave_sync();
+            count(kbase);
+            fbbev_wave_sync();
+            int sum = 0, nz = 0;
+            if (lane * per < nlow) {
+                for (int j = 0; j < per; ++j) {
+                    const int c = cntw[wave][FBBEV_FIN_SLOT(lane * per + j)];
+                    sum += c;
+                    nz += c != 0 ? 1 : 0;
+                }
+            }
+            int run = fbbev_wave_incl_scan(sum, lane) - sum;
+            if (lane * per < nlow) {
+                for (int j = 0; j < per; ++j) {
+                    const int c = cntw[wave][FBBEV_FIN_SLOT(lane * per + j)];
+                    cntw[wave][FBBEV_FIN_SLOT(lane * per + j)] = run;
+                    run += c;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) nz += __shfl_down(nz, o, 64);
+            if (lane == 0) hb[g] = nz;
+            fbbev_wave_sync();
+            rank(start, end, start, kbase);
+            fbbev_wave_sync();                            // the next bucket clears the counters
+        }
+        return;
+    }
+    // ---- the long buckets, one at a time by the whole workgroup.  Workgroup L looks at the buckets L, L + long_wgs, ... (lane l
+    // of every wave at the l-th of them: one round trip for 64 offsets), far apart so that neighbouring long buckets -- the
+    // dense rows next to the rig -- do not queue up in one workgroup
+    const int L = (int)blockIdx.x;
+    const int per = nlow >= NT ? nlow / NT : 1;          // counters per thread of the combine step
+    for (int base = L; base < buckets; base += 64 * long_wgs) {
+        const int mine = base + lane * long_wgs;
+        const bool is_long = mine < buckets && boff[mine + 1] - boff[mine] > 64 * ST;
+        unsigned long long todo = __ballot(is_long ? 1 : 0);           // the same in every wave
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int g = base + l * long_wgs;
+            const int start = boff[g], end = boff[g + 1];
+            const unsigned int kbase = (unsigned int)(g / nbk) * vps;
+            // wave w owns the rounds [w q, (w + 1) q) of the bucket
+            const int q = ((end - start + 64 * WAVES - 1) / (64 * WAVES)) * 64;
+            const int w0 = start + wave * q < end ? start + wave * q : end, w1 = w0 + q < end ? w0 + q : end;
+            for (int d = lane; d < nlow; d += 64) cntw[wave][FBBEV_FIN_SLOT(d)] = 0;
+            fbbev_wave_sync();
+            for (int g0 = w0; g0 < w1; g0 += 64 * ST) {
+                load(g0, w1);
+                count(kbase);
+            }
+            __syncthreads();
+            // counts -> first position of each wave's keys of a digit, in place; thread t owns the digits [t per, (t + 1) per)
+            int sum = 0, nz = 0;
+            if (tid * per < nlow) {
+                for (int j = 0; j < per; ++j) {
+                    int c = 0;
+#pragma unroll
+                    for (int w = 0; w < WAVES; ++w) c += cntw[w][FBBEV_FIN_SLOT(tid * per + j)];
+                    sum += c;
+                    nz += c != 0 ? 1 : 0;
+                }
+            }
+            int total, heads;
+            int run = fbbev_block_excl_scan(sum, lds4, &total);
+            (void)fbbev_block_excl_scan(nz, lds4, &heads);
+            if (tid * per < nlow) {
+                for (int j = 0; j < per; ++j) {
+#pragma unroll
+                    for (int w = 0; w < WAVES; ++w) {
+                        const int c = cntw[w][FBBEV_FIN_SLOT(tid * per + j)];
+                        cntw[w][FBBEV_FIN_SLOT(tid * per + j)] = run;
+                        run += c;
+                    }
+                }
+            }
+            if (tid == 0) hb[g] = heads;
+            __syncthreads();
+            for (int g0 = w0; g0 < w1; g0 += 64 * ST) {
+                load(g0, w1);
+                rank(g0, w1, start, kbase);
+            }
+            __syncthreads();                              // the next bucket clears the counters
         }
     }
 }
