@@ -1,5 +1,10 @@
 """GPU parity of the temporal history fusion against fixtures recorded from the REAL
-FBOCC.fuse_history (tests/golden/make_golden_history.py) and against the CPU oracle."""
+FBOCC.fuse_history (tests/golden/make_golden_history.py) and against the CPU oracle.
+
+Most assertions here compare one project kernel with another ("same bits": voxel-major ring == planar ring, fused == two-kernel
+path, LDS warp == gather warp).  Their float64 anchor is the case table tests/history_kernel_cases.py (run by
+tests/test_gpu_history_kernels.py and tests/test_emu_history_kernels.py): every one of those kernels against a plain float64
+reference, bit for bit on exact inputs and inside derived bounds on real ones, at tile-edge shapes."""
 import os
 
 import numpy as np
