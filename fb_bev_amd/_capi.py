@@ -185,6 +185,9 @@ SIGNATURES = {
     'fbbev_occ_lovasz_fwd': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 6 + [c_size_t, c_void_p]),
     'fbbev_occ_lovasz_grad': (c_int, [c_void_p] + [c_int64] * 5 + [c_int] * 5 + [c_void_p] * 5),
     'fbbev_occ_fscore_counts': (c_int, [c_void_p] * 8 + [c_int, c_int, c_double, c_double] + [c_int] * 4 + [c_void_p, c_void_p]),
+    'fbbev_depth_loss_ws_bytes': (c_size_t, [c_int] * 4),
+    'fbbev_depth_loss_fwd': (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_float, c_float] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    'fbbev_depth_loss_grad': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -2092,4 +2095,65 @@ def occ_lovasz_grad(logits, labels, coef, scale, out=None):
     with _on(logits):
         _check(lib().fbbev_occ_lovasz_grad(*args, _dev(coef, F32, 'coef'), _dev(scale, F32, 'scale'),
                                            _dev(out, F32, 'out', contiguous=False), _stream()), 'fbbev_occ_lovasz_grad')
+    return out
+
+
+def _depth_loss_dims(probs, labels):
+    require_gpu(probs, 'probs')
+    if probs.dtype != F32 or probs.dim() != 4:
+        raise FbbevError(f'probs must be a 4-D float32 tensor (BN, D, h, w), got {probs.dtype} {tuple(probs.shape)}')
+    BN, D, h, w = probs.shape
+    if labels is not None and tuple(labels.shape) != (BN, h, w):
+        raise FbbevError(f'labels must be {(BN, h, w)}, got {tuple(labels.shape)}')
+    return BN, D, h, w
+
+
+def depth_loss_fwd(gt, probs, downsample, num_bins, lo, step, labels=None, out_f=None, out_i=None, ws=None):
+    """fbbev_depth_loss_fwd: the depth supervision of CM_DepthNet with linear bins [lo, hi, step] from one pass over gt (BN, H, W) f32
+    and probs (BN, D, h, w) f32, both contiguous (probs None: labels and the count only).  -> labels (BN, h, w) int32 (-1 = background),
+    out_f (2,) f32 = {bce_sum, bce_sum / max(count, 1)}, out_i (1,) int32 = {count}; see include/fbbev.h.  Bit-identical from run to
+    run; nothing waits for the host."""
+    require_gpu(gt, 'gt')
+    if gt.dtype != F32 or gt.dim() != 3:
+        raise FbbevError(f'gt must be a 3-D float32 tensor (BN, H, W), got {gt.dtype} {tuple(gt.shape)}')
+    BN, H, W = gt.shape
+    ds, D = int(downsample), int(num_bins)
+    if ds <= 0 or H % ds or W % ds:
+        raise FbbevError(f'downsample {ds} must divide the image {(H, W)}')
+    h, w = H // ds, W // ds
+    if probs is not None and _depth_loss_dims(probs, None) != (BN, D, h, w):
+        raise FbbevError(f'probs must be {(BN, D, h, w)}, got {tuple(probs.shape)}')
+    dev = gt.device
+    if labels is None:
+        labels = torch.empty((BN, h, w), dtype=I32, device=dev)
+    if out_f is None:
+        out_f = torch.empty(2, dtype=F32, device=dev)
+    if out_i is None:
+        out_i = torch.empty(1, dtype=I32, device=dev)
+    if tuple(labels.shape) != (BN, h, w) or tuple(out_f.shape) != (2,) or tuple(out_i.shape) != (1,):
+        raise FbbevError(f'labels / out_f / out_i must be {(BN, h, w)} / (2,) / (1,), got {tuple(labels.shape)} / {tuple(out_f.shape)} / '
+                         f'{tuple(out_i.shape)}')
+    if ws is None:
+        ws = torch.empty(max(lib().fbbev_depth_loss_ws_bytes(BN, h, w, D), 16), dtype=U8, device=dev)
+    with _on(gt):
+        _check(lib().fbbev_depth_loss_fwd(_dev(gt, F32, 'gt'), BN, H, W, ds, None if probs is None else _dev(probs, F32, 'probs'), D,
+                                          float(lo) - float(step), float(step), _dev(labels, I32, 'labels'), _dev(out_f, F32, 'out_f'),
+                                          _dev(out_i, I32, 'out_i'), _dev(ws, U8, 'ws'), ws.numel(), _stream()), 'fbbev_depth_loss_fwd')
+    return labels, out_f, out_i
+
+
+def depth_loss_grad(probs, labels, out_i, grad_loss, out=None):
+    """fbbev_depth_loss_grad: the gradient of probs (BN, D, h, w) from labels and out_i of depth_loss_fwd and grad_loss, a one-element
+    f32 tensor on the device (the upstream gradient of out_f[1]).  Every element of `out` is written."""
+    BN, D, h, w = _depth_loss_dims(probs, labels)
+    if grad_loss.numel() != 1 or out_i.numel() != 1:
+        raise FbbevError(f'grad_loss and out_i must hold one element, got {tuple(grad_loss.shape)} and {tuple(out_i.shape)}')
+    if out is None:
+        out = torch.empty_like(probs, memory_format=torch.contiguous_format)
+    elif out.shape != probs.shape:
+        raise FbbevError(f'out must be {tuple(probs.shape)}, got {tuple(out.shape)}')
+    with _on(probs):
+        _check(lib().fbbev_depth_loss_grad(_dev(probs, F32, 'probs'), _dev(labels, I32, 'labels'), _dev(out_i, I32, 'out_i'),
+                                           _dev(grad_loss, F32, 'grad_loss'), BN, D, h, w, _dev(out, F32, 'out'), _stream()),
+               'fbbev_depth_loss_grad')
     return out

@@ -7,6 +7,7 @@
 #include "wgrad_kernels.h"
 #include "rows_wgrad_f32_kernels.h"
 #include "occ_lovasz_kernels.h"
+#include "depth_loss_kernels.h"
 #include "../../include/fbbev.h"
 
 // ------------------------------------------------------------------------------ weight / bias gradient of a row-wise linear layer
@@ -423,6 +424,79 @@ extern "C" int fbbev_occ_lovasz_grad(const float* logits, long long stride_b, lo
     if (p.staged) FBBEV_OCCLV_GRAD(true);
     else FBBEV_OCCLV_GRAD(false);
 #undef FBBEV_OCCLV_GRAD
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ depth supervision loss: labels + BCE, and its backward
+namespace {
+struct dl_plan { int h, w, cc, vec; long long nrec; size_t off_i, total; };
+// the counts the kernels index with 32 bits: cells and elements below 2^31 (factor by factor: no product leaves 64 bits)
+bool dl_counts_fit(int BN, int D, int h, int w) {
+    long long cells = BN;
+    for (const int f : {h, w}) {
+        cells *= f;
+        if (cells >= (1ll << 31)) return false;
+    }
+    return cells * D < (1ll << 31);
+}
+dl_plan dl_plan_of(const void* gt, int BN, int W, int ds, int h, int w) {
+    dl_plan p;
+    p.h = h; p.w = w;
+    p.cc = FBBEV_DL_COLS / ds;                                             // ds <= FBBEV_DL_COLS has been checked
+    if (p.cc >= 4) p.cc &= ~3;                                             // a chunk starts on a column that is a multiple of 4
+    p.vec = (W % 4 == 0 && aligned16(gt) && ((long long)p.cc * ds) % 4 == 0) ? 1 : 0;
+    p.nrec = (long long)BN * h;
+    p.off_i = align_up((size_t)p.nrec * sizeof(float), 16);
+    p.total = p.off_i + align_up((size_t)p.nrec * sizeof(int32_t), 16);
+    return p;
+}
+}  // namespace
+
+extern "C" size_t fbbev_depth_loss_ws_bytes(int BN, int h, int w, int D) {
+    if (BN <= 0 || h <= 0 || w <= 0 || D <= 0 || !dl_counts_fit(BN, D, h, w)) return 0;
+    return dl_plan_of(nullptr, BN, 4, 1, h, w).total;
+}
+
+extern "C" int fbbev_depth_loss_fwd(const float* gt, int BN, int H, int W, int ds, const float* probs, int D, float bin0, float step,
+                                    int32_t* labels, float* out_f, int32_t* out_i, void* ws, size_t ws_bytes, fbbev_stream_t stream_) {
+    if (!gt || !labels || !out_f || !out_i || (BN > 0 && !ws)) return FBBEV_E_BADARG;
+    if (BN < 0 || H <= 0 || W <= 0 || ds <= 0 || D <= 0 || H % ds != 0 || W % ds != 0) return FBBEV_E_BADARG;
+    if (!(step > 0.f) || !(step <= 3.402823466e38f) || !(bin0 >= -3.402823466e38f && bin0 <= 3.402823466e38f)) return FBBEV_E_BADARG;
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    if (BN == 0) {
+        int e = fbbev_rt_memset_async(out_f, 0, 2 * sizeof(float), stream);
+        if (!e) e = fbbev_rt_memset_async(out_i, 0, sizeof(int32_t), stream);
+        return e;
+    }
+    const int h = H / ds, w = W / ds;
+    if (D > FBBEV_DL_MAX_D || ds > FBBEV_DL_COLS || !dl_counts_fit(BN, D, h, w)) return FBBEV_E_UNSUPPORTED;
+    const dl_plan p = dl_plan_of(gt, BN, W, ds, h, w);
+    if (ws_bytes < p.total || !aligned16(ws)) return FBBEV_E_WORKSPACE;
+    float* part_f = static_cast<float*>(ws);
+    int* part_i = reinterpret_cast<int*>(static_cast<char*>(ws) + p.off_i);
+    const size_t lds = ((size_t)2 * FBBEV_DL_COLS + FBBEV_DL_THREADS) * 4;
+#define FBBEV_DL_LAUNCH(V)                                                                                                        \
+    FBBEV_LAUNCH((k_depth_loss_fwd<V>), p.nrec, FBBEV_DL_THREADS, lds, stream, gt, H, W, ds, h, w, p.cc, probs, D, bin0, step, labels, \
+                 part_f, part_i)
+    if (p.vec) FBBEV_DL_LAUNCH(true);
+    else FBBEV_DL_LAUNCH(false);
+#undef FBBEV_DL_LAUNCH
+    FBBEV_CHECK_LAUNCH();
+    FBBEV_LAUNCH(k_depth_loss_reduce, 1, FBBEV_DL_THREADS, (size_t)FBBEV_DL_THREADS * 12, stream, (const float*)part_f,
+                 (const int*)part_i, (int)p.nrec, out_f, out_i);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int fbbev_depth_loss_grad(const float* probs, const int32_t* labels, const int32_t* out_i, const float* grad_loss, int BN,
+                                     int D, int h, int w, float* grad_probs, fbbev_stream_t stream_) {
+    if (!probs || !labels || !out_i || !grad_loss || !grad_probs || BN < 0 || D <= 0 || h <= 0 || w <= 0) return FBBEV_E_BADARG;
+    if (BN == 0) return 0;
+    if (D > FBBEV_DL_MAX_D || !dl_counts_fit(BN, D, h, w)) return FBBEV_E_UNSUPPORTED;
+    const unsigned int hw = (unsigned int)h * w, total = (unsigned int)BN * D * hw;
+    FBBEV_LAUNCH(k_depth_loss_grad, (total + FBBEV_DL_THREADS - 1) / FBBEV_DL_THREADS, FBBEV_DL_THREADS, 0, (fbbev_rt_stream)stream_, probs,
+                 labels, out_i, grad_loss, (unsigned int)D, hw, total, grad_probs);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

@@ -115,19 +115,57 @@ class BasicBlock(nn.Module):
         return self.relu(out + identity)
 
 
+class _DepthLoss(torch.autograd.Function):
+    """the kernels of fb_bev_amd/csrc/depth_loss_kernels.h: gt, probs -> the mean BCE over the foreground cells; backward: one pass
+    over probs.  Only probs, the labels (BN, h, w) int32 and the foreground count are kept; gt gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, gt, probs, downsample, lo, step):
+        from . import _capi
+        labels, out_f, out_i = _capi.depth_loss_fwd(gt, probs, downsample, probs.shape[1], lo, step)
+        ctx.save_for_backward(probs, labels, out_i)
+        return out_f[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        from . import _capi
+        probs, labels, out_i = ctx.saved_tensors
+        grad_loss = grad_out.to(torch.float32).reshape(1)                               # on the device: nothing waits for the host
+        return None, _capi.depth_loss_grad(probs, labels, out_i, grad_loss), None, None, None
+
+
+def depth_loss_fused(gt_depths, depth_preds, downsample, depth_cfg):
+    """-> the unweighted depth supervision loss of gt_depths (B, N, H, W) and depth_preds (B, N, D, h, w) f32 with the linear bins
+    depth_cfg = [lo, hi, step]: CM_DepthNet.get_depth_loss / loss_depth_weight up to fp32 summation order, from one pass over
+    both tensors forward and one over depth_preds backward.  No one-hot, permuted copy or per-element loss is kept."""
+    from . import _capi
+    _capi.require_gpu(depth_preds, 'depth_preds')
+    _capi.require_gpu(gt_depths, 'gt_depths')
+    B, N, D, h, w = depth_preds.shape
+    lo, _, step = depth_cfg
+    gt = gt_depths.to(torch.float32).contiguous().view(B * N, gt_depths.shape[-2], gt_depths.shape[-1])
+    probs = depth_preds.to(torch.float32).contiguous().view(B * N, D, h, w)
+    return _DepthLoss.apply(gt, probs, int(downsample), float(lo), float(step))
+
+
 class CM_DepthNet(nn.Module):
-    """Constructor arguments of the reference (depth_net.py:262-276) + two execution knobs:
+    """Constructor arguments of the reference (depth_net.py:262-276) + three execution knobs:
     channels_last (default True): run the convolution stack on NHWC activations;
     compute_dtype (default torch.float32, as the reference's @force_fp32): torch.bfloat16 wraps the conv stack in
-    autocast; softmax and outputs stay fp32."""
+    autocast; softmax and outputs stay fp32;
+    fused_depth_loss (default False): get_depth_loss through depth_loss_fused for fp32 GPU predictions with linear bins (sid
+    binning takes a logf before its truncation and stays on torch)."""
 
     def __init__(self, in_channels=512, context_channels=64, depth_channels=118, mid_channels=512, use_dcn=True,
                  downsample=16, grid_config=None, loss_depth_weight=3.0, with_cp=False, se_depth_map=False, sid=False,
-                 bias=0.0, input_size=None, use_aspp=True, channels_last=True, compute_dtype=torch.float32):
+                 bias=0.0, input_size=None, use_aspp=True, channels_last=True, compute_dtype=torch.float32,
+                 fused_depth_loss=False):
         super().__init__()
         if use_dcn:
             raise NotImplementedError('use_dcn=True needs mmcv\'s deformable convolution; the FB-OCC configs use use_dcn=False')
         self.sid, self.with_cp, self.downsample, self.grid_config = sid, with_cp, downsample, grid_config
+        self.fused_depth_loss = bool(fused_depth_loss)
         self.loss_depth_weight, self.se_depth_map = loss_depth_weight, se_depth_map
         self.context_channels, self.depth_channels = context_channels, depth_channels
         self.channels_last, self.compute_dtype = channels_last, compute_dtype
@@ -203,6 +241,9 @@ class CM_DepthNet(nn.Module):
         return onehot[:, 1:].float()
 
     def get_depth_loss(self, depth_labels, depth_preds):
+        if self.fused_depth_loss and depth_preds.is_cuda and depth_preds.dtype == torch.float32 and not self.sid:
+            loss = depth_loss_fused(depth_labels, depth_preds, self.downsample, self.grid_config['depth'])
+            return dict(loss_depth=self.loss_depth_weight * loss)
         labels = self.get_downsampled_gt_depth(depth_labels)
         preds = depth_preds.permute(0, 1, 3, 4, 2).contiguous().view(-1, self.depth_channels)
         fg = labels.max(dim=1).values > 0.0

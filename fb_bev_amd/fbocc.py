@@ -81,6 +81,8 @@ class FBOCC(nn.Module):
         backward (occ_loss.voxel_losses_fused; same values up to fp32 summation order; default off);
         fused_lovasz=True: the head's Lovasz-softmax loss from a segmented radix sort on the logits, forward and backward
         (occ_loss.lovasz_softmax_fused; no full-size softmax, error matrix or permutation is kept; default off);
+        fused_depth_loss=True: the depth net's supervision loss (labels, BCE, mean) from one pass each way over the depth maps and
+        the depth distribution (depth_net.depth_loss_fused; fp32 predictions on the GPU with linear bins; default off);
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -94,6 +96,8 @@ class FBOCC(nn.Module):
         self.img_backbone = _build(img_backbone, **cp, compute_dtype=_dtype(ex.get('img_dtype')))
         self.img_neck = _build(img_neck, **cp, compute_dtype=_dtype(ex.get('img_dtype')))
         self.depth_net = _build(depth_net, **cp, compute_dtype=_dtype(ex.get('depth_dtype')))
+        if self.depth_net is not None and ex.get('fused_depth_loss') is not None:
+            self.depth_net.fused_depth_loss = bool(ex['fused_depth_loss'])
         fvt = FBViewTransform(forward_projection, backward_projection, readd=readd)
         self.forward_projection = fvt.forward_projection
         self.backward_projection = fvt.backward_projection

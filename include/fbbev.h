@@ -1261,6 +1261,47 @@ int fbbev_occ_fscore_counts(const uint8_t* classes, const uint8_t* gt, const uin
                             const double* sq_x, const double* sq_y, const double* sq_z, const int32_t* offsets, int n_off, int R,
                             double T_acc, double T_cmpl, int B, int X, int Y, int Z, int32_t* counts, fbbev_stream_t stream);
 
+/* Depth supervision loss of CM_DepthNet (training; replaces depth_net.py:396-450, get_downsampled_gt_depth + get_depth_loss with
+ * linear bins) from ONE pass over the depth maps and the depth distribution.
+ *   gt (BN, H, W) f32, contiguous (4-byte alignment is enough; 16-byte loads are used when W % 4 == 0 and gt is 16-byte aligned):
+ *   metric depth, 0 = no return.  ds: the cell size; h = H / ds, w = W / ds.
+ *   probs (BN, D, h, w) f32, contiguous, or NULL: labels and the count only (out_f = {0, 0}).
+ *   Per cell: m = min over its ds x ds entries of (x == 0 ? 1e5f : x) -- -0.0 is masked too, a NaN wins as in torch.min;
+ *   bins = (m - bin0) / step, ONE IEEE fp32 subtraction and ONE IEEE fp32 division, bin0 = (float)(lo - step) taken in double by
+ *   the caller and rounded once; b = 0 <= bins < D + 1 ? (int)bins : 0.  labels[cell] = b - 1: -1 = background (no return, out of
+ *   range, NaN, or bin 0), else the one-hot row's index 0..D-1.  (BN, h, w) int32, written for EVERY cell.
+ *   For a foreground cell: sum_d -max(d == label ? logf(p_d) : log1pf(-p_d), -100), what F.binary_cross_entropy evaluates; a p
+ *   outside [0, 1] or a NaN comes out as the device's libm gives it (the clamp lets a NaN through), nothing traps.
+ *   out_f (2 f32) = {bce_sum, bce_sum / max(count, 1)} (one IEEE division); out_i (1 i32) = {count}, the foreground cells.
+ *   ws: fbbev_depth_loss_ws_bytes(BN, h, w, D) = 2 * round_up(4 * BN * h, 16) bytes (one float and one int per workgroup, a
+ *   workgroup per image and cell row: the grid is not capped), 16-byte aligned; its contents on entry do not matter.
+ * No atomics: a workgroup adds its terms through a fixed tree, one workgroup adds the records in a fixed order (thread t records
+ * t, t + 256, ... ascending, then the 256 thread sums through a fixed tree; floats in double, rounded once): bit-identical from
+ * run to run.
+ * No allocation and no host synchronisation: the pair can be captured into a graph.
+ * A non-dyadic step: torch's GPU kernel for `x / step` multiplies by 1 / step and may land one ulp away from the division before
+ * the truncation (2 of 10^6 random depths changed bin at step 0.4); this entry follows the division, which is what torch
+ * evaluates on the CPU and what tests/golden/depth_net_small.npz pins.  Every shipped config has step 0.5 or 1, where both agree.
+ * Checked in this order.  FBBEV_E_BADARG: a null gt / labels / out_f / out_i, a null ws with BN > 0, BN < 0, a non-positive
+ * H / W / ds / D, H % ds or W % ds non-zero, step not finite or <= 0, bin0 not finite.  BN == 0: 0, no launch, out_f and out_i
+ * zeroed.  FBBEV_E_UNSUPPORTED: D > 4096, ds > 4096 (a chunk of column minima is 4096 floats of LDS), BN*h*w >= 2^31 or
+ * BN*D*h*w >= 2^31.  FBBEV_E_WORKSPACE: ws too small or not 16-byte aligned.  fbbev_depth_loss_ws_bytes returns 0 for a
+ * non-positive argument or an unsupported count. */
+size_t fbbev_depth_loss_ws_bytes(int BN, int h, int w, int D);
+int fbbev_depth_loss_fwd(const float* gt, int BN, int H, int W, int ds, const float* probs, int D, float bin0, float step,
+                         int32_t* labels, float* out_f, int32_t* out_i, void* ws, size_t ws_bytes, fbbev_stream_t stream);
+
+/* Backward of fbbev_depth_loss_fwd's out_f[1]: with g = *grad_loss (one f32 in DEVICE memory) and count = out_i[0] (read on the
+ * device: nothing waits for the host),
+ *   grad_probs[n, d, y, x] = g / max(count, 1) * (p - [d == label]) / max((1 - p) p, 1e-12f)      for a foreground cell
+ * which is torch's binary_cross_entropy backward (not the derivative of the clamped forward), and an exact 0 for a background cell.
+ * grad_probs (BN, D, h, w) f32 contiguous: EVERY element is written, no memset is needed.  probs, labels, out_i as the forward
+ * took and left them.
+ * FBBEV_E_BADARG: a null pointer, BN < 0, a non-positive D / h / w.  BN == 0: 0 and no launch.  FBBEV_E_UNSUPPORTED: D > 4096,
+ * BN*h*w >= 2^31 or BN*D*h*w >= 2^31. */
+int fbbev_depth_loss_grad(const float* probs, const int32_t* labels, const int32_t* out_i, const float* grad_loss, int BN, int D,
+                          int h, int w, float* grad_probs, fbbev_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
