@@ -188,6 +188,8 @@ SIGNATURES = {
     'fbbev_depth_loss_ws_bytes': (c_size_t, [c_int] * 4),
     'fbbev_depth_loss_fwd': (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_int, c_float, c_float] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     'fbbev_depth_loss_grad': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
+    'fbbev_points_to_depth': (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 3 + [c_float, c_float] +
+                              [c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -2156,4 +2158,45 @@ def depth_loss_grad(probs, labels, out_i, grad_loss, out=None):
         _check(lib().fbbev_depth_loss_grad(_dev(probs, F32, 'probs'), _dev(labels, I32, 'labels'), _dev(out_i, I32, 'out_i'),
                                            _dev(grad_loss, F32, 'grad_loss'), BN, D, h, w, _dev(out, F32, 'out'), _stream()),
                'fbbev_depth_loss_grad')
+    return out
+
+
+def points_to_depth(points, offsets, max_points, lidar2img, post_rots, post_trans, H, W, downsample, depth_lo, depth_hi, out=None):
+    """fbbev_points_to_depth: a LiDAR sweep to multi-view depth maps.  points (sum P, C >= 3) f32 with a unit column stride (the row
+    stride is taken from the view, so a (P, 5) sweep or a slice of one is read in place), offsets (B + 1) int32 on the device,
+    max_points >= the largest per-sample count (the caller's host-side knowledge: nothing waits for the host), lidar2img
+    (B, N, 4, 4), post_rots (B, N, 3, 3), post_trans (B, N, 3) f32 contiguous -> out (B, N, H // ds, W // ds) f32: the nearest kept
+    depth per pixel, 0 = no return; see include/fbbev.h.  Bit-identical from run to run."""
+    require_gpu(points, 'points')
+    if points.dtype != F32 or points.dim() != 2 or points.shape[1] < 3:
+        raise FbbevError(f'points must be a 2-D float32 tensor (P, >= 3), got {points.dtype} {tuple(points.shape)}')
+    P, C = points.shape
+    stride = C if P <= 1 else points.stride(0)
+    if (C > 1 and points.stride(1) != 1) or stride < 3 or stride >= 2 ** 31:
+        raise FbbevError(f'points must have a unit column stride and rows of at least 3 floats apart, got strides {points.stride()}')
+    if lidar2img.dim() != 4 or tuple(lidar2img.shape[2:]) != (4, 4):
+        raise FbbevError(f'lidar2img must be (B, N, 4, 4), got {tuple(lidar2img.shape)}')
+    B, N = lidar2img.shape[:2]
+    if tuple(post_rots.shape) != (B, N, 3, 3) or tuple(post_trans.shape) != (B, N, 3):
+        raise FbbevError(f'post_rots / post_trans must be {(B, N, 3, 3)} / {(B, N, 3)}, got {tuple(post_rots.shape)} / '
+                         f'{tuple(post_trans.shape)}')
+    if tuple(offsets.shape) != (B + 1,):
+        raise FbbevError(f'offsets must be {(B + 1,)}, got {tuple(offsets.shape)}')
+    H, W, ds, max_points = int(H), int(W), int(downsample), int(max_points)
+    if ds < 1 or H < 0 or W < 0 or max_points < 0 or max_points > P:
+        raise FbbevError(f'downsample {ds} must be >= 1, H {H} and W {W} >= 0, max_points {max_points} within 0..{P}')
+    h, w = H // ds, W // ds
+    if P == 0:                                                   # an empty tensor has no address: one unread row stands in
+        points = torch.zeros((1, 3), dtype=F32, device=points.device)
+    if out is None:
+        out = torch.empty((B, N, h, w), dtype=F32, device=points.device)
+    elif tuple(out.shape) != (B, N, h, w):
+        raise FbbevError(f'out must be {(B, N, h, w)}, got {tuple(out.shape)}')
+    if out.numel() == 0:                                         # nothing to write (the entry returns 0 as well; empty tensors have no address)
+        return out
+    with _on(points):
+        _check(lib().fbbev_points_to_depth(_dev(points, F32, 'points', contiguous=False), int(stride), _dev(offsets, I32, 'offsets'),
+                                           max_points, B, N, _dev(lidar2img, F32, 'lidar2img'), _dev(post_rots, F32, 'post_rots'),
+                                           _dev(post_trans, F32, 'post_trans'), H, W, ds, float(depth_lo), float(depth_hi),
+                                           _dev(out, F32, 'out'), _stream()), 'fbbev_points_to_depth')
     return out

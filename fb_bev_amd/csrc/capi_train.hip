@@ -8,6 +8,7 @@
 #include "rows_wgrad_f32_kernels.h"
 #include "occ_lovasz_kernels.h"
 #include "depth_loss_kernels.h"
+#include "points_depth_kernels.h"
 #include "../../include/fbbev.h"
 
 // ------------------------------------------------------------------------------ weight / bias gradient of a row-wise linear layer
@@ -497,6 +498,41 @@ extern "C" int fbbev_depth_loss_grad(const float* probs, const int32_t* labels, 
     const unsigned int hw = (unsigned int)h * w, total = (unsigned int)BN * D * hw;
     FBBEV_LAUNCH(k_depth_loss_grad, (total + FBBEV_DL_THREADS - 1) / FBBEV_DL_THREADS, FBBEV_DL_THREADS, 0, (fbbev_rt_stream)stream_, probs,
                  labels, out_i, grad_loss, (unsigned int)D, hw, total, grad_probs);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ LiDAR points -> multi-view depth maps
+extern "C" int fbbev_points_to_depth(const float* points, int point_stride, const int32_t* offsets, int max_points, int B, int N,
+                                     const float* lidar2img, const float* post_rots, const float* post_trans, int H, int W,
+                                     int downsample, float depth_lo, float depth_hi, float* out, fbbev_stream_t stream_) {
+    if (!points || !offsets || !lidar2img || !post_rots || !post_trans || !out) return FBBEV_E_BADARG;
+    if (point_stride < 3 || downsample < 1 || max_points < 0 || B < 0 || N < 0 || H < 0 || W < 0) return FBBEV_E_BADARG;
+    if (!(depth_lo > 0.f) || depth_hi != depth_hi) return FBBEV_E_BADARG;          // a kept depth must be positive (and lo no NaN)
+    const int h = H / downsample, w = W / downsample;
+    if (h == 0 || w == 0 || B == 0 || N == 0) return 0;                            // nothing to write
+    if (depth_hi >= 100.f) return FBBEV_E_DEPTH_RANGE;
+    if ((long long)h * w >= (1ll << 24)) return FBBEV_E_MAP_SIZE;
+    const long long BN = (long long)B * N;
+    if (BN >= (1ll << 24)) return FBBEV_E_UNSUPPORTED;                             // BN * chunks < 2^31; BN * h * w < 2^48
+    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
+    const long long n = BN * h * w;
+    unsigned int* plane = reinterpret_cast<unsigned int*>(out);
+    const int e = fbbev_rt_memset_async(plane, 0, (size_t)n * sizeof(float), stream);
+    if (e) return e;
+    if (max_points == 0) return 0;                                                 // zeros are the resolved plane already
+    long long chunks = ((long long)max_points + FBBEV_PD_THREADS - 1) / FBBEV_PD_THREADS;
+    if (chunks > FBBEV_PD_MAX_CHUNKS) chunks = FBBEV_PD_MAX_CHUNKS;
+    FBBEV_LAUNCH(k_points_depth_splat, BN * chunks, FBBEV_PD_THREADS, 0, stream, points, point_stride, (const int*)offsets, N, (int)chunks,
+                 lidar2img, post_rots, post_trans, (float)downsample, h, w, depth_lo, depth_hi, plane);
+    FBBEV_CHECK_LAUNCH();
+    long long head = (long long)((16 - (reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) / 4;   // out is 4-byte aligned
+    if (head > n) head = n;
+    const long long nv = (n - head) / 4;
+    long long blocks = (nv + FBBEV_PD_THREADS - 1) / FBBEV_PD_THREADS;
+    if (blocks < 1) blocks = 1;
+    if (blocks > FBBEV_PD_RESOLVE_BLOCKS) blocks = FBBEV_PD_RESOLVE_BLOCKS;
+    FBBEV_LAUNCH(k_points_depth_resolve, blocks, FBBEV_PD_THREADS, 0, stream, plane, n, (int)head, nv);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

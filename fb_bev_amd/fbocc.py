@@ -83,6 +83,10 @@ class FBOCC(nn.Module):
         (occ_loss.lovasz_softmax_fused; no full-size softmax, error matrix or permutation is kept; default off);
         fused_depth_loss=True: the depth net's supervision loss (labels, BCE, mean) from one pass each way over the depth maps and
         the depth distribution (depth_net.depth_loss_fused; fp32 predictions on the GPU with linear bins; default off);
+        depth_from_points=True: forward_train(points=..., lidar2img=(B, N, 4, 4)) without gt_depth builds gt_depth on the device from
+        the LiDAR sweeps (points_depth.points_to_depth: a list of (P_i, >= 3) tensors, img_inputs' post_rots / post_trans, the image
+        size, the depth net's grid_config['depth'], downsample 1) instead of taking it from the loader; a gt_depth that is given
+        is used as it is; default off;
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -98,6 +102,7 @@ class FBOCC(nn.Module):
         self.depth_net = _build(depth_net, **cp, compute_dtype=_dtype(ex.get('depth_dtype')))
         if self.depth_net is not None and ex.get('fused_depth_loss') is not None:
             self.depth_net.fused_depth_loss = bool(ex['fused_depth_loss'])
+        self.depth_from_points = bool(ex.get('depth_from_points', False))
         fvt = FBViewTransform(forward_projection, backward_projection, readd=readd)
         self.forward_projection = fvt.forward_projection
         self.backward_projection = fvt.backward_projection
@@ -286,6 +291,13 @@ class FBOCC(nn.Module):
     def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
                       gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, gt_occupancy_flow=None,
                       **kwargs):
+        if self.depth_from_points:
+            lidar2img = kwargs.pop('lidar2img', None)                                                     # extract_feat never sees it
+            if (kwargs.get('gt_depth') is None and points is not None and lidar2img is not None and self.use_depth_supervision
+                    and self.depth_net is not None):
+                from .points_depth import points_to_depth
+                kwargs['gt_depth'] = points_to_depth(points, lidar2img, img_inputs[4], img_inputs[5], img_inputs[0].shape[-2],
+                                                     img_inputs[0].shape[-1], 1, self.depth_net.grid_config['depth'])
         results = self.extract_feat(points, img=img_inputs, img_metas=img_metas, **kwargs)
         losses = {}
         if self.occupancy_head is not None:

@@ -26,6 +26,8 @@ typedef void* fbbev_stream_t; /* hipStream_t */
 #define FBBEV_E_BADARG (-1)
 #define FBBEV_E_UNSUPPORTED (-2)
 #define FBBEV_E_WORKSPACE (-3)
+#define FBBEV_E_DEPTH_RANGE (-4) /* fbbev_points_to_depth: depth_hi >= 100 */
+#define FBBEV_E_MAP_SIZE (-5)    /* fbbev_points_to_depth: (H / ds) * (W / ds) >= 2^24 */
 
 /* flags word of the *_ex entry points.  FBBEV_FLAG_DETERMINISTIC: deterministic mode -- every gradient the call computes is
  * bit-identical from run to run (no float atomics: fixed-point integer sums, fixed-order reductions or owner-computes).  Without
@@ -1301,6 +1303,44 @@ int fbbev_depth_loss_fwd(const float* gt, int BN, int H, int W, int ds, const fl
  * BN*h*w >= 2^31 or BN*D*h*w >= 2^31. */
 int fbbev_depth_loss_grad(const float* probs, const int32_t* labels, const int32_t* out_i, const float* grad_loss, int BN, int D,
                           int h, int w, float* grad_probs, fbbev_stream_t stream);
+
+/* A LiDAR sweep to multi-view depth maps, gt_depth of fbbev_depth_loss_fwd (training; replaces PointToMultiViewDepth,
+ * mmdet3d/datasets/pipelines/loading.py:876-966: the projection of :951-957 and points2depthmap :883-907, a CPU pipeline step with
+ * an argsort per camera, and the (N, H, W) map through the loader).  A z-buffer: one projection and one integer atomic per point
+ * and camera, no sort.
+ *   points: rows of point_stride >= 3 floats (4-byte alignment is enough), the samples of the batch one after another; the first
+ *   three columns are read (nuScenes rows have 5).  offsets (B + 1) int32 in DEVICE memory: sample b owns rows offsets[b] ..
+ *   offsets[b + 1] - 1; a sample with no points is legal, its maps are zeros.  The entry does not read offsets on the host (no
+ *   synchronisation): max_points >= the largest per-sample count, which the caller knows, sizes the grid; threads past a sample's
+ *   count exit, and a sample longer than the capped grid (64 workgroups of 256 per sample and camera) is walked in a loop.  Rows
+ *   named by offsets must lie inside `points`; nothing checks that.
+ *   lidar2img (B, N, 4, 4) row-major (the last row is not read), post_rots (B, N, 3, 3), post_trans (B, N, 3), f32.
+ *   out (B, N, h, w) f32, h = H / downsample, w = W / downsample (integer division), contiguous, 4-byte alignment is enough:
+ *   EVERY element is written -- the nearest kept depth of the pixel, +0.0 where no point is kept.
+ * Arithmetic per point p and camera, M = lidar2img[b, n], R = post_rots[b, n], T = post_trans[b, n]; every step ONE correctly
+ * rounded fp32 operation (the division too: no fast-math), the dot products as fmaf chains like the f32 row kernels:
+ *     c_i = fmaf(M[i][2], p.z, fmaf(M[i][1], p.y, M[i][0] * p.x)) + M[i][3]          i = 0, 1, 2
+ *     (u, v, z) = (c_0 / c_2, c_1 / c_2, c_2)
+ *     q_i = fmaf(R[i][2], z, fmaf(R[i][1], v, R[i][0] * u)) + T[i]
+ *     x = rintf(q_0 / (float)downsample), y = rintf(q_1 / (float)downsample)         half to even, as torch.round
+ *     kept = x >= 0 && x < w && y >= 0 && y < h && q_2 < depth_hi && q_2 >= depth_lo  on floats: -0.0 is pixel 0; NaN, inf fail
+ *   The reference's matmul may associate a dot product otherwise (a BLAS decides); inputs whose products and sums are exact in fp32
+ *   give the same bits either way, others differ by the roundings of a three-term dot product.
+ *   out[b, n, y, x] = min of q_2 over the kept points of the pixel.  The reference keeps the first point of the pixel in the order of
+ *   an UNSTABLE argsort of fl32(rank + depth / 100): two kept points of a pixel whose keys round to the same float (closer than
+ *   1.5625 m from image row 187 on at width 704) tie, and it keeps either.  Rounding is monotone, so the minimum is always one of
+ *   the answers the reference may give, and it is the one that does not depend on the order of the points.
+ * Mechanism: `out` is zeroed through the runtime, a kept point does atomicMax(word, ~bits(q_2)) (no-return form; kept depths are
+ * positive and finite, so ~bits orders them inversely and 0 stays "no return"), a second kernel turns word into word ? ~word : 0 in
+ * place.  Integer maximum only: bit-identical from run to run.  No allocation, no workspace, no host synchronisation.
+ * Checked in this order.  FBBEV_E_BADARG: a null points / offsets / lidar2img / post_rots / post_trans / out, point_stride < 3,
+ * downsample < 1, a negative max_points / B / N / H / W, depth_lo not > 0 (or NaN), depth_hi NaN.  H / ds == 0, W / ds == 0 or
+ * B * N == 0: 0, no launch, nothing written.  FBBEV_E_DEPTH_RANGE: depth_hi >= 100; FBBEV_E_MAP_SIZE: h * w >= 2^24 -- beyond
+ * either the reference's own key no longer separates two pixels, there is nothing to be faithful to.  FBBEV_E_UNSUPPORTED:
+ * B * N >= 2^24.  max_points == 0: `out` is zeroed, 0. */
+int fbbev_points_to_depth(const float* points, int point_stride, const int32_t* offsets, int max_points, int B, int N,
+                          const float* lidar2img, const float* post_rots, const float* post_trans, int H, int W, int downsample,
+                          float depth_lo, float depth_hi, float* out, fbbev_stream_t stream);
 
 #ifdef __cplusplus
 }
