@@ -575,7 +575,38 @@ extern "C" int fbbev_lift_rank_build_cached(const float* frustum, const float* x
                                 (fbbev_rt_stream)stream_, cam_key, cache_state);
 }
 
-// ------------------------------------------------------------------------------ fused dense fwd
+// ------------------------------------------------------------------------------ view-transformation pooling
+// The lift-splat of the view transformation: the tile index over the ranked intervals, the dense forward that writes every voxel of
+// the volume exactly once, the Z-mean, the store-floor diagnostic and the fused backward.  Every entry fills the small records
+// below from its positional C arguments; everything under the entries works on those records.  Every entry strings its checks
+// together itself: their ORDER is part of the ABI (tests/test_abi_symbols.py pins it), and what a flags word launches is pinned by
+// tests/test_emu_pool_launch_record.py.
+//   entry                               output layout                        kernels                                       flag bits and knobs that route it
+//   fbbev_pool_tile_index[_cached]      tile table, (tiles + 1) x 2 ints     [k_tile_table_gate +] k_tile_lower_bound2     CHANNELS_LAST: flat tiles over B*Z*Y*X
+//                                       first / last interval per tile       memset + k_tile_scatter                       CHANNELS_LAST with tiles of 8 / 16 / 32
+//                                                                                                                          (_cached: UNSUPPORTED)
+//   fbbev_bev_pool_v2_dense_fwd[_add]   planes (B, C, Z, Y, X), strided,     k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16,   store bits 0-1 and 17, CPL8, CSPLIT, WG,
+//                                       fp32 / bf16 / fp16                   0, SPLIT, GU>                                 XCD_SWIZZLE + chunk, OUT_BF16 / OUT_F16,
+//                                                                                                                          SPLIT_LONG, GATHER8 (not with SPLIT_LONG)
+//                                       planes, fp32                         k_pool_fwd_dense_pipe<TV, CPL, 4, 256>        PIPE (fp32, 256 threads, `sc1 nt`, tiles
+//                                                                                                                          64 .. 256, not SPLIT_LONG); FBBEV_POOL_PIPE_TPW
+//                                       channels-last (B, Z, Y, X, C),       k_pool_fwd_dense_cl<TV, CPL, ST, 256>         CHANNELS_LAST (no addend, fp32); store bits,
+//                                       dense, fp32                          tiles of 8 / 16 / 32: k_pool_fwd_cl_small<ST> CPL8, XCD_SWIZZLE + chunk
+//   fbbev_bev_pool_v2_dense_fwd_rows    rows (B, Z*Y*X, C) of a strided      k_pool_fwd_dense_rows<TV, CPL, ST, 256, ET>   OUT_BF16 / OUT_F16 (then CPL 8, `sc1 nt`),
+//                                       slot, fp32 / bf16 / fp16                                                           store bits, CPL8, XCD_SWIZZLE + chunk
+//   fbbev_diag_pool_store_floor         planes, zeros                        k_pool_fwd_dense2<128, 8, 4, 256, OT, T16,    the one product route only; OUT_BF16,
+//                                                                            MODE>                                         CSPLIT, XCD_SWIZZLE + chunk; `mode`
+//   fbbev_lift_splat_fused              as fbbev_bev_pool_v2_dense_fwd       rank build, fbbev_nchw_to_nhwc, the tile      as the tile index and the dense forward
+//                                                                            index and the dense forward's
+//   fbbev_pool_zmean[_split|_rows]      (B, C, Y, X) or rows (B, Y*X, C)     k_pool_zmean<TV, CPL, 256>                    CPL8, CSPLIT; z_groups
+//                                                                            [+ k_pool_zmean_reduce], or                   FBBEV_ZMEAN_COL=1 (planes, one group, Z <= 64)
+//                                                                            k_pool_zmean_col<TV, CPL, 256>
+//   fbbev_bev_pool_v2_dense_bwd[_z]     depth_grad, feat_grad                memset + k_point_row_table,                   none.  C > 128 with C % 8 != 0 is refused
+//                                                                            k_tile_lower_bound2, k_pool_bwd_rows<128>,    (UNSUPPORTED) only AFTER the first three
+//                                                                            k_pool_bwd_pixel<4 | 8>                       launches, where the pixel kernel is chosen
+//   (behind the cross-attention family)
+//   fbbev_pool_dense_workspace_bytes, fbbev_pool_dense_bwd_workspace_bytes, fbbev_lift_splat_fused_ws_bytes / _ws_offsets: host functions, no launch
+
 static inline int pick_tile(int tile_voxels) {
     switch (tile_voxels) { case 64: case 128: case 256: case 512: case 1024: return tile_voxels; default: return 64; }
 }
@@ -584,6 +615,135 @@ static inline int small_tile_shift(int tile_voxels) {
     switch (tile_voxels) { case 8: return 3; case 16: return 4; case 32: return 5; default: return 0; }
 }
 
+// The gather operands: depth (B, N, D, H, W), channels-last features and the ranked index arrays of the intervals
+struct pool_gather {
+    const float *depth, *feat;
+    const int32_t *rd, *rf, *irank, *starts, *lengths;
+};
+static inline bool pool_gather_present(const pool_gather& g) { return g.depth && g.feat && g.rd && g.rf && g.irank && g.starts && g.lengths; }
+#define FBBEV_POOL_GATHER(g) (g).depth, (g).feat, (g).rd, (g).rf, (g).irank, (g).starts, (g).lengths   /* as the kernels take them */
+
+// The grid: yx = Y * X voxels of a plane, nvox = B * Z * Y * X of them in all -- saturated at 2^31, beyond which every entry only
+// asks whether a flat voxel index still fits an int; both 0 unless every dimension is positive (an entry without channels says C = 1)
+struct pool_grid {
+    int B, C, Z, Y, X;
+    long long yx, nvox;
+};
+static inline bool pool_grid_positive(const pool_grid& g) { return g.B > 0 && g.C > 0 && g.Z > 0 && g.Y > 0 && g.X > 0; }
+static inline bool pool_grid_fits_int(const pool_grid& g) { return g.nvox < (1ll << 31); }
+static inline pool_grid pool_grid_of(int B, int C, int Z, int Y, int X) {
+    pool_grid g = {B, C, Z, Y, X, 0, 0};
+    if (!pool_grid_positive(g)) return g;
+    const long long lim = 1ll << 31;
+    g.yx = (long long)Y * X;
+    const long long zyx = g.yx < lim ? Z * g.yx : lim;
+    g.nvox = zyx < lim ? B * zyx : lim;
+    return g;
+}
+
+// The flags word of include/fbbev.h, decoded once.  What depends on the shape or on the kernel is a function of it.
+struct pool_flags {
+    int st_bits;                                            // store policy field: bits 0-1, bit 17 as bit 2
+    bool bf16, f16;                                         // element type of the output (both: every entry that stores 16 bits refuses it)
+    bool cpl8;                                              // the WISH for 8 channels per lane: cpl() grants it
+    int csplit_field, wg, chunk_field;
+    bool xcd_swizzle, channels_last, pipe, split_long;
+    bool gather8;                                           // ignored when split_long is set
+    // store cache policy: 0 plain, 1 nontemporal, anything else `sc1 nt` (4), the measured best
+    int store() const { return st_bits == 0 ? 0 : st_bits == 1 ? 1 : 4; }
+    int et() const { return bf16 ? 1 : f16 ? 2 : 0; }       // FBBEV_ELEM_*
+    int threads() const { return wg == 1 ? 128 : 256; }
+    // workgroups the channel range is split over: field 0xF means 20, what does not divide C into multiples of 4 means 1
+    int csplit(int C) const {
+        int n = csplit_field == 0xF ? 20 : csplit_field;
+        if (n < 1 || C % (4 * n) != 0) n = 1;
+        return n;
+    }
+    int cpl(int CC) const { return cpl8 && CC % 8 == 0 ? 8 : 4; }   // channels per lane for CC channels per workgroup
+    // XCD order: 0 = off, else 1 + log2(tiles per chunk) with the kernel's own default for a chunk field of 0 (see the call sites)
+    int swizzle(int default_chunk) const { return xcd_swizzle ? (chunk_field ? chunk_field : default_chunk) + 1 : 0; }
+};
+static inline pool_flags pool_flags_of(int flags) {
+    pool_flags f;
+    f.st_bits = (flags & FBBEV_POOL_STORE_MASK) | ((flags >> FBBEV_POOL_STORE_HI_SHIFT) & 1) << 2;
+    f.bf16 = (flags & FBBEV_POOL_OUT_BF16) != 0;
+    f.f16 = (flags & FBBEV_POOL_OUT_F16) != 0;
+    f.cpl8 = (flags & FBBEV_POOL_CPL8) != 0;
+    f.csplit_field = (flags >> FBBEV_POOL_CSPLIT_SHIFT) & 0xF;
+    f.wg = (flags >> FBBEV_POOL_WG_SHIFT) & 0x3;
+    f.chunk_field = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
+    f.xcd_swizzle = (flags & FBBEV_POOL_XCD_SWIZZLE) != 0;
+    f.channels_last = (flags & FBBEV_POOL_CHANNELS_LAST) != 0;
+    f.pipe = (flags & FBBEV_POOL_PIPE) != 0;
+    f.split_long = (flags & FBBEV_POOL_SPLIT_LONG) != 0;
+    f.gather8 = (flags & FBBEV_POOL_GATHER8) != 0 && !f.split_long;
+    return f;
+}
+
+// a swizzled grid is rounded up to whole groups of 8 chunks (the kernel skips what lies past n_blocks)
+static inline long long pool_swizzled_grid(long long n_blocks, int swizzle) {
+    if (!swizzle) return n_blocks;
+    const long long g = 8ll << (swizzle - 1);
+    return (n_blocks + g - 1) / g * g;
+}
+// the tile table: two ints per tile and one pair past the end
+static inline size_t pool_tile_table_bytes(long long n_tiles) { return (size_t)(n_tiles + 1) * 8; }
+// LDS of a tile's staged index (what the channels-last kernels use alone), and with the value tile of CC channels in fp32
+// [CC][TV + 4] or in 16 bits [CC][TV + 8]
+static inline size_t pool_index_lds_bytes(int TV) { return (3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(int); }
+static inline size_t pool_planar_lds_bytes(int CC, int TV) { return (size_t)CC * (TV + 4) * sizeof(float) + pool_index_lds_bytes(TV); }
+static inline size_t pool_planar_lds16_bytes(int CC, int TV) { return (size_t)CC * (TV + 8) * 2 + pool_index_lds_bytes(TV); }
+// The strides of a (B, C, Z, Y, X) volume, forward output and backward gradient alike: 0 = contiguous; planes that would overlap
+// or strides that are no multiple of 4 elements are FBBEV_E_BADARG
+struct pool_strides { long long b, c; int err; };
+static inline pool_strides pool_volume_strides(long long stride_b, long long stride_c, const pool_grid& g) {
+    pool_strides s = {stride_b, stride_c, 0};
+    if (s.c == 0) s.c = g.Z * g.yx;
+    if (s.b == 0) s.b = g.C * s.c;
+    if (s.c < g.Z * g.yx || s.b < g.C * s.c || s.c % 4 != 0 || s.b % 4 != 0) s.err = FBBEV_E_BADARG;
+    return s;
+}
+
+// What every forward entry is given besides its output
+struct pool_call {
+    pool_gather in;
+    pool_grid g;
+    const void* tile_ws; size_t tile_ws_bytes; int tile_voxels;
+    pool_flags f;
+    fbbev_rt_stream stream;
+};
+// One launch of a dense kernel: n_blocks workgroups of work (the grid is pool_swizzled_grid of them)
+struct pool_launch {
+    pool_gather in; const int* tile_meta; fbbev_rt_stream stream;
+    int C, Z, yx, zyx, nvox, tpp, csplit, swizzle;          // tpp: tiles per plane
+    long long n_blocks; size_t lds;
+    long long out_stride_b, out_stride_c, addend_stride;    // out_stride_c: planes; addend_stride: rows
+    const float* addend;                                    // planes: (B, C, Y, X) added to every z; rows: (B, Y*X, C); may be null
+    void* out;
+};
+static inline pool_launch pool_launch_of(const pool_call& c) {
+    pool_launch a = {};
+    a.in = c.in; a.tile_meta = static_cast<const int*>(c.tile_ws); a.stream = c.stream;
+    a.C = c.g.C; a.Z = c.g.Z;
+    return a;
+}
+
+// The family's template ladders: the statement(s) after the value, once per candidate, with `constexpr int NAME` set to the candidate
+// the value equals (the last candidate where it equals none) -- a launch names its instantiation with it.  A `return` inside leaves
+// the enclosing function.  Only the combinations a ladder spells out are instantiated, so a route built for fewer of them has its own.
+#define FBBEV_POOL_WITH(NAME, v, V0, V1, ...) \
+    do { if ((v) == (V0)) { constexpr int NAME = V0; __VA_ARGS__; } else { constexpr int NAME = V1; __VA_ARGS__; } } while (0)
+#define FBBEV_POOL_WITH3(NAME, v, V0, V1, V2, ...)                                                                           \
+    do { if ((v) == (V0)) { constexpr int NAME = V0; __VA_ARGS__; } else FBBEV_POOL_WITH(NAME, v, V1, V2, __VA_ARGS__); } while (0)
+#define FBBEV_POOL_TILE3(tv, ...) FBBEV_POOL_WITH3(TV, tv, 64, 128, 256, __VA_ARGS__)
+#define FBBEV_POOL_TILE(tv, ...)                                                                                             \
+    do { if ((tv) == 64) { constexpr int TV = 64; __VA_ARGS__; } else if ((tv) == 128) { constexpr int TV = 128; __VA_ARGS__; } \
+         else FBBEV_POOL_WITH3(TV, tv, 256, 512, 1024, __VA_ARGS__); } while (0)
+#define FBBEV_POOL_CPL(cpl, ...) FBBEV_POOL_WITH(CPL, cpl, 8, 4, __VA_ARGS__)
+#define FBBEV_POOL_ST(st, ...) FBBEV_POOL_WITH3(ST, st, 0, 1, 4, __VA_ARGS__)
+#define FBBEV_POOL_NT(nt, ...) FBBEV_POOL_WITH(NT, nt, 128, 256, __VA_ARGS__)
+#define FBBEV_POOL_ET16(et, ...) FBBEV_POOL_WITH(ET, et, 1, 2, __VA_ARGS__)
+
 extern "C" size_t fbbev_pool_dense_workspace_bytes(int B, int Z, int Y, int X) {
     if (B <= 0 || Z <= 0 || Y <= 0 || X <= 0) return 256;
     const long long yx = (long long)Y * X;
@@ -591,17 +751,57 @@ extern "C" size_t fbbev_pool_dense_workspace_bytes(int B, int Z, int Y, int X) {
     return align_up((size_t)(tiles + 2) * 8, 256);                // two ints per tile
 }
 
-static int pool_tile_index_impl(const int32_t* interval_rank, const int32_t* interval_starts,
-                                const int32_t* counts, int n_intervals_max, int B, int Z, int Y,
-                                int X, int tile_voxels, int flags, void* tile_ws, size_t tile_ws_bytes,
-                                fbbev_stream_t stream_, const int32_t* skip);
+// ---- the tile index
+struct pool_index_args {
+    const int32_t *irank, *starts, *counts; int n_max;
+    pool_grid g;                                            // C = 1
+    int tile_voxels; bool channels_last;
+    void* tile_ws; size_t tile_ws_bytes;
+    fbbev_rt_stream stream;
+    const int32_t* skip;                                    // device flag: nonzero keeps the table as it is (the cached entry's gate); may be null
+};
+static int pool_tile_index(const pool_index_args& t) {
+    const pool_grid& g = t.g;
+    if (!pool_grid_positive(g) || t.n_max < 0) return FBBEV_E_BADARG;
+    if (!t.irank || !t.starts || !t.counts || !t.tile_ws) return FBBEV_E_BADARG;
+    if (!pool_grid_fits_int(g)) return FBBEV_E_UNSUPPORTED;
+    if (t.channels_last && small_tile_shift(t.tile_voxels)) {
+        // small tiles: scatter-built table (first/last interval per tile), -1 = empty
+        const int sh = small_tile_shift(t.tile_voxels);
+        const long long nt = (g.nvox + (1 << sh) - 1) >> sh;
+        if (t.tile_ws_bytes < (size_t)nt * 8) return FBBEV_E_WORKSPACE;
+        int* first = static_cast<int*>(t.tile_ws);
+        int e = fbbev_rt_memset_async(first, 0xFF, (size_t)nt * 8, t.stream);
+        if (e) return e;
+        long long blocks = ((long long)t.n_max + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        if (blocks < 1) blocks = 1;
+        FBBEV_LAUNCH(k_tile_scatter, blocks, 256, 0, t.stream, t.irank, t.counts, t.n_max, sh, g.nvox, first, first + nt);
+        FBBEV_CHECK_LAUNCH();
+        return 0;
+    }
+    const int TV = pick_tile(t.tile_voxels);
+    int tiles_per_plane = (int)((g.yx + TV - 1) / TV);
+    long long n_tiles = (long long)g.B * g.Z * tiles_per_plane;
+    long long plane = g.yx;
+    if (t.channels_last) {   // flat tiling of the whole (B*Z*Y*X) rank space
+        plane = g.nvox;
+        n_tiles = (plane + TV - 1) / TV;
+        tiles_per_plane = (int)n_tiles + 1;   // every tile index t (incl. t == n_tiles) stays in "plane" 0
+    }
+    if (t.tile_ws_bytes < pool_tile_table_bytes(n_tiles)) return FBBEV_E_WORKSPACE;
+    FBBEV_LAUNCH(k_tile_lower_bound2, (n_tiles + 1 + 255) / 256, 256, 0, t.stream, (int)n_tiles, tiles_per_plane, (int)plane, TV,
+                 t.irank, t.starts, t.counts, t.n_max, t.skip, static_cast<int*>(t.tile_ws));
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int fbbev_pool_tile_index(const int32_t* interval_rank, const int32_t* interval_starts,
                                      const int32_t* counts, int n_intervals_max, int B, int Z, int Y,
                                      int X, int tile_voxels, int flags, void* tile_ws, size_t tile_ws_bytes,
                                      fbbev_stream_t stream_) {
-    return pool_tile_index_impl(interval_rank, interval_starts, counts, n_intervals_max, B, Z, Y, X, tile_voxels, flags,
-                                tile_ws, tile_ws_bytes, stream_, nullptr);
+    return pool_tile_index({interval_rank, interval_starts, counts, n_intervals_max, pool_grid_of(B, 1, Z, Y, X), tile_voxels,
+                            pool_flags_of(flags).channels_last, tile_ws, tile_ws_bytes, (fbbev_rt_stream)stream_, nullptr});
 }
 
 extern "C" int fbbev_pool_tile_index_cached(const int32_t* interval_rank, const int32_t* interval_starts,
@@ -610,269 +810,149 @@ extern "C" int fbbev_pool_tile_index_cached(const int32_t* interval_rank, const 
                                             const int32_t* cache_state, int32_t* table_gate,
                                             fbbev_stream_t stream_) {
     if (!cache_state || !table_gate) return FBBEV_E_BADARG;
-    if ((flags & FBBEV_POOL_CHANNELS_LAST) && small_tile_shift(tile_voxels)) return FBBEV_E_UNSUPPORTED;
-    // keep THIS table only if the index set is unchanged and the table was built for this very build
+    if (pool_flags_of(flags).channels_last && small_tile_shift(tile_voxels)) return FBBEV_E_UNSUPPORTED;
+    // keep THIS table only if the index set is unchanged and the table was built for this very build; the gate is launched before
+    // the shared argument checks run
     FBBEV_LAUNCH(k_tile_table_gate, 1, 1, 0, (fbbev_rt_stream)stream_, cache_state, table_gate);
     FBBEV_CHECK_LAUNCH();
-    return pool_tile_index_impl(interval_rank, interval_starts, counts, n_intervals_max, B, Z, Y, X, tile_voxels, flags,
-                                tile_ws, tile_ws_bytes, stream_, table_gate + 1);
+    return pool_tile_index({interval_rank, interval_starts, counts, n_intervals_max, pool_grid_of(B, 1, Z, Y, X), tile_voxels,
+                            pool_flags_of(flags).channels_last, tile_ws, tile_ws_bytes, (fbbev_rt_stream)stream_, table_gate + 1});
 }
 
-static int pool_tile_index_impl(const int32_t* interval_rank, const int32_t* interval_starts,
-                                const int32_t* counts, int n_intervals_max, int B, int Z, int Y,
-                                int X, int tile_voxels, int flags, void* tile_ws, size_t tile_ws_bytes,
-                                fbbev_stream_t stream_, const int32_t* skip) {
-    if (B <= 0 || Z <= 0 || Y <= 0 || X <= 0 || n_intervals_max < 0) return FBBEV_E_BADARG;
-    if (!interval_rank || !interval_starts || !counts || !tile_ws) return FBBEV_E_BADARG;
-    const long long yx = (long long)Y * X;
-    if ((long long)B * Z * yx >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if ((flags & FBBEV_POOL_CHANNELS_LAST) && small_tile_shift(tile_voxels)) {
-        // small tiles: scatter-built table (first/last interval per tile), -1 = empty
-        const int sh = small_tile_shift(tile_voxels);
-        const long long nvox = (long long)B * Z * yx;
-        const long long nt = (nvox + (1 << sh) - 1) >> sh;
-        if (tile_ws_bytes < (size_t)nt * 8) return FBBEV_E_WORKSPACE;
-        int* first = static_cast<int*>(tile_ws);
-        int e = fbbev_rt_memset_async(first, 0xFF, (size_t)nt * 8, (fbbev_rt_stream)stream_);
-        if (e) return e;
-        long long blocks = ((long long)n_intervals_max + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
-        FBBEV_LAUNCH(k_tile_scatter, blocks, 256, 0, (fbbev_rt_stream)stream_, interval_rank, counts,
-                     n_intervals_max, sh, nvox, first, first + nt);
-        FBBEV_CHECK_LAUNCH();
-        return 0;
-    }
-    const int TV = pick_tile(tile_voxels);
-    int tiles_per_plane = (int)((yx + TV - 1) / TV);
-    long long n_tiles = (long long)B * Z * tiles_per_plane;
-    long long plane = yx;
-    if (flags & FBBEV_POOL_CHANNELS_LAST) {   // flat tiling of the whole (B*Z*Y*X) rank space
-        plane = (long long)B * Z * yx;
-        n_tiles = (plane + TV - 1) / TV;
-        tiles_per_plane = (int)n_tiles + 1;   // every tile index t (incl. t == n_tiles) stays in "plane" 0
-    }
-    if (tile_ws_bytes < (size_t)(n_tiles + 1) * 8) return FBBEV_E_WORKSPACE;
-    FBBEV_LAUNCH(k_tile_lower_bound2, (n_tiles + 1 + 255) / 256, 256, 0, (fbbev_rt_stream)stream_,
-                 (int)n_tiles, tiles_per_plane, (int)plane, TV, interval_rank, interval_starts, counts,
-                 n_intervals_max, skip, static_cast<int*>(tile_ws));
-    FBBEV_CHECK_LAUNCH();
-    return 0;
+// ---- the dense forward on planes (and, with FBBEV_POOL_CHANNELS_LAST, on dense voxel rows)
+// channels-last with tiles of 8 / 16 / 32 voxels (1 << sh): the scatter-built table, a lane per 4 channels of a voxel
+static int pool_fwd_cl_small(const pool_call& c, float* out, int sh) {
+    const long long nvox = c.g.nvox, nt = (nvox + (1 << sh) - 1) >> sh;
+    if (c.tile_ws_bytes < (size_t)nt * 8) return FBBEV_E_WORKSPACE;
+    int threads = (c.g.C / 4) << sh;
+    if (threads > 1024) return FBBEV_E_UNSUPPORTED;
+    threads = (threads + 63) / 64 * 64;
+    // a chunk field of 0 means chunks of one tile, which is the plain round-robin: the sweep these tiles were measured with starts there
+    // (profiles/r01_exp_pool_cl_small.jsonl, swz0 .. swz6)
+    const int swz = c.f.swizzle(0);
+    const long long grid = pool_swizzled_grid(nt, swz);
+    const int* first = static_cast<const int*>(c.tile_ws);
+    FBBEV_POOL_ST(c.f.store(), FBBEV_LAUNCH(k_pool_fwd_cl_small<ST>, grid, threads, 0, c.stream, c.g.C, sh, nvox, (int)nt, swz,
+                                            FBBEV_POOL_GATHER(c.in), first, first + nt, out));
+    return fbbev_rt_last_error();
 }
 
-struct dense2_args {
-    long long n_blocks; size_t lds; fbbev_rt_stream stream; int C, Z, yx, tpp, csplit, swizzle;
-    long long stride_b, stride_c;
-    const float *depth, *feat; const int32_t *rd, *rf, *irank, *starts, *lengths; const int* tile_meta;
-    const float* addend = nullptr;   // optional (B,C,Y,X) broadcast-over-z add in the dense2 epilogue
-    float* out;
-    bool split = false;              // FBBEV_POOL_SPLIT_LONG: long intervals summed by the whole workgroup (tolerance mode)
-    bool gather8 = false;            // FBBEV_POOL_GATHER8: eight points per gather batch (experiment knob, same bits)
-};
+// channels-last with flat tiles of tv voxels over the whole rank space: a linear store stream, no LDS value tile
+static int pool_fwd_cl(const pool_call& c, float* out, int tv) {
+    const int C = c.g.C, cpl = c.f.cpl(C), st = c.f.store();
+    if (256 / (C / cpl) < 1) return FBBEV_E_UNSUPPORTED;
+    const long long nvox = c.g.nvox, n_blocks = (nvox + tv - 1) / tv;
+    if (c.tile_ws_bytes < pool_tile_table_bytes(n_blocks)) return FBBEV_E_WORKSPACE;
+    const size_t lds = pool_index_lds_bytes(tv);
+    // chunks of 16 tiles where the field is 0: the smaller of the two sizes the flat tiles were swept with (profiles/r01_exp_pool_cl.jsonl)
+    const int swz = c.f.swizzle(4);
+    const long long grid = pool_swizzled_grid(n_blocks, swz);
+    const int* meta = static_cast<const int*>(c.tile_ws);
+    FBBEV_POOL_TILE(tv, FBBEV_POOL_CPL(cpl, FBBEV_POOL_ST(st, FBBEV_LAUNCH((k_pool_fwd_dense_cl<TV, CPL, ST, 256>), grid, 256, lds, c.stream, C, (int)nvox,
+                                                                           (int)n_blocks, swz, FBBEV_POOL_GATHER(c.in), meta, out))));
+    return fbbev_rt_last_error();
+}
+
+// FBBEV_POOL_PIPE: a workgroup walks a run of tpw tiles, the next tile's index staged while the current one is summed
+static int pool_fwd_pipe(pool_launch a, long long n_tiles, int tv, int cpl) {
+    // tiles per workgroup: enough to amortise the pipeline's fill, few enough to keep >= ~8 workgroups per CU's worth of runs
+    FBBEV_KNOB_ONCE(int, tpw_env, fbbev_env_int("FBBEV_POOL_PIPE_TPW", 0));   // tuning knob (the emulator tests switch the run length)
+    int tpw = tpw_env > 0 ? (tpw_env > 64 ? 64 : tpw_env) : 4;
+    if (tpw_env <= 0) while (tpw > 1 && (n_tiles / tpw) * a.csplit < 2048) tpw >>= 1;
+    const long long groups = (n_tiles + tpw - 1) / tpw;
+    a.n_blocks = groups * a.csplit;
+    a.lds = pool_planar_lds_bytes(a.C / a.csplit, tv) + pool_index_lds_bytes(tv);   // a second staged index
+    if (a.lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
+    const long long grid = pool_swizzled_grid(a.n_blocks, a.swizzle);
+    FBBEV_POOL_TILE3(tv, FBBEV_POOL_CPL(cpl, FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense_pipe<TV, CPL, 4, 256>), grid, 256, a.lds, a.stream, a.C, a.Z,
+                                                                  a.yx, a.tpp, a.csplit, (int)a.n_blocks, a.swizzle, tpw, (int)n_tiles,
+                                                                  a.out_stride_b, a.out_stride_c, FBBEV_POOL_GATHER(a.in), a.tile_meta,
+                                                                  a.addend, static_cast<float*>(a.out))));
+    return fbbev_rt_last_error();
+}
 
 #define FBBEV_POOL_SPLIT_LEN 32      // points above which an interval is split over the lane groups in tolerance mode
-template <int TV, int CPL, int ST, int NT, int OT, bool T16 = false, int SPLIT = 0, int GU = 4>
-static int launch_dense2(const dense2_args& a) {
-    size_t lds = a.lds;
-    if (SPLIT > 0) lds += ((size_t)TV + 4) * sizeof(int) + (size_t)FBBEV_POOL_SPLIT_GROUPS * (a.C / a.csplit) * sizeof(float);   // long-interval list + partial sums
-    if (T16)                                   // 16-bit tile [CC][TV + 8] instead of fp32 [CC][TV + 4]
-        lds = (size_t)(a.C / a.csplit) * (TV + 8) * 2 + ((size_t)3 * TV + 2 * FBBEV_NP_STAGE) * sizeof(int);
-    long long grid = a.n_blocks;
-    if (a.swizzle) {  // round up to whole groups of 8 chunks
-        const long long g = 8ll << (a.swizzle - 1);
-        grid = (a.n_blocks + g - 1) / g * g;
-    }
-    FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16, 0, SPLIT, GU>), grid, NT, lds, a.stream, a.C, a.Z, a.yx, a.tpp,
-                         a.csplit, (int)a.n_blocks, a.swizzle, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out);
+template <int TV, int CPL, int ST, int NT, int OT, bool T16, int SPLIT, int GU>
+static int pool_launch_dense2(const pool_launch& a) {
+    FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense2<TV, CPL, ST, NT, OT, T16, 0, SPLIT, GU>), pool_swizzled_grid(a.n_blocks, a.swizzle), NT, a.lds,
+                         a.stream, a.C, a.Z, a.yx, a.tpp, a.csplit, (int)a.n_blocks, a.swizzle, a.out_stride_b, a.out_stride_c,
+                         FBBEV_POOL_GATHER(a.in), a.tile_meta, a.addend, static_cast<float*>(a.out));
     return fbbev_rt_last_error();
 }
 
-template <int TV, int CPL, int ST>
-static int launch_dense2_nt(int nt, int ot, const dense2_args& a) {
-    if (a.split) {                // tolerance mode: fp32 volume, default store policy, 256 threads, 64- / 128-voxel tiles
-        if constexpr (ST == 4 && (TV == 64 || TV == 128)) {
-            if (ot == 0 && nt == 256) return launch_dense2<TV, CPL, 4, 256, 0, false, FBBEV_POOL_SPLIT_LEN>(a);
-        }
-        return FBBEV_E_UNSUPPORTED;
-    }
-    if (a.gather8) {              // experiment knob: fp32 volume, default store policy, 256 threads, 64- / 128-voxel tiles
-        if constexpr (ST == 4 && (TV == 64 || TV == 128)) {
-            if (ot == 0 && nt == 256) return launch_dense2<TV, CPL, 4, 256, 0, false, 0, 8>(a);
-        }
-        return FBBEV_E_UNSUPPORTED;
-    }
-    if constexpr (ST == 4) {      // 16-bit output storage is built for the default store policy only
-        if (ot != 0 && !a.addend && nt == 256)        // no epilogue add: the LDS tile itself is 16-bit (see the kernel)
-            return ot == 1 ? launch_dense2<TV, CPL, 4, 256, 1, true>(a) : launch_dense2<TV, CPL, 4, 256, 2, true>(a);
-        if (ot == 1) return nt == 128 ? launch_dense2<TV, CPL, 4, 128, 1>(a) : launch_dense2<TV, CPL, 4, 256, 1>(a);
-        if (ot == 2) return nt == 128 ? launch_dense2<TV, CPL, 4, 128, 2>(a) : launch_dense2<TV, CPL, 4, 256, 2>(a);
-    }
-    return nt == 128 ? launch_dense2<TV, CPL, ST, 128, 0>(a) : launch_dense2<TV, CPL, ST, 256, 0>(a);
-}
-
-template <int TV, int CPL, int ST, int NT>
-static int launch_dense_cl(const dense2_args& a) {
-    long long grid = a.n_blocks;
-    if (a.swizzle) {
-        const long long g = 8ll << (a.swizzle - 1);
-        grid = (a.n_blocks + g - 1) / g * g;
-    }
-    FBBEV_LAUNCH((k_pool_fwd_dense_cl<TV, CPL, ST, NT>), grid, NT, a.lds, a.stream, a.C, a.yx, (int)a.n_blocks,
-                 a.swizzle, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.out);
-    return fbbev_rt_last_error();
-}
-
+// The plain route for one tile size and lane shape: `a` is complete but for the LDS of the routes that size their own.  (A template
+// of its own, not one ladder per route: the instantiations of a tile size stay together, in this order, in the code object.)
 template <int TV, int CPL>
-static int launch_dense_cl_st(int st, const dense2_args& a) {
-    switch (st) {
-        case 0: return launch_dense_cl<TV, CPL, 0, 256>(a);
-        case 1: return launch_dense_cl<TV, CPL, 1, 256>(a);
-        default: return launch_dense_cl<TV, CPL, 4, 256>(a);
-    }
-}
-
-// store cache policy: 0 plain, 1 nontemporal, anything else -> `sc1 nt` (4), the measured best
-template <int TV, int CPL>
-static int launch_dense2_st(int st, int nt, int ot, const dense2_args& a) {
-    if (ot != 0) return launch_dense2_nt<TV, CPL, 4>(nt, ot, a);
-    switch (st) {
-        case 0: return launch_dense2_nt<TV, CPL, 0>(nt, 0, a);
-        case 1: return launch_dense2_nt<TV, CPL, 1>(nt, 0, a);
-        default: return launch_dense2_nt<TV, CPL, 4>(nt, 0, a);
-    }
-}
-
-static int pool_dense_fwd_impl(const float* depth, const float* feat,
-                               const int32_t* ranks_depth, const int32_t* ranks_feat,
-                               const int32_t* interval_rank, const int32_t* interval_starts,
-                               const int32_t* interval_lengths, int B, int C, int Z, int Y,
-                               int X, float* out, long long out_stride_b, long long out_stride_c,
-                               const void* tile_ws, size_t tile_ws_bytes, int tile_voxels,
-                               int flags, const float* addend, fbbev_stream_t stream_) {
-    if (B <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
-    if (!depth || !feat || !ranks_depth || !ranks_feat || !interval_rank || !interval_starts ||
-        !interval_lengths || !out || !tile_ws) return FBBEV_E_BADARG;
-    const long long yx = (long long)Y * X;
-    if (C % 4 != 0 || C > 256 || yx % 4 != 0 || !aligned16(out) || !aligned16(feat)) return FBBEV_E_UNSUPPORTED;
-    if ((long long)B * Z * yx >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (out_stride_c == 0) out_stride_c = (long long)Z * yx;            // contiguous (B,C,Z,Y,X)
-    if (out_stride_b == 0) out_stride_b = (long long)C * out_stride_c;
-    if (out_stride_c < (long long)Z * yx || out_stride_b < (long long)C * out_stride_c || out_stride_c % 4 != 0 ||
-        out_stride_b % 4 != 0) return FBBEV_E_BADARG;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    const int TV = pick_tile(tile_voxels);
-    const int tiles_per_plane = (int)((yx + TV - 1) / TV);
-    const long long n_tiles = (long long)B * Z * tiles_per_plane;
-    if (tile_ws_bytes < (size_t)(n_tiles + 1) * 8) return FBBEV_E_WORKSPACE;
-    const int st = (flags & FBBEV_POOL_STORE_MASK) | ((flags >> FBBEV_POOL_STORE_HI_SHIFT) & 1) << 2;
-    const int ot = (flags & FBBEV_POOL_OUT_BF16) ? 1 : ((flags & FBBEV_POOL_OUT_F16) ? 2 : 0);
-    if (ot != 0) {   // 16-bit storage: 8 elements per 16-byte store
-        if ((flags & FBBEV_POOL_OUT_BF16) && (flags & FBBEV_POOL_OUT_F16)) return FBBEV_E_BADARG;
-        if (flags & FBBEV_POOL_CHANNELS_LAST) return FBBEV_E_UNSUPPORTED;
-        if (yx % 8 != 0 || out_stride_c % 8 != 0 || out_stride_b % 8 != 0) return FBBEV_E_UNSUPPORTED;
-    }
-    if (addend && ((flags & FBBEV_POOL_CHANNELS_LAST) || !aligned16(addend))) return FBBEV_E_UNSUPPORTED;
-    if (flags & FBBEV_POOL_CHANNELS_LAST) {
-        // out is (B,Z,Y,X,C) contiguous: flat tiles, linear store stream, no LDS value tile
-        if (out_stride_b != (long long)C * Z * yx || out_stride_c != (long long)Z * yx) return FBBEV_E_BADARG;
-        const long long nvox = (long long)B * Z * yx;
-        if (const int sh = small_tile_shift(tile_voxels)) {
-            const long long nt = (nvox + (1 << sh) - 1) >> sh;
-            if (tile_ws_bytes < (size_t)nt * 8) return FBBEV_E_WORKSPACE;
-            int threads = (C / 4) << sh;
-            if (threads > 1024) return FBBEV_E_UNSUPPORTED;
-            threads = (threads + 63) / 64 * 64;
-            int swz = 0;
-            if (flags & FBBEV_POOL_XCD_SWIZZLE) {
-                int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
-                swz = lg + 1;            // lg == 0 -> chunks of one tile (== plain round-robin)
+static int pool_fwd_planar(pool_launch a, const pool_flags& f) {
+    const int CC = a.C / a.csplit, nt = f.threads(), et = f.et();
+    const int st = et != 0 ? 4 : f.store();                 // 16-bit output storage is built for the default store policy only
+    if (f.split_long || f.gather8) {
+        // tolerance mode (long intervals summed by the whole workgroup) and the eight-points-per-gather-batch experiment (same
+        // bits): fp32 volume, default store policy, 256 threads, 64- / 128-voxel tiles
+        if constexpr (TV == 64 || TV == 128) {
+            if (st == 4 && et == 0 && nt == 256) {
+                if (f.split_long) {
+                    a.lds += ((size_t)TV + 4) * sizeof(int) + (size_t)FBBEV_POOL_SPLIT_GROUPS * CC * sizeof(float);   // long-interval list + partial sums
+                    return pool_launch_dense2<TV, CPL, 4, 256, 0, false, FBBEV_POOL_SPLIT_LEN, 4>(a);
+                }
+                return pool_launch_dense2<TV, CPL, 4, 256, 0, false, 0, 8>(a);
             }
-            long long grid = nt;
-            if (swz) { const long long g = 8ll << (swz - 1); grid = (nt + g - 1) / g * g; }
-            const int* first = static_cast<const int*>(tile_ws);
-#define FBBEV_CLS(STV)                                                                                          \
-    FBBEV_LAUNCH(k_pool_fwd_cl_small<STV>, grid, threads, 0, stream, C, sh, nvox, (int)nt, swz, depth, feat,    \
-                 ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, first, first + nt, out)
-            if (st == 0) { FBBEV_CLS(0); } else if (st == 1) { FBBEV_CLS(1); } else { FBBEV_CLS(4); }
-#undef FBBEV_CLS
-            return fbbev_rt_last_error();
         }
-        const bool cpl8cl = (flags & FBBEV_POOL_CPL8) && (C % 8 == 0);
-        if (256 / (C / (cpl8cl ? 8 : 4)) < 1) return FBBEV_E_UNSUPPORTED;
-        dense2_args a;
-        a.n_blocks = (nvox + TV - 1) / TV;
-        if (tile_ws_bytes < (size_t)(a.n_blocks + 1) * 8) return FBBEV_E_WORKSPACE;
-        a.lds = (3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(int);
-        a.stream = stream; a.C = C; a.Z = Z; a.yx = (int)nvox; a.tpp = 0; a.csplit = 1;
-        a.swizzle = 0;
-        if (flags & FBBEV_POOL_XCD_SWIZZLE) {
-            int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
-            if (lg == 0) lg = 4;
-            a.swizzle = lg + 1;
+        return FBBEV_E_UNSUPPORTED;
+    }
+    if (et != 0) {
+        if (!a.addend && nt == 256) {                       // no epilogue add: the LDS tile itself is 16-bit (see the kernel)
+            a.lds = pool_planar_lds16_bytes(CC, TV);
+            FBBEV_POOL_ET16(et, return pool_launch_dense2<TV, CPL, 4, 256, ET, true, 0, 4>(a));
         }
-        a.depth = depth; a.feat = feat; a.rd = ranks_depth; a.rf = ranks_feat; a.irank = interval_rank;
-        a.starts = interval_starts; a.lengths = interval_lengths; a.tile_meta = static_cast<const int*>(tile_ws);
-        a.out = out; a.stride_b = 0; a.stride_c = 0;
-        if (TV == 64) return cpl8cl ? launch_dense_cl_st<64, 8>(st, a) : launch_dense_cl_st<64, 4>(st, a);
-        if (TV == 128) return cpl8cl ? launch_dense_cl_st<128, 8>(st, a) : launch_dense_cl_st<128, 4>(st, a);
-        if (TV == 256) return cpl8cl ? launch_dense_cl_st<256, 8>(st, a) : launch_dense_cl_st<256, 4>(st, a);
-        if (TV == 512) return cpl8cl ? launch_dense_cl_st<512, 8>(st, a) : launch_dense_cl_st<512, 4>(st, a);
-        return cpl8cl ? launch_dense_cl_st<1024, 8>(st, a) : launch_dense_cl_st<1024, 4>(st, a);
+        FBBEV_POOL_ET16(et, FBBEV_POOL_NT(nt, return pool_launch_dense2<TV, CPL, 4, NT, ET, false, 0, 4>(a)));
     }
-    int csplit = (flags >> FBBEV_POOL_CSPLIT_SHIFT) & 0xF;
-    if (csplit == 0xF) csplit = 20;
-    if (csplit < 1) csplit = 1;
-    if (C % (4 * csplit) != 0) csplit = 1;
-    const int CC = C / csplit;
-    const bool cpl8 = (flags & FBBEV_POOL_CPL8) && (CC % 8 == 0);
-    int nt = 256;
-    if (((flags >> FBBEV_POOL_WG_SHIFT) & 0x3) == 1) nt = 128;
-    if (nt / (CC / (cpl8 ? 8 : 4)) < 1) return FBBEV_E_UNSUPPORTED;
-    dense2_args a;
-    a.n_blocks = n_tiles * csplit;
-    a.lds = ((size_t)CC * (TV + 4) + 3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(float);
-    a.stream = stream; a.C = C; a.Z = Z; a.yx = (int)yx; a.tpp = tiles_per_plane; a.csplit = csplit;
-    a.swizzle = 0;
-    if (flags & FBBEV_POOL_XCD_SWIZZLE) {
-        int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;   // log2(tiles per chunk); 0 -> default
-        if (lg == 0) lg = 6;
-        a.swizzle = lg + 1;
+    FBBEV_POOL_WITH3(ST, st, 4, 0, 1, FBBEV_POOL_NT(nt, return pool_launch_dense2<TV, CPL, ST, NT, 0, false, 0, 4>(a)));   // (the default policy first)
+    return FBBEV_E_UNSUPPORTED;                             // (not reached: every ladder above returns)
+}
+
+// `strides`: as the caller passed them (0 = contiguous)
+static int pool_dense_fwd(const pool_call& c, float* out, const pool_strides& strides, const float* addend) {
+    const pool_grid& g = c.g;
+    const pool_flags& f = c.f;
+    if (!pool_grid_positive(g)) return FBBEV_E_BADARG;
+    if (!pool_gather_present(c.in) || !out || !c.tile_ws) return FBBEV_E_BADARG;
+    if (g.C % 4 != 0 || g.C > 256 || g.yx % 4 != 0 || !aligned16(out) || !aligned16(c.in.feat)) return FBBEV_E_UNSUPPORTED;
+    if (!pool_grid_fits_int(g)) return FBBEV_E_UNSUPPORTED;
+    const pool_strides s = pool_volume_strides(strides.b, strides.c, g);
+    if (s.err) return s.err;
+    const int tv = pick_tile(c.tile_voxels);
+    const int tiles_per_plane = (int)((g.yx + tv - 1) / tv);
+    const long long n_tiles = (long long)g.B * g.Z * tiles_per_plane;
+    if (c.tile_ws_bytes < pool_tile_table_bytes(n_tiles)) return FBBEV_E_WORKSPACE;
+    if (f.et() != 0) {   // 16-bit storage: 8 elements per 16-byte store
+        if (f.bf16 && f.f16) return FBBEV_E_BADARG;
+        if (f.channels_last) return FBBEV_E_UNSUPPORTED;
+        if (g.yx % 8 != 0 || s.c % 8 != 0 || s.b % 8 != 0) return FBBEV_E_UNSUPPORTED;
     }
+    if (addend && (f.channels_last || !aligned16(addend))) return FBBEV_E_UNSUPPORTED;
+    if (f.channels_last) {
+        // out is (B,Z,Y,X,C) contiguous
+        if (s.b != (long long)g.C * g.Z * g.yx || s.c != g.Z * g.yx) return FBBEV_E_BADARG;
+        if (const int sh = small_tile_shift(c.tile_voxels)) return pool_fwd_cl_small(c, out, sh);
+        return pool_fwd_cl(c, out, tv);
+    }
+    pool_launch a = pool_launch_of(c);
+    a.csplit = f.csplit(g.C);
+    const int CC = g.C / a.csplit, cpl = f.cpl(CC), nt = f.threads();
+    if (nt / (CC / cpl) < 1) return FBBEV_E_UNSUPPORTED;
+    a.yx = (int)g.yx; a.tpp = tiles_per_plane;
+    a.n_blocks = n_tiles * a.csplit;
+    a.lds = pool_planar_lds_bytes(CC, tv);
+    // chunks of 64 tiles where the field is 0: the planar kernel's first measurements with the swizzle name no chunk size
+    // (profiles/r01_pool_variants_BL2_B16.jsonl, the `_swz` variants); the later sweeps and the Python side always say one
+    a.swizzle = f.swizzle(6);
     if (a.n_blocks + 8 >= (1ll << 31) || a.lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
-    a.depth = depth; a.feat = feat; a.rd = ranks_depth; a.rf = ranks_feat; a.irank = interval_rank;
-    a.starts = interval_starts; a.lengths = interval_lengths; a.tile_meta = static_cast<const int*>(tile_ws);
-    a.out = out; a.stride_b = out_stride_b; a.stride_c = out_stride_c; a.addend = addend;
-    a.split = (flags & FBBEV_POOL_SPLIT_LONG) != 0;
-    a.gather8 = (flags & FBBEV_POOL_GATHER8) != 0 && !a.split;
-    if ((flags & FBBEV_POOL_PIPE) && ot == 0 && !a.split && nt == 256 && st >= 2 && (TV == 64 || TV == 128 || TV == 256)) {
-        // tiles per workgroup: enough to amortise the pipeline's fill, few enough to keep >= ~8 workgroups per CU's worth of runs
-        FBBEV_KNOB_ONCE(int, tpw_env, fbbev_env_int("FBBEV_POOL_PIPE_TPW", 0));   // tuning knob (the emulator tests switch the run length)
-        int tpw = tpw_env > 0 ? (tpw_env > 64 ? 64 : tpw_env) : 4;
-        if (tpw_env <= 0) while (tpw > 1 && (n_tiles / tpw) * csplit < 2048) tpw >>= 1;
-        const long long groups = (n_tiles + tpw - 1) / tpw;
-        a.n_blocks = groups * csplit;
-        a.lds = ((size_t)CC * (TV + 4) + 2 * (3 * (size_t)TV + 2 * FBBEV_NP_STAGE)) * sizeof(float);
-        if (a.lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
-        long long grid = a.n_blocks;
-        if (a.swizzle) {
-            const long long g = 8ll << (a.swizzle - 1);
-            grid = (a.n_blocks + g - 1) / g * g;
-        }
-#define FBBEV_POOL_PIPE_LAUNCH(TV_, CPL_)                                                                                             \
-        FBBEV_LAUNCH_DYN_LDS((k_pool_fwd_dense_pipe<TV_, CPL_, 4, 256>), grid, 256, a.lds, a.stream, a.C, a.Z, a.yx, a.tpp, a.csplit, \
-                             (int)a.n_blocks, a.swizzle, tpw, (int)n_tiles, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf,      \
-                             a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.out)
-        if (TV == 64) { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(64, 8); else FBBEV_POOL_PIPE_LAUNCH(64, 4); }
-        else if (TV == 128) { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(128, 8); else FBBEV_POOL_PIPE_LAUNCH(128, 4); }
-        else { if (cpl8) FBBEV_POOL_PIPE_LAUNCH(256, 8); else FBBEV_POOL_PIPE_LAUNCH(256, 4); }
-#undef FBBEV_POOL_PIPE_LAUNCH
-        return fbbev_rt_last_error();
-    }
-    if (TV == 64) return cpl8 ? launch_dense2_st<64, 8>(st, nt, ot, a) : launch_dense2_st<64, 4>(st, nt, ot, a);
-    if (TV == 128) return cpl8 ? launch_dense2_st<128, 8>(st, nt, ot, a) : launch_dense2_st<128, 4>(st, nt, ot, a);
-    if (TV == 256) return cpl8 ? launch_dense2_st<256, 8>(st, nt, ot, a) : launch_dense2_st<256, 4>(st, nt, ot, a);
-    if (TV == 512) return cpl8 ? launch_dense2_st<512, 8>(st, nt, ot, a) : launch_dense2_st<512, 4>(st, nt, ot, a);
-    return cpl8 ? launch_dense2_st<1024, 8>(st, nt, ot, a) : launch_dense2_st<1024, 4>(st, nt, ot, a);
+    a.out = out; a.out_stride_b = s.b; a.out_stride_c = s.c; a.addend = addend;
+    if (f.pipe && f.et() == 0 && !f.split_long && nt == 256 && f.store() == 4 && (tv == 64 || tv == 128 || tv == 256))
+        return pool_fwd_pipe(a, n_tiles, tv, cpl);
+    FBBEV_POOL_TILE(tv, FBBEV_POOL_CPL(cpl, return pool_fwd_planar<TV, CPL>(a, f)));
+    return FBBEV_E_UNSUPPORTED;                             // (not reached)
 }
 
 extern "C" int fbbev_bev_pool_v2_dense_fwd(const float* depth, const float* feat,
@@ -882,141 +962,12 @@ extern "C" int fbbev_bev_pool_v2_dense_fwd(const float* depth, const float* feat
                                            int X, float* out, long long out_stride_b, long long out_stride_c,
                                            const void* tile_ws, size_t tile_ws_bytes, int tile_voxels,
                                            int flags, fbbev_stream_t stream_) {
-    return pool_dense_fwd_impl(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C,
-                               Z, Y, X, out, out_stride_b, out_stride_c, tile_ws, tile_ws_bytes, tile_voxels, flags, nullptr,
-                               stream_);
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    return pool_dense_fwd(c, out, {out_stride_b, out_stride_c, 0}, nullptr);
 }
 
-// ------------------------------------------------------------------------------ fused dense fwd, rows of a strided slot
-struct dense_rows_args {
-    long long n_blocks, addend_row_stride, out_stride_b; size_t lds; fbbev_rt_stream stream; int C, nvox, zyx, yx, swizzle;
-    const float *depth, *feat; const int32_t *rd, *rf, *irank, *starts, *lengths; const int* tile_meta;
-    const float* addend; void* out;
-};
-
-template <int TV, int CPL, int ST, int ET>
-static int launch_dense_rows(const dense_rows_args& a) {
-    long long grid = a.n_blocks;
-    if (a.swizzle) {
-        const long long g = 8ll << (a.swizzle - 1);
-        grid = (a.n_blocks + g - 1) / g * g;
-    }
-    FBBEV_LAUNCH((k_pool_fwd_dense_rows<TV, CPL, ST, 256, ET>), grid, 256, a.lds, a.stream, a.C, a.nvox, a.zyx, a.yx, (int)a.n_blocks,
-                 a.swizzle, a.depth, a.feat, a.rd, a.rf, a.irank, a.starts, a.lengths, a.tile_meta, a.addend, a.addend_row_stride,
-                 a.out, a.out_stride_b);
-    return fbbev_rt_last_error();
-}
-
-// 16-bit rows: 8 channels per lane (one 16-byte store), built for the default `sc1 nt` store policy like the planar 16-bit kernels
-template <int TV>
-static int launch_dense_rows_tv(int et, int st, bool cpl8, const dense_rows_args& a) {
-    if (et == 1) return launch_dense_rows<TV, 8, 4, 1>(a);
-    if (et == 2) return launch_dense_rows<TV, 8, 4, 2>(a);
-    if (cpl8) return st == 0 ? launch_dense_rows<TV, 8, 0, 0>(a) : st == 1 ? launch_dense_rows<TV, 8, 1, 0>(a) : launch_dense_rows<TV, 8, 4, 0>(a);
-    return st == 0 ? launch_dense_rows<TV, 4, 0, 0>(a) : st == 1 ? launch_dense_rows<TV, 4, 1, 0>(a) : launch_dense_rows<TV, 4, 4, 0>(a);
-}
-
-extern "C" int fbbev_bev_pool_v2_dense_fwd_rows(const float* depth, const float* feat, const int32_t* ranks_depth,
-                                                const int32_t* ranks_feat, const int32_t* interval_rank,
-                                                const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C,
-                                                int Z, int Y, int X, void* out_rows, long long out_stride_b,
-                                                const float* addend_rows, long long addend_row_stride, const void* tile_ws,
-                                                size_t tile_ws_bytes, int tile_voxels, int flags, fbbev_stream_t stream_) {
-    if (B <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
-    if (!depth || !feat || !ranks_depth || !ranks_feat || !interval_rank || !interval_starts || !interval_lengths || !out_rows ||
-        !tile_ws) return FBBEV_E_BADARG;
-    if ((flags & FBBEV_POOL_OUT_BF16) && (flags & FBBEV_POOL_OUT_F16)) return FBBEV_E_BADARG;
-    const int et = (flags & FBBEV_POOL_OUT_BF16) ? 1 : ((flags & FBBEV_POOL_OUT_F16) ? 2 : 0);
-    const int ve = et == 0 ? 4 : 8;                                     // elements of a 16-byte store
-    const long long yx = (long long)Y * X;
-    if (yx >= (1ll << 31) || Z * yx >= (1ll << 31) || B * (Z * yx) >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;   // flat voxel index: int
-    const long long zyx = Z * yx, nvox = B * zyx;
-    if (out_stride_b == 0) out_stride_b = zyx * C;                      // contiguous (B, Z*Y*X, C)
-    if (addend_row_stride == 0) addend_row_stride = C;
-    if (out_stride_b < zyx * C || addend_row_stride < C) return FBBEV_E_BADARG;
-    if (C % ve != 0 || C > 256 || out_stride_b % ve != 0 || addend_row_stride % 4 != 0 || !aligned16(out_rows) || !aligned16(feat) ||
-        !aligned16(addend_rows)) return FBBEV_E_UNSUPPORTED;
-    if (small_tile_shift(tile_voxels)) return FBBEV_E_UNSUPPORTED;      // the small-tile kernel keeps its fp32, contiguous, no-addend form
-    const int TV = pick_tile(tile_voxels);
-    const bool cpl8 = et != 0 || ((flags & FBBEV_POOL_CPL8) && C % 8 == 0);
-    if (256 / (C / (cpl8 ? 8 : 4)) < 1) return FBBEV_E_UNSUPPORTED;     // a voxel row takes more lanes than a workgroup has
-    dense_rows_args a;
-    a.n_blocks = (nvox + TV - 1) / TV;
-    if (tile_ws_bytes < (size_t)(a.n_blocks + 1) * 8) return FBBEV_E_WORKSPACE;
-    a.lds = (3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(int);
-    a.stream = (fbbev_rt_stream)stream_; a.C = C; a.nvox = (int)nvox; a.zyx = (int)zyx; a.yx = (int)yx;
-    a.swizzle = 0;
-    if (flags & FBBEV_POOL_XCD_SWIZZLE) {
-        int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
-        if (lg == 0) lg = 4;
-        a.swizzle = lg + 1;
-    }
-    a.depth = depth; a.feat = feat; a.rd = ranks_depth; a.rf = ranks_feat; a.irank = interval_rank;
-    a.starts = interval_starts; a.lengths = interval_lengths; a.tile_meta = static_cast<const int*>(tile_ws);
-    a.addend = addend_rows; a.addend_row_stride = addend_row_stride; a.out = out_rows; a.out_stride_b = out_stride_b;
-    const int st = (flags & FBBEV_POOL_STORE_MASK) | ((flags >> FBBEV_POOL_STORE_HI_SHIFT) & 1) << 2;
-    switch (TV) {
-        case 64: return launch_dense_rows_tv<64>(et, st, cpl8, a);
-        case 128: return launch_dense_rows_tv<128>(et, st, cpl8, a);
-        case 256: return launch_dense_rows_tv<256>(et, st, cpl8, a);
-        case 512: return launch_dense_rows_tv<512>(et, st, cpl8, a);
-        default: return launch_dense_rows_tv<1024>(et, st, cpl8, a);
-    }
-}
-
-// Measurement aid (bench.py `roofline.store_floor_ms` / `no_gather_ms`): the default fp32 instantiation of the dense kernel
-// (128-voxel tiles, 8 channels per lane, 256 threads, `sc1 nt` stores) with its gathers compiled out -- same grid, tile
-// walk and XCD order as the product launch with these flags.  mode 1: store pattern alone; mode 2: all but the depth /
-// feature gathers.  Writes zeros to `out`.
-extern "C" int fbbev_diag_pool_store_floor(const float* depth, const float* feat, const int32_t* ranks_depth,
-                                           const int32_t* ranks_feat, const int32_t* interval_rank,
-                                           const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C,
-                                           int Z, int Y, int X, float* out, const void* tile_ws, size_t tile_ws_bytes,
-                                           int tile_voxels, int flags, int mode, fbbev_stream_t stream_) {
-    if (B <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0 || mode < 1 || mode > 3) return FBBEV_E_BADARG;
-    if (!depth || !feat || !ranks_depth || !ranks_feat || !interval_rank || !interval_starts || !interval_lengths || !out ||
-        !tile_ws) return FBBEV_E_BADARG;
-    const long long yx = (long long)Y * X;
-    const bool bf16 = (flags & FBBEV_POOL_OUT_BF16) != 0;          // round 5: the 16-bit-tile instantiation of the bf16-storage leg
-    if (pick_tile(tile_voxels) != 128 || tile_voxels != 128 || yx % (bf16 ? 8 : 4) != 0 || !aligned16(out) ||
-        (flags & (FBBEV_POOL_CHANNELS_LAST | FBBEV_POOL_OUT_F16)) || (long long)B * Z * yx >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int st = (flags & FBBEV_POOL_STORE_MASK) | ((flags >> FBBEV_POOL_STORE_HI_SHIFT) & 1) << 2;
-    int csplit = (flags >> FBBEV_POOL_CSPLIT_SHIFT) & 0xF;
-    if (csplit == 0xF) csplit = 20;
-    if (csplit < 1 || C % (4 * csplit) != 0) csplit = 1;
-    const int CC = C / csplit;
-    if (!(flags & FBBEV_POOL_CPL8) || CC % 8 != 0 || st < 2 || ((flags >> FBBEV_POOL_WG_SHIFT) & 0x3) != 0 || 256 / (CC / 8) < 1)
-        return FBBEV_E_UNSUPPORTED;
-    const int tiles_per_plane = (int)((yx + 127) / 128);
-    const long long n_tiles = (long long)B * Z * tiles_per_plane;
-    if (tile_ws_bytes < (size_t)(n_tiles + 1) * 8) return FBBEV_E_WORKSPACE;
-    dense2_args a;
-    a.n_blocks = n_tiles * csplit;
-    a.lds = bf16 ? (size_t)CC * (128 + 8) * 2 + ((size_t)3 * 128 + 2 * FBBEV_NP_STAGE) * sizeof(int)
-                 : ((size_t)CC * (128 + 4) + 3 * (size_t)128 + 2 * FBBEV_NP_STAGE) * sizeof(float);
-    a.stream = (fbbev_rt_stream)stream_; a.C = C; a.Z = Z; a.yx = (int)yx; a.tpp = tiles_per_plane; a.csplit = csplit;
-    a.swizzle = 0;
-    if (flags & FBBEV_POOL_XCD_SWIZZLE) {
-        int lg = (flags >> FBBEV_POOL_SWZ_CHUNK_SHIFT) & 0x1F;
-        if (lg == 0) lg = 6;
-        a.swizzle = lg + 1;
-    }
-    if (a.n_blocks + 8 >= (1ll << 31) || a.lds > 64 * 1024) return FBBEV_E_UNSUPPORTED;
-    a.depth = depth; a.feat = feat; a.rd = ranks_depth; a.rf = ranks_feat; a.irank = interval_rank;
-    a.starts = interval_starts; a.lengths = interval_lengths; a.tile_meta = static_cast<const int*>(tile_ws);
-    a.out = out; a.stride_b = (long long)C * Z * yx; a.stride_c = (long long)Z * yx; a.addend = nullptr;
-    long long grid = a.n_blocks;
-    if (a.swizzle) { const long long g = 8ll << (a.swizzle - 1); grid = (a.n_blocks + g - 1) / g * g; }
-#define FBBEV_DIAG_DENSE(OT_, T16_, MODE_)                                                                               \
-    FBBEV_LAUNCH((k_pool_fwd_dense2<128, 8, 4, 256, OT_, T16_, MODE_>), grid, 256, a.lds, a.stream, a.C, a.Z, a.yx, a.tpp, \
-                 a.csplit, (int)a.n_blocks, a.swizzle, a.stride_b, a.stride_c, a.depth, a.feat, a.rd, a.rf, a.irank,      \
-                 a.starts, a.lengths, a.tile_meta, a.addend, a.out)
-    if (bf16) { if (mode == 1) FBBEV_DIAG_DENSE(1, true, 1); else if (mode == 2) FBBEV_DIAG_DENSE(1, true, 2); else FBBEV_DIAG_DENSE(1, true, 3); }
-    else { if (mode == 1) FBBEV_DIAG_DENSE(0, false, 1); else if (mode == 2) FBBEV_DIAG_DENSE(0, false, 2); else FBBEV_DIAG_DENSE(0, false, 3); }
-#undef FBBEV_DIAG_DENSE
-    return fbbev_rt_last_error();
-}
-
+// ... with a (B,C,Y,X) addend broadcast over z in the epilogue
 extern "C" int fbbev_bev_pool_v2_dense_fwd_add(const float* depth, const float* feat,
                                                const int32_t* ranks_depth, const int32_t* ranks_feat,
                                                const int32_t* interval_rank, const int32_t* interval_starts,
@@ -1025,44 +976,140 @@ extern "C" int fbbev_bev_pool_v2_dense_fwd_add(const float* depth, const float* 
                                                const void* tile_ws, size_t tile_ws_bytes, int tile_voxels,
                                                int flags, const float* addend, fbbev_stream_t stream_) {
     if (!addend) return FBBEV_E_BADARG;
-    return pool_dense_fwd_impl(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C,
-                               Z, Y, X, out, out_stride_b, out_stride_c, tile_ws, tile_ws_bytes, tile_voxels, flags, addend,
-                               stream_);
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    return pool_dense_fwd(c, out, {out_stride_b, out_stride_c, 0}, addend);
 }
 
-// ------------------------------------------------------------------------------ lift-splat in ONE entry
+// ---- the dense forward as rows of a strided slot
+template <int TV, int CPL, int ST, int ET>
+static int pool_launch_rows(const pool_launch& a) {
+    FBBEV_LAUNCH((k_pool_fwd_dense_rows<TV, CPL, ST, 256, ET>), pool_swizzled_grid(a.n_blocks, a.swizzle), 256, a.lds, a.stream, a.C, a.nvox, a.zyx,
+                 a.yx, (int)a.n_blocks, a.swizzle, FBBEV_POOL_GATHER(a.in), a.tile_meta, a.addend, a.addend_stride, a.out, a.out_stride_b);
+    return fbbev_rt_last_error();
+}
+
+// 16-bit rows: 8 channels per lane (one 16-byte store), built for the default `sc1 nt` store policy like the planar 16-bit kernels
+template <int TV>
+static int pool_fwd_rows(const pool_launch& a, int et, int cpl, int st) {
+    if (et != 0) FBBEV_POOL_ET16(et, return pool_launch_rows<TV, 8, 4, ET>(a));
+    FBBEV_POOL_CPL(cpl, FBBEV_POOL_ST(st, return pool_launch_rows<TV, CPL, ST, 0>(a)));
+    return FBBEV_E_UNSUPPORTED;                             // (not reached)
+}
+
+extern "C" int fbbev_bev_pool_v2_dense_fwd_rows(const float* depth, const float* feat, const int32_t* ranks_depth,
+                                                const int32_t* ranks_feat, const int32_t* interval_rank,
+                                                const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C,
+                                                int Z, int Y, int X, void* out_rows, long long out_stride_b,
+                                                const float* addend_rows, long long addend_row_stride, const void* tile_ws,
+                                                size_t tile_ws_bytes, int tile_voxels, int flags, fbbev_stream_t stream_) {
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    const pool_grid& g = c.g;
+    const pool_flags& f = c.f;
+    if (!pool_grid_positive(g)) return FBBEV_E_BADARG;
+    if (!pool_gather_present(c.in) || !out_rows || !tile_ws) return FBBEV_E_BADARG;
+    if (f.bf16 && f.f16) return FBBEV_E_BADARG;             // (here right after the pointers; the planar entries look at the table's bytes first)
+    const int et = f.et();
+    const int ve = et == 0 ? 4 : 8;                                     // elements of a 16-byte store
+    if (!pool_grid_fits_int(g)) return FBBEV_E_UNSUPPORTED;             // flat voxel index: int
+    const long long zyx = g.Z * g.yx;
+    if (out_stride_b == 0) out_stride_b = zyx * C;                      // contiguous (B, Z*Y*X, C)
+    if (addend_row_stride == 0) addend_row_stride = C;
+    if (out_stride_b < zyx * C || addend_row_stride < C) return FBBEV_E_BADARG;
+    if (C % ve != 0 || C > 256 || out_stride_b % ve != 0 || addend_row_stride % 4 != 0 || !aligned16(out_rows) || !aligned16(feat) ||
+        !aligned16(addend_rows)) return FBBEV_E_UNSUPPORTED;
+    if (small_tile_shift(tile_voxels)) return FBBEV_E_UNSUPPORTED;      // the small-tile kernel keeps its fp32, contiguous, no-addend form
+    const int tv = pick_tile(tile_voxels);
+    const int cpl = et != 0 ? 8 : f.cpl(C);
+    if (256 / (C / cpl) < 1) return FBBEV_E_UNSUPPORTED;                // a voxel row takes more lanes than a workgroup has
+    pool_launch a = pool_launch_of(c);
+    a.n_blocks = (g.nvox + tv - 1) / tv;
+    if (tile_ws_bytes < pool_tile_table_bytes(a.n_blocks)) return FBBEV_E_WORKSPACE;
+    a.lds = pool_index_lds_bytes(tv);
+    a.nvox = (int)g.nvox; a.zyx = (int)zyx; a.yx = (int)g.yx;
+    a.swizzle = f.swizzle(4);                                           // the flat tiles' default: this kernel walks them as pool_fwd_cl's does
+    a.addend = addend_rows; a.addend_stride = addend_row_stride; a.out = out_rows; a.out_stride_b = out_stride_b;
+    FBBEV_POOL_TILE(tv, return pool_fwd_rows<TV>(a, et, cpl, f.store()));
+    return FBBEV_E_UNSUPPORTED;                                         // (not reached)
+}
+
+// Measurement aid (bench.py `roofline.store_floor_ms` / `no_gather_ms`): the default fp32 instantiation of the dense kernel
+// (128-voxel tiles, 8 channels per lane, 256 threads, `sc1 nt` stores) with its gathers compiled out -- same grid, tile
+// walk and XCD order as the product launch with these flags.  mode 1: store pattern alone; mode 2: all but the depth /
+// feature gathers.  Writes zeros to `out`.  With FBBEV_POOL_OUT_BF16: the 16-bit-tile instantiation of the bf16-storage leg.
+extern "C" int fbbev_diag_pool_store_floor(const float* depth, const float* feat, const int32_t* ranks_depth,
+                                           const int32_t* ranks_feat, const int32_t* interval_rank,
+                                           const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C,
+                                           int Z, int Y, int X, float* out, const void* tile_ws, size_t tile_ws_bytes,
+                                           int tile_voxels, int flags, int mode, fbbev_stream_t stream_) {
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    const pool_grid& g = c.g;
+    const pool_flags& f = c.f;
+    if (!pool_grid_positive(g) || mode < 1 || mode > 3) return FBBEV_E_BADARG;
+    if (!pool_gather_present(c.in) || !out || !tile_ws) return FBBEV_E_BADARG;
+    if (tile_voxels != 128 || g.yx % (f.bf16 ? 8 : 4) != 0 || !aligned16(out) || f.channels_last || f.f16 || !pool_grid_fits_int(g))
+        return FBBEV_E_UNSUPPORTED;
+    pool_launch a = pool_launch_of(c);
+    a.csplit = f.csplit(C);
+    const int CC = C / a.csplit;
+    if (f.cpl(CC) != 8 || f.store() != 4 || f.wg != 0 || 256 / (CC / 8) < 1) return FBBEV_E_UNSUPPORTED;
+    a.yx = (int)g.yx; a.tpp = (int)((g.yx + 127) / 128);
+    const long long n_tiles = (long long)B * Z * a.tpp;
+    if (tile_ws_bytes < pool_tile_table_bytes(n_tiles)) return FBBEV_E_WORKSPACE;
+    a.n_blocks = n_tiles * a.csplit;
+    a.lds = f.bf16 ? pool_planar_lds16_bytes(CC, 128) : pool_planar_lds_bytes(CC, 128);
+    a.swizzle = f.swizzle(6);                               // as the product launch (pool_dense_fwd)
+    if (a.n_blocks + 8 >= (1ll << 31) || a.lds > 64 * 1024) return FBBEV_E_UNSUPPORTED;   // (64 KiB here; the product takes 160)
+    a.out = out; a.out_stride_b = (long long)C * Z * g.yx; a.out_stride_c = Z * g.yx;
+    const long long grid = pool_swizzled_grid(a.n_blocks, a.swizzle);
+    FBBEV_POOL_WITH(OT, f.bf16 ? 1 : 0, 1, 0, FBBEV_POOL_WITH3(MODE, mode, 1, 2, 3, FBBEV_LAUNCH(
+        (k_pool_fwd_dense2<128, 8, 4, 256, OT, OT == 1, MODE>), grid, 256, a.lds, a.stream, a.C, a.Z, a.yx, a.tpp, a.csplit, (int)a.n_blocks,
+        a.swizzle, a.out_stride_b, a.out_stride_c, FBBEV_POOL_GATHER(a.in), a.tile_meta, a.addend, static_cast<float*>(a.out))));
+    return fbbev_rt_last_error();
+}
+
+// ---- lift-splat in ONE entry
 // Workspace layout of fbbev_lift_splat_fused (all blocks 256-byte aligned): the seven padded index tensors + counts the build
 // writes, the NHWC feature rows, the tile table, the ranking workspace.
+struct lift_dims { int B, N, D, H, W, C, Z, Y, X; };
+static inline bool lift_dims_positive(const lift_dims& d) {
+    return d.B > 0 && d.N > 0 && d.D > 0 && d.H > 0 && d.W > 0 && d.C > 0 && d.Z > 0 && d.Y > 0 && d.X > 0;
+}
+static inline long long lift_points(const lift_dims& d) { return (long long)d.B * d.N * d.D * d.H * d.W; }   // frustum points
 struct lift_splat_layout {
+    bool ok;                                                // positive dimensions and fewer than 2^31 frustum points
     size_t ranks_bev, ranks_depth, ranks_feat, interval_starts, interval_lengths, interval_rank, counts, feat, tile, rank, total;
     size_t tile_bytes, rank_bytes;
 };
-static bool lift_splat_plan(int B, int N, int D, int H, int W, int C, int Z, int Y, int X, lift_splat_layout& L) {
-    if (B <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return false;
-    const long long n = (long long)B * N * D * H * W;
-    if (n >= (1ll << 31)) return false;
+static lift_splat_layout lift_splat_plan(const lift_dims& d) {
+    lift_splat_layout L = {};
+    if (!lift_dims_positive(d)) return L;
+    const long long n = lift_points(d);
+    if (n >= (1ll << 31)) return L;
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
     L.ranks_bev = take((size_t)n * 4); L.ranks_depth = take((size_t)n * 4); L.ranks_feat = take((size_t)n * 4);
     L.interval_starts = take((size_t)n * 4); L.interval_lengths = take((size_t)n * 4); L.interval_rank = take((size_t)n * 4);
     L.counts = take(16);
-    L.feat = take((size_t)B * N * H * W * C * 4);
-    L.tile_bytes = fbbev_pool_dense_workspace_bytes(B, Z, Y, X);
+    L.feat = take((size_t)d.B * d.N * d.H * d.W * d.C * 4);
+    L.tile_bytes = fbbev_pool_dense_workspace_bytes(d.B, d.Z, d.Y, d.X);
     L.tile = take(L.tile_bytes);
     L.rank_bytes = fbbev_rank_workspace_bytes(n);
     L.rank = take(L.rank_bytes);
     L.total = off;
-    return true;
+    L.ok = true;
+    return L;
 }
 
 extern "C" size_t fbbev_lift_splat_fused_ws_bytes(int B, int N, int D, int H, int W, int C, int Z, int Y, int X) {
-    lift_splat_layout L;
-    return lift_splat_plan(B, N, D, H, W, C, Z, Y, X, L) ? L.total : 0;
+    return lift_splat_plan({B, N, D, H, W, C, Z, Y, X}).total;      // 0 without a plan
 }
 
 extern "C" int fbbev_lift_splat_fused_ws_offsets(int B, int N, int D, int H, int W, int C, int Z, int Y, int X, size_t* offsets8) {
-    lift_splat_layout L;
-    if (!offsets8 || !lift_splat_plan(B, N, D, H, W, C, Z, Y, X, L)) return FBBEV_E_BADARG;
+    const lift_splat_layout L = lift_splat_plan({B, N, D, H, W, C, Z, Y, X});
+    if (!offsets8 || !L.ok) return FBBEV_E_BADARG;
     offsets8[0] = L.ranks_bev; offsets8[1] = L.ranks_depth; offsets8[2] = L.ranks_feat; offsets8[3] = L.interval_starts;
     offsets8[4] = L.interval_lengths; offsets8[5] = L.interval_rank; offsets8[6] = L.counts; offsets8[7] = L.feat;
     return 0;
@@ -1075,15 +1122,16 @@ extern "C" int fbbev_lift_splat_fused(const float* frustum, const float* xs, con
                                       int Y, int X, void* out, long long out_stride_b, long long out_stride_c, int tile_voxels,
                                       int flags, void* workspace, size_t workspace_bytes, uint32_t* cam_key, int32_t* cache_state,
                                       fbbev_stream_t stream_) {
-    lift_splat_layout L;
-    if (!depth || !context || !out || !workspace) return FBBEV_E_BADARG;
-    if (!lift_splat_plan(B, N, D, H, W, C, Z, Y, X, L)) return FBBEV_E_BADARG;
+    const lift_dims d = {B, N, D, H, W, C, Z, Y, X};
+    if (!depth || !context || !out || !workspace) return FBBEV_E_BADARG;      // (its four pointers before the plan)
+    const lift_splat_layout L = lift_splat_plan(d);
+    if (!L.ok) return FBBEV_E_BADARG;
     if ((cam_key == nullptr) != (cache_state == nullptr)) return FBBEV_E_BADARG;
     if (workspace_bytes < L.total) return FBBEV_E_WORKSPACE;
     if (!aligned16(workspace)) return FBBEV_E_UNSUPPORTED;
     char* ws = static_cast<char*>(workspace);
     auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(ws + o); };
-    const long long n = (long long)B * N * D * H * W;
+    const int n = (int)lift_points(d);
     // view_transformer.py:458-498 + :547-605: geometry + voxel ranking, device-side counts (cache_state[0] = 1 on a key hit)
     int rc = lift_rank_build_impl(frustum, xs, ys, ds, rots, trans, intrins, post_rots, post_trans, bda, B, N, D, H, W, lower3,
                                   interval3, grid_size3, i32(L.ranks_bev), i32(L.ranks_depth), i32(L.ranks_feat),
@@ -1096,31 +1144,78 @@ extern "C" int fbbev_lift_splat_fused(const float* frustum, const float* xs, con
     if (rc) return rc;
     // bev_pool.py:24-35,88: new_zeros + kernel + permute().contiguous() as tile index + one dense pass
     if (cache_state)
-        rc = fbbev_pool_tile_index_cached(i32(L.interval_rank), i32(L.interval_starts), i32(L.counts), (int)n, B, Z, Y, X,
+        rc = fbbev_pool_tile_index_cached(i32(L.interval_rank), i32(L.interval_starts), i32(L.counts), n, B, Z, Y, X,
                                           tile_voxels, flags, ws + L.tile, L.tile_bytes, cache_state, cache_state + 2, stream_);
     else
-        rc = pool_tile_index_impl(i32(L.interval_rank), i32(L.interval_starts), i32(L.counts), (int)n, B, Z, Y, X, tile_voxels,
-                                  flags, ws + L.tile, L.tile_bytes, stream_, nullptr);
+        rc = fbbev_pool_tile_index(i32(L.interval_rank), i32(L.interval_starts), i32(L.counts), n, B, Z, Y, X, tile_voxels, flags,
+                                   ws + L.tile, L.tile_bytes, stream_);
     if (rc) return rc;
-    return pool_dense_fwd_impl(depth, feat, i32(L.ranks_depth), i32(L.ranks_feat), i32(L.interval_rank), i32(L.interval_starts),
-                               i32(L.interval_lengths), B, C, Z, Y, X, static_cast<float*>(out), out_stride_b, out_stride_c,
-                               ws + L.tile, L.tile_bytes, tile_voxels, flags, nullptr, stream_);
+    return fbbev_bev_pool_v2_dense_fwd(depth, feat, i32(L.ranks_depth), i32(L.ranks_feat), i32(L.interval_rank), i32(L.interval_starts),
+                                       i32(L.interval_lengths), B, C, Z, Y, X, static_cast<float*>(out), out_stride_b, out_stride_c,
+                                       ws + L.tile, L.tile_bytes, tile_voxels, flags, stream_);
 }
 
-static int pool_zmean_impl(const float* depth, const float* feat, const int32_t* ranks_depth,
-                           const int32_t* ranks_feat, const int32_t* interval_rank,
-                           const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C, int Z,
-                           int Y, int X, float* out_mean, const void* tile_ws, size_t tile_ws_bytes,
-                           int tile_voxels, int flags, int z_groups, float* partial, size_t partial_bytes, fbbev_stream_t stream_,
-                           int rows_out = 0, const float* row_bias = nullptr);
+// ---- the Z-mean: out = mean over z of the pooled volume, (B, C, Y, X) or as rows
+struct pool_zmean_out {
+    float* out;
+    int z_groups; float* partial; size_t partial_bytes;     // z_groups > 1: the planes dealt to that many workgroups, summed by a second kernel
+    int rows_out; const float* row_bias;                    // rows_out: out is (B, Y*X, C) = mean + row_bias (Y*X, C; may be null)
+};
+static int pool_zmean(const pool_call& c, const pool_zmean_out& o) {
+    const pool_grid& g = c.g;
+    const pool_flags& f = c.f;
+    if (!pool_grid_positive(g)) return FBBEV_E_BADARG;
+    if (o.rows_out && (o.z_groups != 1 || (o.row_bias && !aligned16(o.row_bias)))) return FBBEV_E_UNSUPPORTED;   // (before the pointers)
+    if (!pool_gather_present(c.in) || !o.out || !c.tile_ws) return FBBEV_E_BADARG;
+    if (g.C % 4 != 0 || g.C > 256 || g.yx % 4 != 0 || !aligned16(o.out) || !aligned16(c.in.feat)) return FBBEV_E_UNSUPPORTED;
+    if (!pool_grid_fits_int(g) || f.channels_last) return FBBEV_E_UNSUPPORTED;
+    const int tv = pick_tile(c.tile_voxels);
+    if (tv > 256) return FBBEV_E_UNSUPPORTED;
+    const int tiles_per_plane = (int)((g.yx + tv - 1) / tv);
+    const long long n_tiles = (long long)g.B * g.Z * tiles_per_plane;
+    if (c.tile_ws_bytes < pool_tile_table_bytes(n_tiles)) return FBBEV_E_WORKSPACE;
+    const int csplit = f.csplit(g.C), CC = g.C / csplit, cpl = f.cpl(CC);
+    if (256 / (CC / cpl) < 1) return FBBEV_E_UNSUPPORTED;
+    const size_t lds = pool_planar_lds_bytes(CC, tv);
+    if (lds > 64 * 1024) return FBBEV_E_UNSUPPORTED;
+    const long long blocks = (long long)g.B * tiles_per_plane * csplit;
+    const int z_groups = o.z_groups > g.Z ? g.Z : o.z_groups;
+    const long long n_out = (long long)g.B * g.C * g.yx;
+    if (z_groups > 1 && o.partial_bytes < (size_t)z_groups * n_out * sizeof(float)) return FBBEV_E_WORKSPACE;
+    if (blocks * z_groups >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    const int* meta = static_cast<const int*>(c.tile_ws);
+    // round 5: the column form (every plane's metadata at once, a lane group per pixel; the same bits) when the column's slot table
+    // fits -- OPT-IN (FBBEV_ZMEAN_COL=1): built to cut the Z dependent round-trip chains of the plane walk, measured SLOWER at the
+    // BASELINE configs[2] grid, B = 4 (135.7 vs 103.9 us, S3 1.395 vs 1.360 ms: profiles/r05_exp_zmean_col.md -- 54 KB of LDS = 2
+    // workgroups per CU instead of 5, and a lane group's pixels are a serial chain of their own)
+    FBBEV_KNOB_ONCE(bool, col_on, fbbev_env_int("FBBEV_ZMEAN_COL", 0) != 0);
+    const size_t lds_col = fbbev_zmean_col_lds_bytes(CC, tv, g.Z);
+    if (col_on && !o.rows_out && z_groups == 1 && g.Z <= 64 && lds_col <= 64 * 1024) {
+        FBBEV_POOL_TILE3(tv, FBBEV_POOL_CPL(cpl, FBBEV_LAUNCH((k_pool_zmean_col<TV, CPL, 256>), blocks, 256, lds_col, c.stream, g.C, g.Z, (int)g.yx,
+                                                              tiles_per_plane, csplit, (int)blocks, FBBEV_POOL_GATHER(c.in), meta, o.out)));
+        FBBEV_CHECK_LAUNCH();
+        return 0;
+    }
+    FBBEV_POOL_TILE3(tv, FBBEV_POOL_CPL(cpl, FBBEV_LAUNCH((k_pool_zmean<TV, CPL, 256>), blocks * z_groups, 256, lds, c.stream, g.C, g.Z, (int)g.yx,
+                                                          tiles_per_plane, csplit, (int)blocks, FBBEV_POOL_GATHER(c.in), meta, o.out, z_groups,
+                                                          o.partial, o.rows_out, o.row_bias)));
+    FBBEV_CHECK_LAUNCH();
+    if (z_groups > 1) {
+        FBBEV_LAUNCH(k_pool_zmean_reduce, (n_out / 4 + 255) / 256, 256, 0, c.stream, (const float*)o.partial, n_out, z_groups, (float)g.Z,
+                     o.out);
+        FBBEV_CHECK_LAUNCH();
+    }
+    return 0;
+}
 
 extern "C" int fbbev_pool_zmean(const float* depth, const float* feat, const int32_t* ranks_depth,
                                 const int32_t* ranks_feat, const int32_t* interval_rank,
                                 const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C, int Z,
                                 int Y, int X, float* out_mean, const void* tile_ws, size_t tile_ws_bytes,
                                 int tile_voxels, int flags, fbbev_stream_t stream_) {
-    return pool_zmean_impl(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C, Z, Y, X,
-                           out_mean, tile_ws, tile_ws_bytes, tile_voxels, flags, 1, nullptr, 0, stream_);
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    return pool_zmean(c, {out_mean, 1, nullptr, 0, 0, nullptr});
 }
 
 // fbbev_pool_zmean with the Z planes of a tile dealt to z_groups workgroups (each walks ceil(Z / z_groups) planes) and a caller-owned
@@ -1134,77 +1229,9 @@ extern "C" int fbbev_pool_zmean_split(const float* depth, const float* feat, con
                                       fbbev_stream_t stream_) {
     if (z_groups < 1 || z_groups > 64) return FBBEV_E_BADARG;
     if (z_groups > 1 && (!partial_ws || !aligned16(partial_ws))) return FBBEV_E_BADARG;
-    return pool_zmean_impl(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C, Z, Y, X,
-                           out_mean, tile_ws, tile_ws_bytes, tile_voxels, flags, z_groups, static_cast<float*>(partial_ws),
-                           partial_ws_bytes, stream_);
-}
-
-static int pool_zmean_impl(const float* depth, const float* feat, const int32_t* ranks_depth,
-                           const int32_t* ranks_feat, const int32_t* interval_rank,
-                           const int32_t* interval_starts, const int32_t* interval_lengths, int B, int C, int Z,
-                           int Y, int X, float* out_mean, const void* tile_ws, size_t tile_ws_bytes,
-                           int tile_voxels, int flags, int z_groups, float* partial, size_t partial_bytes, fbbev_stream_t stream_,
-                           int rows_out, const float* row_bias) {
-    if (B <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return FBBEV_E_BADARG;
-    if (rows_out && (z_groups != 1 || (row_bias && !aligned16(row_bias)))) return FBBEV_E_UNSUPPORTED;
-    if (!depth || !feat || !ranks_depth || !ranks_feat || !interval_rank || !interval_starts || !interval_lengths ||
-        !out_mean || !tile_ws) return FBBEV_E_BADARG;
-    const long long yx = (long long)Y * X;
-    if (C % 4 != 0 || C > 256 || yx % 4 != 0 || !aligned16(out_mean) || !aligned16(feat)) return FBBEV_E_UNSUPPORTED;
-    if ((long long)B * Z * yx >= (1ll << 31) || (flags & FBBEV_POOL_CHANNELS_LAST)) return FBBEV_E_UNSUPPORTED;
-    const int TV = pick_tile(tile_voxels);
-    if (TV > 256) return FBBEV_E_UNSUPPORTED;
-    const int tiles_per_plane = (int)((yx + TV - 1) / TV);
-    const long long n_tiles = (long long)B * Z * tiles_per_plane;
-    if (tile_ws_bytes < (size_t)(n_tiles + 1) * 8) return FBBEV_E_WORKSPACE;
-    int csplit = (flags >> FBBEV_POOL_CSPLIT_SHIFT) & 0xF;
-    if (csplit == 0xF) csplit = 20;
-    if (csplit < 1) csplit = 1;
-    if (C % (4 * csplit) != 0) csplit = 1;
-    const int CC = C / csplit;
-    const bool cpl8 = (flags & FBBEV_POOL_CPL8) && (CC % 8 == 0);
-    if (256 / (CC / (cpl8 ? 8 : 4)) < 1) return FBBEV_E_UNSUPPORTED;
-    const size_t lds = ((size_t)CC * (TV + 4) + 3 * (size_t)TV + 2 * FBBEV_NP_STAGE) * sizeof(float);
-    if (lds > 64 * 1024) return FBBEV_E_UNSUPPORTED;
-    const long long blocks = (long long)B * tiles_per_plane * csplit;
-    if (z_groups > Z) z_groups = Z;
-    const long long n_out = (long long)B * C * yx;
-    if (z_groups > 1 && partial_bytes < (size_t)z_groups * n_out * sizeof(float)) return FBBEV_E_WORKSPACE;
-    if (blocks * z_groups >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const int* meta = static_cast<const int*>(tile_ws);
-    // round 5: the column form (every plane's metadata at once, a lane group per pixel; the same bits) when the column's slot table
-    // fits -- OPT-IN (FBBEV_ZMEAN_COL=1): built to cut the Z dependent round-trip chains of the plane walk, measured SLOWER at the
-    // BASELINE configs[2] grid, B = 4 (135.7 vs 103.9 us, S3 1.395 vs 1.360 ms: profiles/r05_exp_zmean_col.md -- 54 KB of LDS = 2
-    // workgroups per CU instead of 5, and a lane group's pixels are a serial chain of their own)
-    FBBEV_KNOB_ONCE(bool, col_on, fbbev_env_int("FBBEV_ZMEAN_COL", 0) != 0);
-    const size_t lds_col = fbbev_zmean_col_lds_bytes(CC, TV, Z);
-    if (col_on && !rows_out && z_groups == 1 && Z <= 64 && lds_col <= 64 * 1024) {
-#define FBBEV_ZMEAN_COL(TV_, CPL_)                                                                                   \
-    FBBEV_LAUNCH((k_pool_zmean_col<TV_, CPL_, 256>), blocks, 256, lds_col, (fbbev_rt_stream)stream_, C, Z, (int)yx,   \
-                 tiles_per_plane, csplit, (int)blocks, depth, feat, ranks_depth, ranks_feat, interval_rank,          \
-                 interval_starts, interval_lengths, meta, out_mean)
-        if (TV == 64) { if (cpl8) FBBEV_ZMEAN_COL(64, 8); else FBBEV_ZMEAN_COL(64, 4); }
-        else if (TV == 128) { if (cpl8) FBBEV_ZMEAN_COL(128, 8); else FBBEV_ZMEAN_COL(128, 4); }
-        else { if (cpl8) FBBEV_ZMEAN_COL(256, 8); else FBBEV_ZMEAN_COL(256, 4); }
-#undef FBBEV_ZMEAN_COL
-        FBBEV_CHECK_LAUNCH();
-        return 0;
-    }
-#define FBBEV_ZMEAN(TV_, CPL_)                                                                                       \
-    FBBEV_LAUNCH((k_pool_zmean<TV_, CPL_, 256>), blocks * z_groups, 256, lds, (fbbev_rt_stream)stream_, C, Z, (int)yx, \
-                 tiles_per_plane, csplit, (int)blocks, depth, feat, ranks_depth, ranks_feat, interval_rank,          \
-                 interval_starts, interval_lengths, meta, out_mean, z_groups, partial, rows_out, row_bias)
-    if (TV == 64) { if (cpl8) FBBEV_ZMEAN(64, 8); else FBBEV_ZMEAN(64, 4); }
-    else if (TV == 128) { if (cpl8) FBBEV_ZMEAN(128, 8); else FBBEV_ZMEAN(128, 4); }
-    else { if (cpl8) FBBEV_ZMEAN(256, 8); else FBBEV_ZMEAN(256, 4); }
-#undef FBBEV_ZMEAN
-    FBBEV_CHECK_LAUNCH();
-    if (z_groups > 1) {
-        FBBEV_LAUNCH(k_pool_zmean_reduce, (n_out / 4 + 255) / 256, 256, 0, (fbbev_rt_stream)stream_, (const float*)partial, n_out,
-                     z_groups, (float)Z, out_mean);
-        FBBEV_CHECK_LAUNCH();
-    }
-    return 0;
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    return pool_zmean(c, {out_mean, z_groups, static_cast<float*>(partial_ws), partial_ws_bytes, 0, nullptr});
 }
 
 // fbbev_pool_zmean with the result written as the backward projection's QUERY ROWS: out_rows (B, Y*X, C) = mean + row_bias (Y*X, C)
@@ -1215,8 +1242,9 @@ extern "C" int fbbev_pool_zmean_rows(const float* depth, const float* feat, cons
                                      const int32_t* interval_lengths, int B, int C, int Z, int Y, int X, const float* row_bias,
                                      float* out_rows, const void* tile_ws, size_t tile_ws_bytes, int tile_voxels, int flags,
                                      fbbev_stream_t stream_) {
-    return pool_zmean_impl(depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths, B, C, Z, Y, X,
-                           out_rows, tile_ws, tile_ws_bytes, tile_voxels, flags, 1, nullptr, 0, stream_, 1, row_bias);
+    const pool_call c = {{depth, feat, ranks_depth, ranks_feat, interval_rank, interval_starts, interval_lengths}, pool_grid_of(B, C, Z, Y, X),
+                         tile_ws, tile_ws_bytes, tile_voxels, pool_flags_of(flags), (fbbev_rt_stream)stream_};
+    return pool_zmean(c, {out_rows, 1, nullptr, 0, 1, row_bias});
 }
 
 // ------------------------------------------------------------------------------ MSDeformAttn
@@ -2644,81 +2672,80 @@ extern "C" int fbbev_da_cross_attn_bwd_planes_ex(const float* planes, const int6
                       [&](const da_args& d) { return da_bwd_planes(d, level_hw_host, ws, ws_bytes, true); });
 }
 
-// ---------------------------------------------------------------- fused lift-splat backward (training)
+// ------------------------------------------------------------------------------ view-transformation pooling, continued: the fused backward
+// (training).  On the records and helpers of the pooling block above; it stands here, behind the cross-attention family, because the
+// compiler emits kernel instantiations in the order of their first use in this file, and the code objects are held byte-identical.
 struct bwd_layout { size_t table, meta, rows, total; long long n_tiles; int tpp; long long max_rows; };
 
-static bwd_layout pool_bwd_layout(int B, int N, int D, int H, int W, int C, int Z, int Y, int X) {
+static bwd_layout pool_bwd_layout(const lift_dims& d) {
     bwd_layout l;
-    const long long n = (long long)B * N * D * H * W, yx = (long long)Y * X, nvox = (long long)B * Z * yx;
+    const long long n = lift_points(d), yx = (long long)d.Y * d.X, nvox = (long long)d.B * d.Z * yx;
     l.tpp = (int)((yx + 127) / 128);
-    l.n_tiles = (long long)B * Z * l.tpp;
+    l.n_tiles = (long long)d.B * d.Z * l.tpp;
     l.max_rows = n < nvox ? n : nvox;                 // I <= min(points, voxels)
     l.table = 0;
     l.meta = align_up((size_t)n * 4, 256);
-    l.rows = l.meta + align_up((size_t)(l.n_tiles + 1) * 8, 256);
-    l.total = l.rows + align_up((size_t)l.max_rows * C * 4, 256);
+    l.rows = l.meta + align_up(pool_tile_table_bytes(l.n_tiles), 256);
+    l.total = l.rows + align_up((size_t)l.max_rows * d.C * 4, 256);
     return l;
 }
 
 extern "C" size_t fbbev_pool_dense_bwd_workspace_bytes(int B, int N, int D, int H, int W, int C, int Z, int Y, int X) {
-    if (B <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0) return 256;
-    return pool_bwd_layout(B, N, D, H, W, C, Z, Y, X).total;
+    const lift_dims d = {B, N, D, H, W, C, Z, Y, X};
+    return lift_dims_positive(d) ? pool_bwd_layout(d).total : 256;
 }
 
-static int pool_dense_bwd_impl(const float* out_grad, long long og_stride_b, long long og_stride_c,
-                               const float* depth, const float* feat, const int32_t* ranks_depth,
-                               const int32_t* interval_rank, const int32_t* interval_starts,
-                               const int32_t* counts, int n_intervals_max, int B, int N, int D,
-                               int H, int W, int C, int Z, int Y, int X, float* depth_grad,
-                               float* feat_grad, void* workspace, size_t workspace_bytes,
-                               fbbev_stream_t stream_, const float* zgrad, float zscale) {
-    if (zgrad && !aligned16(zgrad)) return FBBEV_E_UNSUPPORTED;
-    if (B <= 0 || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || Z <= 0 || Y <= 0 || X <= 0 || n_intervals_max < 0)
+struct pool_bwd_args {
+    const float* out_grad; long long og_stride_b, og_stride_c;           // (B, C, Z, Y, X), strides as the caller passed them
+    const float *depth, *feat;
+    const int32_t *rd, *irank, *starts, *counts; int n_max;
+    lift_dims d;
+    float *depth_grad, *feat_grad;
+    void* ws; size_t ws_bytes;
+    fbbev_rt_stream stream;
+    const float* zgrad; float zscale;                       // a second gradient (B, C, Y, X) every z plane receives, scaled; may be null
+};
+static int pool_dense_bwd(const pool_bwd_args& p) {
+    const lift_dims& d = p.d;
+    const int C = d.C;
+    if (p.zgrad && !aligned16(p.zgrad)) return FBBEV_E_UNSUPPORTED;      // (before the dimensions)
+    if (!lift_dims_positive(d) || p.n_max < 0) return FBBEV_E_BADARG;
+    if (!p.out_grad || !p.depth || !p.feat || !p.rd || !p.irank || !p.starts || !p.counts || !p.depth_grad || !p.feat_grad || !p.ws)
         return FBBEV_E_BADARG;
-    if (!out_grad || !depth || !feat || !ranks_depth || !interval_rank || !interval_starts || !counts ||
-        !depth_grad || !feat_grad || !workspace) return FBBEV_E_BADARG;
-    const long long yx = (long long)Y * X, n = (long long)B * N * D * H * W;
-    if (C % 4 != 0 || C > 256 || yx % 4 != 0 || !aligned16(out_grad) || !aligned16(feat) || !aligned16(feat_grad) ||
-        !aligned16(workspace)) return FBBEV_E_UNSUPPORTED;
-    if ((long long)B * Z * yx >= (1ll << 31) || n >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    if (og_stride_c == 0) og_stride_c = (long long)Z * yx;
-    if (og_stride_b == 0) og_stride_b = (long long)C * og_stride_c;
-    if (og_stride_c < (long long)Z * yx || og_stride_b < (long long)C * og_stride_c || og_stride_c % 4 != 0 ||
-        og_stride_b % 4 != 0) return FBBEV_E_BADARG;
-    const bwd_layout l = pool_bwd_layout(B, N, D, H, W, C, Z, Y, X);
-    if (workspace_bytes < l.total) return FBBEV_E_WORKSPACE;
+    const pool_grid g = pool_grid_of(d.B, C, d.Z, d.Y, d.X);
+    const long long n = lift_points(d);
+    if (C % 4 != 0 || C > 256 || g.yx % 4 != 0 || !aligned16(p.out_grad) || !aligned16(p.feat) || !aligned16(p.feat_grad) ||
+        !aligned16(p.ws)) return FBBEV_E_UNSUPPORTED;
+    if (!pool_grid_fits_int(g) || n >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    const pool_strides s = pool_volume_strides(p.og_stride_b, p.og_stride_c, g);
+    if (s.err) return s.err;
+    const bwd_layout l = pool_bwd_layout(d);
+    if (p.ws_bytes < l.total) return FBBEV_E_WORKSPACE;
     const size_t lds = (size_t)C * (128 + 4) * 4;
     if (lds > 160 * 1024) return FBBEV_E_UNSUPPORTED;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-    char* ws = static_cast<char*>(workspace);
+    char* ws = static_cast<char*>(p.ws);
     int* table = reinterpret_cast<int*>(ws + l.table);
     int* meta = reinterpret_cast<int*>(ws + l.meta);
     float* rows = reinterpret_cast<float*>(ws + l.rows);
-    int e = fbbev_rt_memset_async(table, 0xFF, (size_t)n * 4, stream);      // -1 = point dropped
+    int e = fbbev_rt_memset_async(table, 0xFF, (size_t)n * 4, p.stream);      // -1 = point dropped
     if (e) return e;
     {
         long long blocks = (n + 255) / 256;      // P <= n, grid-stride over the device-side P
         if (blocks > 8192) blocks = 8192;
-        FBBEV_LAUNCH(k_point_row_table, blocks, 256, 0, stream, ranks_depth, interval_starts, counts,
-                     n_intervals_max, table);
+        FBBEV_LAUNCH(k_point_row_table, blocks, 256, 0, p.stream, p.rd, p.starts, p.counts, p.n_max, table);
         FBBEV_CHECK_LAUNCH();
     }
-    FBBEV_LAUNCH(k_tile_lower_bound2, (l.n_tiles + 1 + 255) / 256, 256, 0, stream, (int)l.n_tiles, l.tpp, (int)yx,
-                 128, interval_rank, interval_starts, counts, n_intervals_max, (const int*)nullptr, meta);
+    FBBEV_LAUNCH(k_tile_lower_bound2, (l.n_tiles + 1 + 255) / 256, 256, 0, p.stream, (int)l.n_tiles, l.tpp, (int)g.yx,
+                 128, p.irank, p.starts, p.counts, p.n_max, (const int*)nullptr, meta);
     FBBEV_CHECK_LAUNCH();
-    FBBEV_LAUNCH_DYN_LDS(k_pool_bwd_rows<128>, l.n_tiles, 256, lds, stream, C, Z, (int)yx, l.tpp, og_stride_b, og_stride_c,
-                         out_grad, interval_rank, meta, rows, zgrad, zscale);
+    FBBEV_LAUNCH_DYN_LDS(k_pool_bwd_rows<128>, l.n_tiles, 256, lds, p.stream, C, d.Z, (int)g.yx, l.tpp, s.b, s.c,
+                         p.out_grad, p.irank, meta, rows, p.zgrad, p.zscale);
     FBBEV_CHECK_LAUNCH();
-    const long long n_pixels = (long long)B * N * H * W;
+    const long long n_pixels = (long long)d.B * d.N * d.H * d.W;
     const long long blocks = (n_pixels + 7) / 8;      // 8 half-waves per 256-thread workgroup
-    if (C <= 128)
-        FBBEV_LAUNCH(k_pool_bwd_pixel<4>, blocks, 256, 0, stream, C, D, H * W, n_pixels, (long long)C, rows, depth,
-                     feat, table, depth_grad, feat_grad);
-    else if (C % 8 == 0)
-        FBBEV_LAUNCH(k_pool_bwd_pixel<8>, blocks, 256, 0, stream, C, D, H * W, n_pixels, (long long)C, rows, depth,
-                     feat, table, depth_grad, feat_grad);
-    else
-        return FBBEV_E_UNSUPPORTED;
+    if (C > 128 && C % 8 != 0) return FBBEV_E_UNSUPPORTED;               // (only here, behind three launches: see the table of entries)
+    FBBEV_POOL_WITH(CPL, C <= 128 ? 4 : 8, 4, 8, FBBEV_LAUNCH(k_pool_bwd_pixel<CPL>, blocks, 256, 0, p.stream, C, d.D, d.H * d.W, n_pixels,
+                                                              (long long)C, rows, p.depth, p.feat, table, p.depth_grad, p.feat_grad));
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -2730,9 +2757,9 @@ extern "C" int fbbev_bev_pool_v2_dense_bwd(const float* out_grad, long long og_s
                                            int H, int W, int C, int Z, int Y, int X, float* depth_grad,
                                            float* feat_grad, void* workspace, size_t workspace_bytes,
                                            fbbev_stream_t stream_) {
-    return pool_dense_bwd_impl(out_grad, og_stride_b, og_stride_c, depth, feat, ranks_depth, interval_rank, interval_starts, counts,
-                               n_intervals_max, B, N, D, H, W, C, Z, Y, X, depth_grad, feat_grad, workspace, workspace_bytes, stream_,
-                               nullptr, 0.f);
+    return pool_dense_bwd({out_grad, og_stride_b, og_stride_c, depth, feat, ranks_depth, interval_rank, interval_starts, counts,
+                           n_intervals_max, {B, N, D, H, W, C, Z, Y, X}, depth_grad, feat_grad, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_, nullptr, 0.f});
 }
 // ... with a second gradient (B, C, Y, X) that every z plane receives, scaled by zscale: out_grad_eff = out_grad + zscale * zgrad[..., None]
 extern "C" int fbbev_bev_pool_v2_dense_bwd_z(const float* out_grad, long long og_stride_b, long long og_stride_c,
@@ -2742,9 +2769,9 @@ extern "C" int fbbev_bev_pool_v2_dense_bwd_z(const float* out_grad, long long og
                                              int N, int D, int H, int W, int C, int Z, int Y, int X, float* depth_grad,
                                              float* feat_grad, void* workspace, size_t workspace_bytes, fbbev_stream_t stream_) {
     if (!zgrad) return FBBEV_E_BADARG;
-    return pool_dense_bwd_impl(out_grad, og_stride_b, og_stride_c, depth, feat, ranks_depth, interval_rank, interval_starts, counts,
-                               n_intervals_max, B, N, D, H, W, C, Z, Y, X, depth_grad, feat_grad, workspace, workspace_bytes, stream_,
-                               zgrad, zscale);
+    return pool_dense_bwd({out_grad, og_stride_b, og_stride_c, depth, feat, ranks_depth, interval_rank, interval_starts, counts,
+                           n_intervals_max, {B, N, D, H, W, C, Z, Y, X}, depth_grad, feat_grad, workspace, workspace_bytes,
+                           (fbbev_rt_stream)stream_, zgrad, zscale});
 }
 
 // ------------------------------------------------------------------------------ temporal history fusion

@@ -163,9 +163,29 @@ inline float __fmul_rn(float a, float b) { volatile float r = a * b; return r; }
 inline float __fdiv_rn(float a, float b) { volatile float r = a / b; return r; }
 inline float __expf(float x) { return expf(x); }   // device fast exp (v_exp_f32 based): the emulator uses libm's
 
+// The launch log: which kernel instantiation every FBBEV_LAUNCH of this thread ran, on what grid, block and dynamic LDS -- the
+// route a call took, which its results cannot show (tests/test_emu_pool_launch_record.py).
+namespace emu {
+struct LaunchRecord { const char* kernel; long long grid, block, lds; };
+inline std::vector<LaunchRecord>& launch_log() { static thread_local std::vector<LaunchRecord> log; return log; }
+// g++ spells the whole instantiation: "... [with auto K = k_pool_fwd_dense2<128, 8, 4, 256, 1, true, 1>]"
+template <auto K> const char* kname() { return __PRETTY_FUNCTION__; }
+}  // namespace emu
+extern "C" __attribute__((used, visibility("default"))) inline void fbbev_emu_launch_log_clear(void) { emu::launch_log().clear(); }
+// the number of launches logged; record i (when there is one) as its kernel's text and {grid, block, lds bytes}
+extern "C" __attribute__((used, visibility("default"))) inline int fbbev_emu_launch_log_read(int i, const char** kernel, long long* grid_block_lds) {
+    const std::vector<emu::LaunchRecord>& log = emu::launch_log();
+    if (i >= 0 && i < (int)log.size()) {
+        *kernel = log[i].kernel;
+        grid_block_lds[0] = log[i].grid; grid_block_lds[1] = log[i].block; grid_block_lds[2] = log[i].lds;
+    }
+    return (int)log.size();
+}
+
 typedef void* fbbev_rt_stream;
-#define FBBEV_LAUNCH(kern, grid, block, lds_bytes, stream, ...) \
-    emu::launch((unsigned)(grid), (unsigned)(block), (size_t)(lds_bytes), [=]() { kern(__VA_ARGS__); })
+#define FBBEV_LAUNCH(kern, grid, block, lds_bytes, stream, ...)                                                                    \
+    (emu::launch_log().push_back({emu::kname<kern>(), (long long)(unsigned)(grid), (long long)(unsigned)(block), (long long)(lds_bytes)}), \
+     emu::launch((unsigned)(grid), (unsigned)(block), (size_t)(lds_bytes), [=]() { kern(__VA_ARGS__); }))
 static inline int fbbev_rt_last_error() { return 0; }
 typedef int fbbev_rt_event;                                  // launches are synchronous here: streams and events are no-ops
 static inline int fbbev_rt_device() { return 0; }

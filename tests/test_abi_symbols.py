@@ -1055,3 +1055,375 @@ def test_history_entries_keep_their_error_codes():
     assert got == want, [(g, w[2]) for g, w in zip(got, want) if g != w]
     assert {entry for entry, _, _ in table} == set(H_PARAMS)
     assert [lib.fbbev_layernorm_bwd_partials(r) for r in (-1, 0, 1, 8, 9, 16384, 16385, 1 << 40)] == [1, 1, 1, 1, 2, 2048, 2048, 2048]
+
+
+# ---- the pooling family (tile index, dense forward in its planar / channels-last / row / pipelined forms, Z-mean, one-entry
+# lift-splat, store-floor diagnostic, fused backward): one table, recorded on the launchers before they shared their operand records
+PL_GATHER = ['depth', 'feat', 'ranks_depth', 'ranks_feat', 'interval_rank', 'interval_starts', 'interval_lengths', 'B', 'C', 'Z', 'Y', 'X']
+PL_TABLE = ['tile_ws', 'tile_ws_bytes', 'tile_voxels', 'flags']
+PL_INDEX = ['interval_rank', 'interval_starts', 'counts', 'n_intervals_max', 'B', 'Z', 'Y', 'X', 'tile_voxels', 'flags', 'tile_ws', 'tile_ws_bytes']
+PL_BWD = ['depth', 'feat', 'ranks_depth', 'interval_rank', 'interval_starts', 'counts', 'n_intervals_max', 'B', 'N', 'D', 'H', 'W', 'C',
+          'Z', 'Y', 'X', 'depth_grad', 'feat_grad', 'workspace', 'workspace_bytes', 'stream']
+PL_PARAMS = {
+    'pool_tile_index': PL_INDEX + ['stream'],
+    'pool_tile_index_cached': PL_INDEX + ['cache_state', 'table_gate', 'stream'],
+    'bev_pool_v2_dense_fwd': PL_GATHER + ['out', 'out_stride_b', 'out_stride_c'] + PL_TABLE + ['stream'],
+    'bev_pool_v2_dense_fwd_add': PL_GATHER + ['out', 'out_stride_b', 'out_stride_c'] + PL_TABLE + ['addend', 'stream'],
+    'bev_pool_v2_dense_fwd_rows': PL_GATHER + ['out_rows', 'out_stride_b', 'addend_rows', 'addend_row_stride'] + PL_TABLE + ['stream'],
+    'diag_pool_store_floor': PL_GATHER + ['out'] + PL_TABLE + ['mode', 'stream'],
+    'lift_splat_fused': ['frustum', 'xs', 'ys', 'ds', 'rots', 'trans', 'intrins', 'post_rots', 'post_trans', 'bda', 'depth', 'context',
+                         'B', 'N', 'D', 'H', 'W', 'C', 'lower3', 'interval3', 'grid_size3', 'Z', 'Y', 'X', 'out', 'out_stride_b',
+                         'out_stride_c', 'tile_voxels', 'flags', 'workspace', 'workspace_bytes', 'cam_key', 'cache_state', 'stream'],
+    'pool_zmean': PL_GATHER + ['out_mean'] + PL_TABLE + ['stream'],
+    'pool_zmean_split': PL_GATHER + ['out_mean'] + PL_TABLE + ['z_groups', 'partial_ws', 'partial_ws_bytes', 'stream'],
+    'pool_zmean_rows': PL_GATHER + ['row_bias', 'out_rows'] + PL_TABLE + ['stream'],
+    'bev_pool_v2_dense_bwd': ['out_grad', 'og_stride_b', 'og_stride_c'] + PL_BWD,
+    'bev_pool_v2_dense_bwd_z': ['out_grad', 'og_stride_b', 'og_stride_c', 'zgrad', 'zscale'] + PL_BWD,
+}
+# a call that would LAUNCH (so no row below is this alone): one sample of one 2 x 4 camera with 2 depth bins, 16 channels into a
+# 12 x 12 x 3 grid (432 voxels), 128-voxel tiles (6 planar tiles: a table of 56 bytes; 4 flat ones: 40; 27 of 16 voxels: 216),
+# `sc1 nt` stores, 8 channels per lane, dense strides, workspaces of any size; every pointer non-null and 16-byte aligned
+PL_SC1_NT, PL_CPL8, PL_WG128, PL_CL, PL_BF16, PL_F16, PL_SPLIT, PL_PIPE, PL_G8 = (0x20000, 0x4, 0x100, 0x100000, 0x800000, 0x1000000,
+                                                                                 0x2000000, 0x4000000, 0x8000000)
+PL_BASE = dict(B=1, N=1, D=2, H=2, W=4, C=16, Z=3, Y=12, X=12, tile_voxels=128, flags=PL_SC1_NT | PL_CPL8, n_intervals_max=10,
+               out_stride_b=0, out_stride_c=0, og_stride_b=0, og_stride_c=0, addend_row_stride=0, tile_ws_bytes=1 << 40,
+               workspace_bytes=1 << 40, partial_ws_bytes=1 << 40, mode=1, z_groups=1, zscale=0.5, stream=DA_NULL)
+PL_2G_VOXELS = dict(Z=2048, Y=1024, X=1024)                          # 2^31 voxels
+PL_BELOW_2G = dict(Z=2047, Y=1024, X=1024)
+PL_2G_POINTS = dict(N=2048, D=1024, H=1024, W=1)                     # 2^31 frustum points
+PL_POINTS_BELOW_2G = dict(N=2048, D=1023, H=1024, W=1)
+PL_2G_WGS = dict(B=1 << 14, Z=1 << 14, Y=2, X=2, C=32, tile_voxels=64)   # 2^28 one-tile planes (2^30 voxels): x a channel split of 8
+PL_LIFT_WS = 1189120                                                    # fbbev_lift_splat_fused_ws_bytes / _dense_bwd_workspace_bytes of PL_BASE
+PL_BWD_WS = 1536
+
+
+def pl_call(lib, entry, case):
+    """`entry` with PL_BASE's operands, `case` on top of them; 'null': every pointer the entry takes is null unless `case` names it"""
+    case = dict(case)
+    null = case.pop('null', False)
+    args = []
+    for name in PL_PARAMS[entry]:
+        if name in case:
+            args.append(case.pop(name))
+        elif name in PL_BASE:
+            args.append(PL_BASE[name])
+        else:
+            args.append(DA_NULL if null else DA_P16)
+    assert not case, (entry, 'operands the entry does not take', case)
+    return getattr(lib, 'fbbev_' + entry)(*args)
+
+
+def test_pool_entries_keep_their_error_codes():
+    """Every entry of the pooling family: the code of each argument check, which code wins where two defects coincide (the order of
+    an entry's checks is part of the ABI), and the routes a flags word refuses.  Every row returns BEFORE the entry's first runtime
+    call (a launch, a memset, the opt-in to large LDS), so this runs without a GPU; what lies behind a launch -- the tile index
+    inside fbbev_pool_tile_index_cached and fbbev_lift_splat_fused, the backward's `C > 128 && C % 8` -- is on the emulator
+    (tests/test_emu_pool_launch_record.py).  The four host functions are pinned as values."""
+    lib = _capi.declare(ctypes.CDLL(_capi.LIB_PATH))
+    NULL, P16, P8 = DA_NULL, DA_P16, DA_P8
+    F, CL = PL_SC1_NT | PL_CPL8, PL_CL
+    GATHER7 = PL_GATHER[:7]
+    table = []
+    row = lambda entry, case, code: table.append((entry, case, code))   # noqa: E731
+    # ---- fbbev_pool_tile_index: dimensions, pointers, 2^31 voxels (-2), the table's bytes per form (-3)
+    for k in ('B', 'Z', 'Y', 'X'):
+        row('pool_tile_index', {k: 0}, -1)
+    row('pool_tile_index', dict(n_intervals_max=-1), -1)
+    for k in ('interval_rank', 'interval_starts', 'counts', 'tile_ws'):
+        row('pool_tile_index', {k: NULL}, -1)
+    row('pool_tile_index', dict(B=0, null=True), -1)
+    row('pool_tile_index', PL_2G_VOXELS, -2)
+    row('pool_tile_index', dict(PL_2G_VOXELS, counts=NULL), -1)
+    row('pool_tile_index', dict(PL_2G_VOXELS, tile_ws_bytes=0), -2)
+    row('pool_tile_index', dict(PL_BELOW_2G, tile_ws_bytes=0), -3)
+    row('pool_tile_index', dict(PL_2G_VOXELS, flags=CL, tile_voxels=16, tile_ws_bytes=0), -2)
+    row('pool_tile_index', dict(PL_BELOW_2G, flags=CL, tile_voxels=16, tile_ws_bytes=0), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=55), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=79, tile_voxels=64), -3)              # 9 tiles
+    row('pool_tile_index', dict(tile_ws_bytes=79, tile_voxels=100), -3)             # no tile size: 64
+    row('pool_tile_index', dict(tile_ws_bytes=31, tile_voxels=256), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=79, tile_voxels=16), -3)              # small tiles only with channels-last: 64 here
+    row('pool_tile_index', dict(tile_ws_bytes=39, flags=CL), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=63, flags=CL, tile_voxels=64), -3)    # 7 flat tiles
+    row('pool_tile_index', dict(tile_ws_bytes=215, flags=CL, tile_voxels=16), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=431, flags=CL, tile_voxels=8), -3)
+    row('pool_tile_index', dict(tile_ws_bytes=111, flags=CL, tile_voxels=32), -3)
+    # ---- fbbev_pool_tile_index_cached: its own two checks; the gate kernel is launched before the shared ones run
+    row('pool_tile_index_cached', dict(cache_state=NULL), -1)
+    row('pool_tile_index_cached', dict(table_gate=NULL), -1)
+    row('pool_tile_index_cached', dict(flags=CL, tile_voxels=16), -2)
+    row('pool_tile_index_cached', dict(flags=CL, tile_voxels=8, B=0), -2)
+    row('pool_tile_index_cached', dict(flags=CL, tile_voxels=32, table_gate=NULL), -1)
+    # ---- fbbev_bev_pool_v2_dense_fwd[_add]: dimensions, pointers, shape and alignment (-2), 2^31 voxels (-2), strides (-1), table
+    # bytes (-3), THEN the storage flags, the addend, the channels-last rules, LDS and workgroup bounds, the routes
+    for fwd in ('bev_pool_v2_dense_fwd', 'bev_pool_v2_dense_fwd_add'):
+        for k in ('B', 'C', 'Z', 'Y', 'X'):
+            row(fwd, {k: 0}, -1)
+        for k in GATHER7 + ['out', 'tile_ws']:
+            row(fwd, {k: NULL}, -1)
+        row(fwd, dict(C=18), -2)
+        row(fwd, dict(C=260), -2)
+        row(fwd, dict(Y=1, X=6), -2)
+        row(fwd, dict(out=P8), -2)
+        row(fwd, dict(feat=P8), -2)
+        row(fwd, dict(C=18, out=NULL), -1)
+        row(fwd, dict(C=18, out_stride_c=1), -2)
+        row(fwd, PL_2G_VOXELS, -2)
+        row(fwd, dict(PL_2G_VOXELS, out_stride_c=4), -2)
+        row(fwd, dict(PL_BELOW_2G, out_stride_c=4), -1)
+        row(fwd, dict(PL_BELOW_2G, tile_ws_bytes=0), -3)
+        row(fwd, dict(out_stride_c=428), -1)
+        row(fwd, dict(out_stride_c=434), -1)
+        row(fwd, dict(out_stride_c=436, out_stride_b=16 * 436 - 4), -1)
+        row(fwd, dict(out_stride_b=16 * 432 + 2), -1)
+        row(fwd, dict(out_stride_b=16 * 432 - 4), -1)
+        row(fwd, dict(out_stride_c=428, tile_ws_bytes=0), -1)
+        row(fwd, dict(tile_ws_bytes=55), -3)
+        row(fwd, dict(tile_ws_bytes=79, tile_voxels=64), -3)
+        row(fwd, dict(tile_ws_bytes=79, tile_voxels=16), -3)                        # no planar tile size: 64
+        row(fwd, dict(tile_ws_bytes=31, tile_voxels=256), -3)
+        row(fwd, dict(flags=F | PL_BF16 | PL_F16), -1)
+        row(fwd, dict(flags=F | PL_BF16 | PL_F16, tile_ws_bytes=55), -3)            # the storage flags come after the table's bytes
+        row(fwd, dict(flags=F | PL_BF16 | PL_F16 | CL), -1)
+        row(fwd, dict(flags=F | PL_BF16 | CL), -2)
+        row(fwd, dict(flags=F | PL_F16 | CL), -2)
+        row(fwd, dict(flags=F | PL_BF16 | CL, tile_ws_bytes=55), -3)
+        row(fwd, dict(flags=F | PL_BF16, Y=6, X=6), -2)                             # Y * X % 8
+        row(fwd, dict(flags=F | PL_F16, out_stride_c=436), -2)
+        row(fwd, dict(flags=F | PL_BF16, out_stride_b=16 * 432 + 4), -2)
+        # channels-last: dense strides only (-1), the small tiles' table (-3) and thread count (-2), the flat tiles' table (-3)
+        if fwd == 'bev_pool_v2_dense_fwd':                                          # (with an addend channels-last is -2 before any of it)
+            row(fwd, dict(flags=F | CL, out_stride_c=436), -1)
+            row(fwd, dict(flags=F | CL, out_stride_b=16 * 432 + 4), -1)
+            row(fwd, dict(flags=F | CL, out_stride_b=16 * 432 + 4, tile_ws_bytes=0), -3)   # the planar table, never smaller than the flat one
+            row(fwd, dict(flags=F | CL, tile_voxels=16, out_stride_c=436, tile_ws_bytes=215), -1)
+            row(fwd, dict(flags=F | CL, tile_voxels=16, tile_ws_bytes=215), -3)
+            row(fwd, dict(flags=F | CL, tile_voxels=8, tile_ws_bytes=431), -3)
+            row(fwd, dict(flags=F | CL, tile_voxels=32, C=132), -2)                     # 33 * 32 lanes
+            row(fwd, dict(flags=F | CL, tile_voxels=32, C=132, tile_ws_bytes=111), -3)
+            row(fwd, dict(flags=F | CL, tile_voxels=32, C=132, tile_ws_bytes=55), -3)   # (the planar table's bytes are looked at first)
+        # LDS above 160 KiB and 2^31 workgroups (-2), behind the table's bytes
+        row(fwd, dict(tile_voxels=1024, C=256), -2)
+        row(fwd, dict(tile_voxels=1024, C=40), -2)
+        row(fwd, dict(tile_voxels=1024, C=256, tile_ws_bytes=31), -3)
+        row(fwd, dict(tile_voxels=256, C=160, flags=F | PL_PIPE), -2)              # the pipe's second staging buffer tips it over
+        row(fwd, dict(PL_2G_WGS, flags=F | (8 << 4)), -2)
+        # routes a flags word refuses: split-long / gather-8 are built for 256 threads, fp32, `sc1 nt`, 64- / 128-voxel tiles
+        for route in (PL_SPLIT, PL_G8, PL_SPLIT | PL_G8):
+            row(fwd, dict(flags=F | route | PL_WG128), -2)
+            row(fwd, dict(flags=F | route | PL_BF16), -2)
+            row(fwd, dict(flags=F | route | PL_F16), -2)
+            row(fwd, dict(flags=PL_CPL8 | route), -2)
+            row(fwd, dict(flags=PL_CPL8 | route | 1), -2)
+            row(fwd, dict(flags=F | route, tile_voxels=256), -2)
+            row(fwd, dict(flags=F | route, tile_voxels=1024), -2)
+            row(fwd, dict(flags=F | route | PL_PIPE | PL_WG128), -2)
+            row(fwd, dict(flags=F | route | PL_WG128, tile_ws_bytes=55), -3)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=NULL), -1)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=NULL, C=18), -1)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=NULL, flags=F | CL), -1)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=P8), -2)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=P8, B=0), -1)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=P8, tile_ws_bytes=55), -3)
+    row('bev_pool_v2_dense_fwd_add', dict(addend=P8, flags=F | PL_BF16 | PL_F16), -1)
+    row('bev_pool_v2_dense_fwd_add', dict(flags=F | CL), -2)                        # no addend with channels-last
+    row('bev_pool_v2_dense_fwd_add', dict(flags=F | CL, out_stride_c=436), -2)      # ... seen before its stride rule
+    row('bev_pool_v2_dense_fwd_add', dict(flags=F | CL, tile_voxels=16, tile_ws_bytes=215), -2)
+    row('bev_pool_v2_dense_fwd_add', dict(flags=F | CL, tile_voxels=32, C=132), -2)
+    row('bev_pool_v2_dense_fwd_add', dict(flags=F | CL, tile_ws_bytes=0), -3)
+    # ---- fbbev_bev_pool_v2_dense_fwd_rows: both storage flags (-1) right after the pointers, flat index (-2), strides (-1), rows (-2)
+    rows = 'bev_pool_v2_dense_fwd_rows'
+    for k in ('B', 'C', 'Z', 'Y', 'X'):
+        row(rows, {k: 0}, -1)
+    for k in GATHER7 + ['out_rows', 'tile_ws']:
+        row(rows, {k: NULL}, -1)
+    row(rows, dict(flags=F | PL_BF16 | PL_F16), -1)
+    row(rows, dict(flags=F | PL_BF16 | PL_F16, tile_ws_bytes=0), -1)                # ... before the table's bytes here
+    row(rows, dict(PL_2G_VOXELS, flags=F | PL_BF16 | PL_F16), -1)
+    row(rows, PL_2G_VOXELS, -2)
+    row(rows, dict(B=2, Z=1, Y=1 << 15, X=1 << 15), -2)
+    row(rows, dict(B=1, Z=1, Y=1 << 16, X=1 << 15), -2)
+    row(rows, dict(PL_2G_VOXELS, out_stride_b=16), -2)
+    row(rows, dict(PL_BELOW_2G, out_stride_b=16), -1)
+    row(rows, dict(PL_BELOW_2G, tile_ws_bytes=0), -3)
+    row(rows, dict(out_stride_b=432 * 16 - 4), -1)
+    row(rows, dict(addend_row_stride=12), -1)
+    row(rows, dict(addend_row_stride=12, C=18), -1)
+    row(rows, dict(addend_rows=NULL, addend_row_stride=12), -1)                     # the stride is looked at without an addend too
+    row(rows, dict(C=18), -2)
+    row(rows, dict(C=260), -2)
+    row(rows, dict(C=20, flags=F | PL_BF16), -2)                                    # 16-bit rows: C % 8
+    row(rows, dict(out_stride_b=432 * 16 + 4, B=2, flags=F | PL_F16), -2)
+    row(rows, dict(out_stride_b=432 * 16 + 2, B=2), -2)
+    row(rows, dict(addend_row_stride=18), -2)
+    row(rows, dict(out_rows=P8), -2)
+    row(rows, dict(feat=P8), -2)
+    row(rows, dict(addend_rows=P8), -2)
+    row(rows, dict(C=18, tile_ws_bytes=0), -2)
+    row(rows, dict(tile_voxels=16), -2)
+    row(rows, dict(tile_voxels=8, tile_ws_bytes=0), -2)
+    row(rows, dict(tile_ws_bytes=39), -3)
+    row(rows, dict(tile_ws_bytes=63, tile_voxels=64), -3)
+    row(rows, dict(tile_ws_bytes=63, tile_voxels=100, addend_rows=NULL), -3)
+    # ---- fbbev_diag_pool_store_floor: one instantiation; LDS bound 64 KiB
+    diag = 'diag_pool_store_floor'
+    for k in ('B', 'C', 'Z', 'Y', 'X'):
+        row(diag, {k: 0}, -1)
+    row(diag, dict(mode=0), -1)
+    row(diag, dict(mode=4), -1)
+    for k in GATHER7 + ['out', 'tile_ws']:
+        row(diag, {k: NULL}, -1)
+    row(diag, dict(tile_voxels=64, out=NULL), -1)
+    row(diag, dict(tile_voxels=64), -2)
+    row(diag, dict(tile_voxels=100), -2)
+    row(diag, dict(Y=1, X=6), -2)
+    row(diag, dict(Y=6, X=6, flags=F | PL_BF16), -2)
+    row(diag, dict(out=P8), -2)
+    row(diag, dict(flags=F | CL), -2)
+    row(diag, dict(flags=F | PL_F16), -2)
+    row(diag, PL_2G_VOXELS, -2)
+    row(diag, dict(PL_2G_VOXELS, tile_ws_bytes=0), -2)
+    row(diag, dict(PL_BELOW_2G, tile_ws_bytes=0), -3)
+    row(diag, dict(flags=PL_SC1_NT), -2)                                            # 4 channels per lane
+    row(diag, dict(flags=PL_SC1_NT, tile_ws_bytes=0), -2)
+    row(diag, dict(C=20), -2)
+    row(diag, dict(C=24, flags=F | (2 << 4)), -2)                                   # 12 channels per workgroup
+    row(diag, dict(flags=PL_CPL8 | 1), -2)
+    row(diag, dict(flags=PL_CPL8), -2)
+    row(diag, dict(flags=F | PL_WG128), -2)
+    row(diag, dict(tile_ws_bytes=55), -3)
+    row(diag, dict(C=128), -2)                                                      # 73 216 bytes of LDS
+    row(diag, dict(C=128, tile_ws_bytes=55), -3)
+    row(diag, dict(C=256, flags=F | PL_BF16), -2)                                   # 75 264 bytes
+    row(diag, dict(C=256, flags=F | PL_BF16 | (2 << 4), tile_ws_bytes=55), -3)
+    # ---- fbbev_lift_splat_fused: its four pointers, the plan, the cache pair, the workspace; then the rank build (another family)
+    lift = 'lift_splat_fused'
+    for k in ('depth', 'context', 'out', 'workspace'):
+        row(lift, {k: NULL}, -1)
+    for k in ('B', 'N', 'D', 'H', 'W', 'C', 'Z', 'Y', 'X'):
+        row(lift, {k: 0}, -1)
+    row(lift, PL_2G_POINTS, -1)
+    row(lift, dict(PL_2G_POINTS, workspace_bytes=0), -1)
+    row(lift, dict(PL_POINTS_BELOW_2G, workspace_bytes=0), -3)
+    row(lift, dict(cam_key=NULL), -1)
+    row(lift, dict(cache_state=NULL), -1)
+    row(lift, dict(cache_state=NULL, workspace_bytes=0), -1)
+    row(lift, dict(workspace_bytes=PL_LIFT_WS - 1), -3)
+    row(lift, dict(workspace_bytes=PL_LIFT_WS - 1, workspace=P8), -3)
+    row(lift, dict(workspace=P8), -2)
+    row(lift, dict(workspace=P8, cam_key=NULL, cache_state=NULL), -2)
+    row(lift, dict(workspace=P8, workspace_bytes=PL_LIFT_WS), -2)
+    # ---- fbbev_pool_zmean / _split / _rows
+    for zm in ('pool_zmean', 'pool_zmean_split', 'pool_zmean_rows'):
+        out = 'out_rows' if zm == 'pool_zmean_rows' else 'out_mean'
+        for k in ('B', 'C', 'Z', 'Y', 'X'):
+            row(zm, {k: 0}, -1)
+        for k in GATHER7 + [out, 'tile_ws']:
+            row(zm, {k: NULL}, -1)
+        row(zm, dict(C=18), -2)
+        row(zm, dict(C=18, depth=NULL), -1)
+        row(zm, dict(C=260), -2)
+        row(zm, dict(Y=1, X=6), -2)
+        row(zm, {out: P8}, -2)
+        row(zm, dict(feat=P8), -2)
+        row(zm, PL_2G_VOXELS, -2)
+        row(zm, dict(PL_2G_VOXELS, tile_ws_bytes=0), -2)
+        row(zm, dict(PL_BELOW_2G, tile_ws_bytes=0), -3)
+        row(zm, dict(flags=F | CL), -2)
+        row(zm, dict(flags=F | CL, tile_ws_bytes=0), -2)
+        row(zm, dict(tile_voxels=512), -2)
+        row(zm, dict(tile_voxels=1024, tile_ws_bytes=0), -2)
+        row(zm, dict(tile_ws_bytes=55), -3)
+        row(zm, dict(tile_ws_bytes=79, tile_voxels=64), -3)
+        row(zm, dict(tile_ws_bytes=79, tile_voxels=16), -3)
+        row(zm, dict(tile_ws_bytes=31, tile_voxels=256), -3)
+        row(zm, dict(C=128), -2)                                                    # 73 216 bytes of LDS: the bound is 64 KiB
+        row(zm, dict(C=64, tile_voxels=256), -2)
+        row(zm, dict(C=128, tile_ws_bytes=55), -3)
+    split = 'pool_zmean_split'
+    row(split, dict(z_groups=0), -1)
+    row(split, dict(z_groups=65), -1)
+    row(split, dict(z_groups=65, C=18), -1)
+    row(split, dict(z_groups=2, partial_ws=NULL), -1)
+    row(split, dict(z_groups=2, partial_ws=P8), -1)
+    row(split, dict(z_groups=2, partial_ws=P8, C=18), -1)
+    row(split, dict(z_groups=2, partial_ws_bytes=2 * 16 * 144 * 4 - 1), -3)
+    row(split, dict(z_groups=64, partial_ws_bytes=3 * 16 * 144 * 4 - 1), -3)        # more groups than planes: Z of them
+    row(split, dict(z_groups=2, partial_ws_bytes=0, C=128), -2)                     # LDS before the partial buffer
+    row(split, dict(z_groups=2, partial_ws_bytes=0, tile_ws_bytes=55), -3)
+    row(split, dict(B=1 << 25, Z=8, Y=2, X=2, C=32, tile_voxels=64, flags=F | (8 << 4), z_groups=8, partial_ws_bytes=1 << 62), -2)   # 2^31 workgroups
+    row(split, dict(B=1 << 25, Z=8, Y=2, X=2, C=32, tile_voxels=64, flags=F | (8 << 4), z_groups=8, partial_ws_bytes=0), -3)
+    zrows = 'pool_zmean_rows'
+    row(zrows, dict(row_bias=P8), -2)
+    row(zrows, dict(row_bias=P8, depth=NULL), -2)                                   # the bias comes before the pointers
+    row(zrows, dict(row_bias=P8, B=0), -1)
+    row(zrows, dict(row_bias=NULL, tile_ws_bytes=55), -3)
+    # ---- fbbev_bev_pool_v2_dense_bwd[_z]
+    for bwd in ('bev_pool_v2_dense_bwd', 'bev_pool_v2_dense_bwd_z'):
+        for k in ('B', 'N', 'D', 'H', 'W', 'C', 'Z', 'Y', 'X'):
+            row(bwd, {k: 0}, -1)
+        row(bwd, dict(n_intervals_max=-1), -1)
+        for k in ('out_grad', 'depth', 'feat', 'ranks_depth', 'interval_rank', 'interval_starts', 'counts', 'depth_grad', 'feat_grad',
+                  'workspace'):
+            row(bwd, {k: NULL}, -1)
+        row(bwd, dict(C=18), -2)
+        row(bwd, dict(C=18, counts=NULL), -1)
+        row(bwd, dict(C=260), -2)
+        row(bwd, dict(Y=1, X=6), -2)
+        for k in ('out_grad', 'feat', 'feat_grad', 'workspace'):
+            row(bwd, {k: P8}, -2)
+        row(bwd, PL_2G_VOXELS, -2)
+        row(bwd, PL_2G_POINTS, -2)
+        row(bwd, dict(PL_2G_VOXELS, og_stride_c=4), -2)
+        row(bwd, dict(PL_BELOW_2G, og_stride_c=4), -1)
+        row(bwd, dict(PL_2G_POINTS, og_stride_c=4), -2)
+        row(bwd, dict(PL_POINTS_BELOW_2G, og_stride_c=4), -1)
+        row(bwd, dict(PL_BELOW_2G, workspace_bytes=0), -3)
+        row(bwd, dict(PL_POINTS_BELOW_2G, workspace_bytes=0), -3)
+        row(bwd, dict(og_stride_c=428), -1)
+        row(bwd, dict(og_stride_c=434), -1)
+        row(bwd, dict(og_stride_b=16 * 432 - 4), -1)
+        row(bwd, dict(og_stride_b=16 * 432 + 2), -1)
+        row(bwd, dict(og_stride_c=436, og_stride_b=16 * 436 - 4), -1)
+        row(bwd, dict(og_stride_c=428, workspace_bytes=0), -1)
+        row(bwd, dict(workspace_bytes=PL_BWD_WS - 1), -3)
+    bwdz = 'bev_pool_v2_dense_bwd_z'
+    row(bwdz, dict(zgrad=NULL), -1)
+    row(bwdz, dict(zgrad=NULL, C=18), -1)
+    row(bwdz, dict(zgrad=P8), -2)
+    row(bwdz, dict(zgrad=P8, B=0), -2)                                              # its alignment comes before the dimensions
+    row(bwdz, dict(zgrad=P8, depth=NULL), -2)
+    shown = lambda case: {k: (v.value if isinstance(v, ctypes.c_void_p) else v) for k, v in case.items()}   # noqa: E731
+    got = [(entry, shown(case), pl_call(lib, entry, case)) for entry, case, _ in table]
+    want = [(entry, shown(case), code) for entry, case, code in table]
+    assert got == want, [(g, w[2]) for g, w in zip(got, want) if g != w]
+    assert {entry for entry, _, _ in table} == set(PL_PARAMS)
+    # ---- the host functions, as values: the shipped grid (100 x 100 x 8) and BASELINE configs[2] (6 cameras of 16 x 44 pixels and
+    # 59 depth bins, 80 channels, 200 x 200 x 16), the 12 x 12 x 3 grid, non-positive sizes, 2^31 points
+    tile, bwd_ws, lift_ws = lib.fbbev_pool_dense_workspace_bytes, lib.fbbev_pool_dense_bwd_workspace_bytes, lib.fbbev_lift_splat_fused_ws_bytes
+    assert [tile(*a) for a in ((1, 8, 100, 100), (4, 16, 200, 200), (1, 3, 12, 12), (2, 3, 12, 12), (0, 3, 12, 12), (1, -1, 12, 12),
+                               (1, 3, 0, 12), (1, 3, 12, 0))] == PL_TILE_BYTES
+    shapes = ((1, 6, 59, 16, 44, 80, 8, 100, 100), (4, 6, 59, 16, 44, 80, 16, 200, 200), (1, 1, 2, 2, 4, 16, 3, 12, 12),
+              (2, 1, 2, 2, 4, 16, 3, 12, 12), (1, 2048, 1024, 1024, 1, 16, 3, 12, 12), (1, 2048, 1023, 1024, 1, 16, 3, 12, 12))
+    zeros = [tuple(0 if i == k else v for i, v in enumerate(shapes[2])) for k in range(9)]
+    assert [bwd_ws(*a) for a in shapes + tuple(zeros)] == PL_BWD_BYTES
+    assert [lift_ws(*a) for a in shapes + tuple(zeros)] == PL_LIFT_BYTES
+    off = (ctypes.c_size_t * 8)()
+    got = []
+    for a in shapes + (zeros[0], zeros[5]):
+        got.append([lib.fbbev_lift_splat_fused_ws_offsets(*a, ctypes.cast(off, ctypes.c_void_p))] + list(off))
+        for i in range(8):
+            off[i] = 0
+    assert got == PL_LIFT_OFFSETS
+    assert lib.fbbev_lift_splat_fused_ws_offsets(*shapes[2], NULL) == -1
+    assert (bwd_ws(*shapes[2]), lift_ws(*shapes[2])) == (PL_BWD_WS, PL_LIFT_WS)
+
+
+PL_TILE_BYTES = [80128, 2560768, 512, 1024, 256, 256, 256, 256]
+PL_BWD_BYTES = [26601984, 323144448, 1536, 2560, 8589962496, 8581573888, 256, 256, 256, 256, 256, 256, 256, 256, 256]
+PL_LIFT_BYTES = [13680128, 47504128, 1189120, 1321216, 0, 78447119616, 0, 0, 0, 0, 0, 0, 0, 0, 0]
+PL_LIFT_OFFSETS = [[0, 0, 996864, 1993728, 2990592, 3987456, 4984320, 5981184, 5981440],
+                   [0, 0, 3987456, 7974912, 11962368, 15949824, 19937280, 23924736, 23924992],
+                   [0, 0, 256, 512, 768, 1024, 1280, 1536, 1792], [0, 0, 256, 512, 768, 1024, 1280, 1536, 1792], [-1, 0, 0, 0, 0, 0, 0, 0, 0],
+                   [0, 0, 8581545984, 17163091968, 25744637952, 34326183936, 42907729920, 51489275904, 51489276160],
+                   [-1, 0, 0, 0, 0, 0, 0, 0, 0], [-1, 0, 0, 0, 0, 0, 0, 0, 0]]
