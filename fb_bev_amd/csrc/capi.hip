@@ -3498,34 +3498,64 @@ extern "C" int fbbev_rows_linear_x3_fragments(const float* weight, int in_featur
     return 0;
 }
 
-// What the split-bf16 (x3) and the exact-fp32 (f32) entries have in common: the checks of the addend and of the LayerNorm tail's
-// operands, which the entries make before anything else is looked at, ...
-static int rows_linear_addend_check(const float* addend, long long* addend_row_stride, long long addend_period, int in_features) {
-    if (!addend || addend_period <= 0) return FBBEV_E_BADARG;
-    return row_operand(addend, addend_row_stride, in_features);
-}
-static int rows_linear_ln_check(const float* residual, long long* residual_row_stride, const float* ln_weight, const float* ln_bias,
-                                int out_features) {
-    if (!ln_weight || !ln_bias || out_features <= 0) return FBBEV_E_BADARG;
-    if (out_features > 128) return FBBEV_E_UNSUPPORTED;
-    if (residual) { if (const int e = row_operand(residual, residual_row_stride, out_features)) return e; }
-    if (!aligned16(ln_weight) || !aligned16(ln_bias)) return FBBEV_E_UNSUPPORTED;
+// One row-GEMM call: out = epilogue((x [+ addend]) W^T + bias).  The nine fbbev_rows_linear_x3* / _f32* entries fill it -- the head
+// every entry has in the order of their own operands, each optional operand BY NAME -- and every helper down to the launch takes it;
+// an optional operand that is absent has a null pointer (the head planes: no tokens).
+struct rows_ref { const float* p; long long stride; };             // rows `stride` floats apart (0: dense, see row_operand)
+struct rows_gemm {
+    rows_ref x;
+    const void* weights; const float* bias;                        // weights: the fragment buffer (x3) or the weight matrix (out, in) (f32)
+    float* out; long long out_stride;
+    long long rows; int in_features, out_features, relu;
+    fbbev_rt_stream stream;
+    // (an entry names what follows; what it does not name is absent)
+    struct { const float* p; long long stride, period; } addend;   // added to x: row r takes addend row r % period (none: period 1)
+    rows_ref residual;                                             // added to the product (LayerNorm tail, training epilogue)
+    struct { const float *weight, *bias; float eps; } ln;          // LayerNorm over a row of the outputs
+    rows_ref mask;                                                 // training epilogue: the product is kept where mask > 0
+    struct { int tokens_per_image, head_dim, elem_type; } planes;  // out as head planes (images, heads, tokens, head_dim) of FBBEV_ELEM_*
+    bool train_epilogue;
+};
+// The head-plane epilogue takes the head width and the element type of the planes as ONE int, head_dim | elem_type << 16, and
+// divides an output's index by head_dim through a 32-bit reciprocal, exact below 2^16: head_dim and out_features at most
+// 0xffff, which also keeps the width clear of the type.  rows_planes_check is the only way into this family with planes set.
+static inline int rows_plane_word(const rows_gemm& c) { return c.planes.head_dim | (c.planes.elem_type << 16); }
+static int rows_planes_check(const rows_gemm& c) {
+    const int head_dim = c.planes.head_dim, et = c.planes.elem_type;
+    if (c.planes.tokens_per_image <= 0 || head_dim <= 0 || c.out_features <= 0 || et < 0 || et > 2) return FBBEV_E_BADARG;
+    if (head_dim % 2 != 0 || c.out_features % head_dim != 0 || c.rows % c.planes.tokens_per_image != 0 || head_dim > 0xffff ||
+        c.out_features > 0xffff) return FBBEV_E_UNSUPPORTED;
     return 0;
 }
-// ... and the checks of x / weights / bias / out with the launch geometry.  `weights`: the fragment buffer (x3) or the weight matrix
-// (f32).  A nonzero result, or rows == 0, ends the call.
+
+// What the split-bf16 (x3) and the exact-fp32 (f32) entries have in common: the checks of the addend and of the LayerNorm tail's
+// operands, which the entries make before anything else is looked at, ...
+static int rows_linear_addend_check(rows_gemm* c) {
+    if (!c->addend.p || c->addend.period <= 0) return FBBEV_E_BADARG;
+    return row_operand(c->addend.p, &c->addend.stride, c->in_features);
+}
+static int rows_linear_ln_check(rows_gemm* c) {
+    if (!c->ln.weight || !c->ln.bias || c->out_features <= 0) return FBBEV_E_BADARG;
+    if (c->out_features > 128) return FBBEV_E_UNSUPPORTED;
+    if (c->residual.p) { if (const int e = row_operand(c->residual.p, &c->residual.stride, c->out_features)) return e; }
+    if (!aligned16(c->ln.weight) || !aligned16(c->ln.bias)) return FBBEV_E_UNSUPPORTED;
+    return 0;
+}
+// ... and the checks of x / weights / bias / out with the launch geometry.  A nonzero result, or rows == 0, ends the call.
 struct rows_linear_geom { int n_oc, n_kc, nmt; long long tiles, RT, groups; };
-static int rows_linear_prepare(const float* x, long long* x_row_stride, const void* weights, const float* bias, long long rows,
-                               int in_features, int out_features, const float* out, long long* out_row_stride, rows_linear_geom* g) {
-    if (rows < 0 || in_features <= 0 || out_features <= 0) return FBBEV_E_BADARG;
-    if (rows == 0) return 0;
-    if (!x || !weights || !out) return FBBEV_E_BADARG;
-    if (const int e = row_worse(row_operand(x, x_row_stride, in_features), row_operand(out, out_row_stride, out_features))) return e;
-    if (in_features % 8 != 0 || out_features % 4 != 0 || !aligned16(weights) || (bias && !aligned16(bias))) return FBBEV_E_UNSUPPORTED;
-    g->n_oc = (out_features + 127) / 128; g->n_kc = (in_features + 127) / 128;
-    g->tiles = (rows + 127) / 128;
+static int rows_linear_prepare(rows_gemm* c, rows_linear_geom* g) {
+    if (!c->addend.p) c->addend.period = 1;
+    if (c->rows < 0 || c->in_features <= 0 || c->out_features <= 0) return FBBEV_E_BADARG;
+    if (c->rows == 0) return 0;
+    if (!c->x.p || !c->weights || !c->out) return FBBEV_E_BADARG;
+    if (const int e = row_worse(row_operand(c->x.p, &c->x.stride, c->in_features), row_operand(c->out, &c->out_stride, c->out_features)))
+        return e;
+    if (c->in_features % 8 != 0 || c->out_features % 4 != 0 || !aligned16(c->weights) || (c->bias && !aligned16(c->bias)))
+        return FBBEV_E_UNSUPPORTED;
+    g->n_oc = (c->out_features + 127) / 128; g->n_kc = (c->in_features + 127) / 128;
+    g->tiles = (c->rows + 127) / 128;
     if (g->tiles * g->n_oc >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    g->nmt = out_features >= 128 ? 8 : (out_features + 15) / 16;
+    g->nmt = c->out_features >= 128 ? 8 : (c->out_features + 15) / 16;
     // consecutive row tiles per workgroup (fragments / the weight staged once) as long as ~4 workgroups per CU remain; the chain of
     // an f32 element does not depend on it
     g->RT = g->n_kc == 1 ? g->tiles * g->n_oc / 1024 : 1;
@@ -3536,102 +3566,94 @@ static int rows_linear_prepare(const float* x, long long* x_row_stride, const vo
     return 0;
 }
 
+// Which kernel takes a split-bf16 call.  Round 6: the persistent form (k_rows_linear_x3p: fragments staged once per workgroup, the
+// next tile's rows in flight under the MFMAs, fragment reads under the MFMAs of the tile before) for one K chunk, no addend, no
+// LayerNorm tail.  Same bits.  FBBEV_ROWS_LINEAR_P=0: off (A/B knob).  FBBEV_ROWS_LINEAR_NT=1: 16 rows per wave on the plain route.
+enum rows_x3_route { ROWS_X3_PERSISTENT, ROWS_X3_TRAIN, ROWS_X3_LN, ROWS_X3_NT1, ROWS_X3_PLAIN };
 static bool rows_linear_nt1() { static const bool v = fbbev_env_int("FBBEV_ROWS_LINEAR_NT", 0) == 1; return v; }   // tuning knob, read once
-static int rows_linear_x3_impl(const float* x, long long x_row_stride, const void* fragments, const float* bias, long long rows,
-                               int in_features, int out_features, int relu, float* out, long long out_row_stride,
-                               const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
-                               int plane_S = 0, int plane_TS = 0, const float* res = nullptr, long long ld_res = 0,
-                               const float* ln_w = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
-                               const float* mask = nullptr, long long ld_mask = 0, bool train_epi = false);
+static rows_x3_route rows_x3_route_of(const rows_gemm& c, const rows_linear_geom& g) {
+    FBBEV_KNOB_ONCE(bool, persist, fbbev_env_int("FBBEV_ROWS_LINEAR_P", 1) != 0);
+    // (the training epilogue at 8 output tiles x 4 k-steps -- 96 < I <= 128 and O > 80: no layer of the model -- would spill: old kernel)
+    if (persist && g.n_kc == 1 && !c.ln.weight && !c.addend.p && !(rows_linear_nt1() && !c.train_epilogue) &&
+        !(c.train_epilogue && c.out_features > 80 && c.in_features > 96)) return ROWS_X3_PERSISTENT;
+    if (c.train_epilogue) return ROWS_X3_TRAIN;
+    if (c.ln.weight) return ROWS_X3_LN;
+    return rows_linear_nt1() && g.n_kc == 1 ? ROWS_X3_NT1 : ROWS_X3_PLAIN;
+}
+// The kernel arguments every split-bf16 kernel starts with, and what k_rows_linear_x3 takes behind its geometry
+#define FBBEV_ROWS_X3_HEAD(c) \
+    c.x.p, c.x.stride, static_cast<const unsigned short*>(c.weights), c.bias, c.out, c.out_stride, c.rows, c.in_features, c.out_features, c.relu
+#define FBBEV_ROWS_X3_TAIL(c)                                                                                                          \
+    c.addend.p, c.addend.stride, c.addend.period, c.planes.tokens_per_image, rows_plane_word(c), c.residual.p, c.residual.stride, c.ln.weight, \
+        c.ln.bias, c.ln.eps, c.mask.p, c.mask.stride
+// The persistent kernel's ladders: NMTP output tiles x KSP k-steps; with the training epilogue all but <8, 4> (see the route)
+#define FBBEV_ROWS_KSP(ksp, ...) FBBEV_POOL_WITH(KSP, ksp, 3, 4, __VA_ARGS__)
+#define FBBEV_ROWS_TILES(nmtp, ksp, ...) FBBEV_POOL_WITH(NMTP, nmtp, 5, 8, FBBEV_ROWS_KSP(ksp, __VA_ARGS__))
+#define FBBEV_ROWS_TILES_TRAIN(nmtp, ksp, ...) \
+    do { if ((nmtp) == 5) { constexpr int NMTP = 5; FBBEV_ROWS_KSP(ksp, __VA_ARGS__); } else { constexpr int NMTP = 8, KSP = 3; __VA_ARGS__; } } while (0)
+
+static int rows_linear_x3_dispatch(rows_gemm c) {
+    rows_linear_geom g;
+    int e = rows_linear_prepare(&c, &g);
+    if (e || c.rows == 0) return e;
+    const int n_oc = g.n_oc;
+    const size_t lds = (size_t)g.nmt * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short);
+    // (kept ahead of the dispatch although most calls launch k_rows_linear_x3p: as the first use of these two kernels in the file it
+    // also fixes their place in the code object, and device code is compared byte for byte across host-only changes)
+    e = c.ln.weight ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, false>, lds);
+    if (e) return e;
+#define FBBEV_ROWS_X3(KERNEL, grid, rt) \
+    FBBEV_LAUNCH_DYN_LDS(KERNEL, (grid) * n_oc, 256, lds, c.stream, FBBEV_ROWS_X3_HEAD(c), g.n_kc, n_oc, (int)(rt), FBBEV_ROWS_X3_TAIL(c))
+    const rows_x3_route route = rows_x3_route_of(c, g);
+    if (route == ROWS_X3_PERSISTENT) {
+        const int nmtp = c.out_features <= 80 ? 5 : 8, ksp = c.in_features <= 96 ? 3 : 4;
+        long long n_slots = 512 / n_oc;
+        const int slots_emu = FBBEV_KNOB_EMU_INT("FBBEV_ROWS_LINEAR_SLOTS", 0);   // lets a small case walk several row tiles per workgroup
+        if (slots_emu >= 1) n_slots = slots_emu;
+        if (n_slots < 1) n_slots = 1;
+        if (n_slots > g.tiles) n_slots = g.tiles;
+        const size_t ldsp = (size_t)nmtp * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short) + (size_t)16 * nmtp * sizeof(float);
+#define FBBEV_ROWS_X3P(EPI_)                                                                                                       \
+    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3p<NMTP, KSP, EPI_>), n_slots * n_oc, 256, ldsp, c.stream, FBBEV_ROWS_X3_HEAD(c), n_oc,    \
+                         (int)n_slots, c.planes.tokens_per_image, rows_plane_word(c), c.residual.p, c.residual.stride, c.mask.p, \
+                         c.mask.stride)
+        if (c.train_epilogue) FBBEV_ROWS_TILES_TRAIN(nmtp, ksp, FBBEV_ROWS_X3P(1));
+        else FBBEV_ROWS_TILES(nmtp, ksp, FBBEV_ROWS_X3P(0));
+#undef FBBEV_ROWS_X3P
+    } else if (route == ROWS_X3_TRAIN) {
+        FBBEV_ROWS_X3((k_rows_linear_x3<2, false, 1>), g.groups, g.RT);
+    } else if (route == ROWS_X3_LN) {
+        if (n_oc != 1) return FBBEV_E_UNSUPPORTED;
+        FBBEV_ROWS_X3((k_rows_linear_x3<2, true>), g.groups, g.RT);
+    } else if (route == ROWS_X3_NT1) {
+        // 16 rows per wave (64 per workgroup): half the accumulators / row pieces in registers -> more waves per SIMD
+        const long long tiles1 = (c.rows + 63) / 64;
+        long long RT1 = tiles1 * n_oc / 2048;
+        RT1 = RT1 < 1 ? 1 : (RT1 > 8 ? 8 : RT1);
+        FBBEV_ROWS_X3((k_rows_linear_x3<1, false>), (tiles1 + RT1 - 1) / RT1, RT1);
+    } else {
+        FBBEV_ROWS_X3((k_rows_linear_x3<2, false>), g.groups, g.RT);
+    }
+#undef FBBEV_ROWS_X3
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int fbbev_rows_linear_x3(const float* x, long long x_row_stride, const void* fragments, const float* bias, long long rows,
                                     int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                     fbbev_stream_t stream_) {
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, relu, out, out_row_stride, nullptr,
-                               0, 1, stream_);
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, out, out_row_stride, rows, in_features, out_features, relu, (fbbev_rt_stream)stream_};
+    return rows_linear_x3_dispatch(c);
 }
 
 extern "C" int fbbev_rows_linear_x3_add(const float* x, long long x_row_stride, const float* addend, long long addend_row_stride,
                                         long long addend_period, const void* fragments, const float* bias, long long rows,
                                         int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                         fbbev_stream_t stream_) {
-    if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
-                               addend_row_stride, addend_period, stream_);
-}
-
-static int rows_linear_x3_impl(const float* x, long long x_row_stride, const void* fragments, const float* bias, long long rows,
-                               int in_features, int out_features, int relu, float* out, long long out_row_stride,
-                               const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
-                               int plane_S, int plane_TS, const float* res, long long ld_res, const float* ln_w, const float* ln_b,
-                               float ln_eps, const float* mask, long long ld_mask, bool train_epi) {
-    rows_linear_geom g;
-    int e = rows_linear_prepare(x, &x_row_stride, fragments, bias, rows, in_features, out_features, out, &out_row_stride, &g);
-    if (e || rows == 0) return e;
-    const int n_oc = g.n_oc, n_kc = g.n_kc;
-    const long long tiles = g.tiles, RT = g.RT, groups = g.groups;
-    const size_t lds = (size_t)g.nmt * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short);
-    // (kept ahead of the dispatch although most calls launch k_rows_linear_x3p: as the first use of these two kernels in the file it
-    // also fixes their place in the code object, and device code is compared byte for byte across host-only changes)
-    e = ln_w ? fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, true>, lds) : fbbev_rt_allow_dyn_lds((const void*)k_rows_linear_x3<2, false>, lds);
-    if (e) return e;
-    // round 6: the persistent form (k_rows_linear_x3p: fragments staged once per workgroup, the next tile's rows in flight under the
-    // MFMAs, fragment reads under the MFMAs of the tile before) for one K chunk, no addend, no LayerNorm tail.  Same bits.
-    // FBBEV_ROWS_LINEAR_P=0: off (A/B knob)
-    FBBEV_KNOB_ONCE(bool, persist, fbbev_env_int("FBBEV_ROWS_LINEAR_P", 1) != 0);
-    // (the training epilogue at 8 output tiles x 4 k-steps -- 96 < I <= 128 and O > 80: no layer of the model -- would spill: old kernel)
-    if (persist && n_kc == 1 && !ln_w && !addend && !(rows_linear_nt1() && !train_epi) &&
-        !(train_epi && out_features > 80 && in_features > 96)) {
-        const int nmtp = out_features <= 80 ? 5 : 8, ksp = in_features <= 96 ? 3 : 4;
-        long long n_slots = 512 / n_oc;
-        const int slots_emu = FBBEV_KNOB_EMU_INT("FBBEV_ROWS_LINEAR_SLOTS", 0);   // lets a small case walk several row tiles per workgroup
-        if (slots_emu >= 1) n_slots = slots_emu;
-        if (n_slots < 1) n_slots = 1;
-        if (n_slots > tiles) n_slots = tiles;
-        const size_t ldsp = (size_t)nmtp * FBBEV_RL_TILE_ELEMS * sizeof(unsigned short) + (size_t)16 * nmtp * sizeof(float);
-#define FBBEV_RLP(NMT_, KS_, EPI_)                                                                                                        \
-    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3p<NMT_, KS_, EPI_>), n_slots * n_oc, 256, ldsp, (fbbev_rt_stream)stream_, x, x_row_stride,      \
-                         static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu, \
-                         n_oc, (int)n_slots, plane_S, plane_TS, res, ld_res, mask, ld_mask)
-        if (train_epi) {
-            if (nmtp == 5) { if (ksp == 3) FBBEV_RLP(5, 3, 1); else FBBEV_RLP(5, 4, 1); }
-            else FBBEV_RLP(8, 3, 1);
-        } else {
-            if (nmtp == 5) { if (ksp == 3) FBBEV_RLP(5, 3, 0); else FBBEV_RLP(5, 4, 0); }
-            else { if (ksp == 3) FBBEV_RLP(8, 3, 0); else FBBEV_RLP(8, 4, 0); }
-        }
-#undef FBBEV_RLP
-        FBBEV_CHECK_LAUNCH();
-        return 0;
-    }
-    if (train_epi) {
-        FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3<2, false, 1>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                             static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                             n_kc, n_oc, (int)RT, addend, addend_row_stride, addend_period, 0, 0, res, ld_res, (const float*)nullptr,
-                             (const float*)nullptr, 0.f, mask, ld_mask);
-    } else if (ln_w) {
-        if (n_oc != 1) return FBBEV_E_UNSUPPORTED;
-        FBBEV_LAUNCH((k_rows_linear_x3<2, true>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                     static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                     n_kc, n_oc, (int)RT, addend, addend_row_stride, addend_period, plane_S, plane_TS, res, ld_res, ln_w, ln_b, ln_eps,
-                     (const float*)nullptr, 0ll);
-    } else if (rows_linear_nt1() && n_kc == 1) {
-        // 16 rows per wave (64 per workgroup): half the accumulators / row pieces in registers -> more waves per SIMD
-        const long long tiles1 = (rows + 63) / 64;
-        long long RT1 = tiles1 * n_oc / 2048;
-        RT1 = RT1 < 1 ? 1 : (RT1 > 8 ? 8 : RT1);
-        FBBEV_LAUNCH_DYN_LDS((k_rows_linear_x3<1, false>), (tiles1 + RT1 - 1) / RT1 * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                             static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                             n_kc, n_oc, (int)RT1, addend, addend_row_stride, addend_period, plane_S, plane_TS, res, ld_res, ln_w, ln_b, ln_eps,
-                             (const float*)nullptr, 0ll);
-    } else {
-        FBBEV_LAUNCH((k_rows_linear_x3<2, false>), groups * n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,
-                     static_cast<const unsigned short*>(fragments), bias, out, out_row_stride, rows, in_features, out_features, relu,
-                     n_kc, n_oc, (int)RT, addend, addend_row_stride, addend_period, plane_S, plane_TS, res, ld_res, ln_w, ln_b, ln_eps,
-                     (const float*)nullptr, 0ll);
-    }
-    FBBEV_CHECK_LAUNCH();
-    return 0;
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, out, out_row_stride, rows, in_features, out_features, relu, (fbbev_rt_stream)stream_};
+    c.addend = {addend, addend_row_stride, addend_period};
+    if (const int e = rows_linear_addend_check(&c)) return e;
+    return rows_linear_x3_dispatch(c);
 }
 
 // training epilogue (round 6): out = ((x W^T + b) [ReLU]) * [mask > 0] + residual -- the forward recomputations and dgrads of the
@@ -3641,17 +3663,14 @@ extern "C" int fbbev_rows_linear_x3_train(const float* x, long long x_row_stride
                                           int in_features, int out_features, int relu, const float* residual, long long residual_row_stride,
                                           const float* mask, long long mask_row_stride, float* out, long long out_row_stride,
                                           fbbev_stream_t stream_) {
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, out, out_row_stride, rows, in_features, out_features, relu, (fbbev_rt_stream)stream_};
+    c.addend = {addend, addend_row_stride, addend_period}; c.residual = {residual, residual_row_stride}; c.mask = {mask, mask_row_stride};
+    c.train_epilogue = true;
     if (out_features <= 0 || in_features <= 0) return FBBEV_E_BADARG;
-    if (addend) {
-        if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
-    } else {
-        addend_period = 1;
-    }
-    if (residual) { if (const int e = row_operand(residual, &residual_row_stride, out_features)) return e; }
-    if (mask) { if (const int e = row_operand(mask, &mask_row_stride, out_features)) return e; }
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
-                               addend_row_stride, addend_period, stream_, 0, 0, residual, residual_row_stride, nullptr, nullptr, 0.f,
-                               mask, mask_row_stride, true);
+    if (addend) { if (const int e = rows_linear_addend_check(&c)) return e; }   // (none: its period is not looked at and becomes 1)
+    if (residual) { if (const int e = row_operand(residual, &c.residual.stride, out_features)) return e; }
+    if (mask) { if (const int e = row_operand(mask, &c.mask.stride, out_features)) return e; }
+    return rows_linear_x3_dispatch(c);
 }
 
 // out = LayerNorm(x W^T + b [+ residual]) over the out_features outputs of a row, weight / bias / eps of torch.nn.LayerNorm: the
@@ -3662,29 +3681,26 @@ extern "C" int fbbev_rows_linear_x3_ln(const float* x, long long x_row_stride, c
                                        int in_features, int out_features, const float* residual, long long residual_row_stride,
                                        const float* ln_weight, const float* ln_bias, float ln_eps, float* out,
                                        long long out_row_stride, fbbev_stream_t stream_) {
-    if (const int e = rows_linear_ln_check(residual, &residual_row_stride, ln_weight, ln_bias, out_features)) return e;
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
-                               stream_, 0, 0, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, out, out_row_stride, rows, in_features, out_features, 0, (fbbev_rt_stream)stream_};
+    c.residual = {residual, residual_row_stride}; c.ln = {ln_weight, ln_bias, ln_eps};
+    if (const int e = rows_linear_ln_check(&c)) return e;
+    return rows_linear_x3_dispatch(c);
 }
 
 // ------------------------------------------------------------------------------ row-wise linear layers, exact fp32 (FP32 MFMA)
 // fbbev_rows_linear_f32*: every output element is one fp32 fmaf chain in the order of fbbev_rows_linear_f32_k_order (the arithmetic
 // contract in include/fbbev.h).  The weight is the nn.Linear parameter itself (row-major (out_features, in_features) fp32).
-static int rows_linear_f32_impl(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
-                                int in_features, int out_features, int relu, float* out, long long out_row_stride,
-                                const float* addend, long long addend_row_stride, long long addend_period, fbbev_stream_t stream_,
-                                const float* res = nullptr, long long ld_res = 0, const float* ln_w = nullptr,
-                                const float* ln_b = nullptr, float ln_eps = 0.f) {
+static int rows_linear_f32_dispatch(rows_gemm c) {
     rows_linear_geom g;
-    const int e = rows_linear_prepare(x, &x_row_stride, weight, bias, rows, in_features, out_features, out, &out_row_stride, &g);
-    if (e || rows == 0) return e;
-    if (ln_w && g.n_oc != 1) return FBBEV_E_UNSUPPORTED;
+    const int e = rows_linear_prepare(&c, &g);
+    if (e || c.rows == 0) return e;
+    if (c.ln.weight && g.n_oc != 1) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)g.nmt * FBBEV_RLF_TILE_FLOATS * sizeof(float);
-#define FBBEV_RLF(LN_)                                                                                                                   \
-    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_f32<LN_>), g.groups * g.n_oc, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride, weight, bias, \
-                         out, out_row_stride, rows, in_features, out_features, relu, g.n_kc, g.n_oc, (int)g.RT, addend,                  \
-                         addend_row_stride, addend_period, res, ld_res, ln_w, ln_b, ln_eps)
-    if (ln_w) FBBEV_RLF(true); else FBBEV_RLF(false);
+#define FBBEV_RLF(LN_)                                                                                                            \
+    FBBEV_LAUNCH_DYN_LDS((k_rows_linear_f32<LN_>), g.groups * g.n_oc, 256, lds, c.stream, c.x.p, c.x.stride, static_cast<const float*>(c.weights), \
+                         c.bias, c.out, c.out_stride, c.rows, c.in_features, c.out_features, c.relu, g.n_kc, g.n_oc, (int)g.RT, c.addend.p, \
+                         c.addend.stride, c.addend.period, c.residual.p, c.residual.stride, c.ln.weight, c.ln.bias, c.ln.eps)
+    if (c.ln.weight) FBBEV_RLF(true); else FBBEV_RLF(false);
 #undef FBBEV_RLF
     FBBEV_CHECK_LAUNCH();
     return 0;
@@ -3693,26 +3709,28 @@ static int rows_linear_f32_impl(const float* x, long long x_row_stride, const fl
 extern "C" int fbbev_rows_linear_f32(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
                                      int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                      fbbev_stream_t stream_) {
-    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, relu, out, out_row_stride, nullptr,
-                                0, 1, stream_);
+    rows_gemm c = {{x, x_row_stride}, weight, bias, out, out_row_stride, rows, in_features, out_features, relu, (fbbev_rt_stream)stream_};
+    return rows_linear_f32_dispatch(c);
 }
 
 extern "C" int fbbev_rows_linear_f32_add(const float* x, long long x_row_stride, const float* addend, long long addend_row_stride,
                                          long long addend_period, const float* weight, const float* bias, long long rows,
                                          int in_features, int out_features, int relu, float* out, long long out_row_stride,
                                          fbbev_stream_t stream_) {
-    if (const int e = rows_linear_addend_check(addend, &addend_row_stride, addend_period, in_features)) return e;
-    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, relu, out, out_row_stride, addend,
-                                addend_row_stride, addend_period, stream_);
+    rows_gemm c = {{x, x_row_stride}, weight, bias, out, out_row_stride, rows, in_features, out_features, relu, (fbbev_rt_stream)stream_};
+    c.addend = {addend, addend_row_stride, addend_period};
+    if (const int e = rows_linear_addend_check(&c)) return e;
+    return rows_linear_f32_dispatch(c);
 }
 
 extern "C" int fbbev_rows_linear_f32_ln(const float* x, long long x_row_stride, const float* weight, const float* bias, long long rows,
                                         int in_features, int out_features, const float* residual, long long residual_row_stride,
                                         const float* ln_weight, const float* ln_bias, float ln_eps, float* out,
                                         long long out_row_stride, fbbev_stream_t stream_) {
-    if (const int e = rows_linear_ln_check(residual, &residual_row_stride, ln_weight, ln_bias, out_features)) return e;
-    return rows_linear_f32_impl(x, x_row_stride, weight, bias, rows, in_features, out_features, 0, out, out_row_stride, nullptr, 0, 1,
-                                stream_, residual, residual_row_stride, ln_weight, ln_bias, ln_eps);
+    rows_gemm c = {{x, x_row_stride}, weight, bias, out, out_row_stride, rows, in_features, out_features, 0, (fbbev_rt_stream)stream_};
+    c.residual = {residual, residual_row_stride}; c.ln = {ln_weight, ln_bias, ln_eps};
+    if (const int e = rows_linear_ln_check(&c)) return e;
+    return rows_linear_f32_dispatch(c);
 }
 
 extern "C" int fbbev_rows_linear_f32_k_order(int in_features, int* order) {
@@ -3726,14 +3744,11 @@ extern "C" int fbbev_rows_linear_f32_k_order(int in_features, int* order) {
 extern "C" int fbbev_rows_linear_x3_planes(const float* x, long long x_row_stride, const void* fragments, const float* bias,
                                            long long rows, int in_features, int out_features, int tokens_per_image, int head_dim,
                                            float* out, fbbev_stream_t stream_) {
-    if (tokens_per_image <= 0 || head_dim <= 0 || out_features <= 0) return FBBEV_E_BADARG;
-    // (the head-plane epilogue divides by head_dim through a 32-bit reciprocal, exact for outputs < 2^16, and packs the element
-    // type above bit 16 of its head-width argument)
-    if (head_dim % 2 != 0 || out_features % head_dim != 0 || rows % tokens_per_image != 0 || head_dim > 0xffff || out_features > 0xffff)
-        return FBBEV_E_UNSUPPORTED;
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, out, 0, rows, in_features, out_features, 0, (fbbev_rt_stream)stream_};
+    c.planes = {tokens_per_image, head_dim, FBBEV_ELEM_F32};
+    if (const int e = rows_planes_check(c)) return e;
     if (out && ((uintptr_t)out & 7) != 0) return FBBEV_E_UNSUPPORTED;
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, 0, out, 0, nullptr, 0, 1, stream_,
-                               tokens_per_image, head_dim);
+    return rows_linear_x3_dispatch(c);
 }
 
 // The same projection with the planes STORED in 16 bits (elem_type 1 bf16, 2 fp16; 0 = fbbev_rows_linear_x3_planes): the fp32 result
@@ -3741,13 +3756,23 @@ extern "C" int fbbev_rows_linear_x3_planes(const float* x, long long x_row_strid
 extern "C" int fbbev_rows_linear_x3_planes_e(const float* x, long long x_row_stride, const void* fragments, const float* bias,
                                              long long rows, int in_features, int out_features, int tokens_per_image, int head_dim,
                                              int elem_type, void* out, fbbev_stream_t stream_) {
-    if (tokens_per_image <= 0 || head_dim <= 0 || out_features <= 0 || elem_type < 0 || elem_type > 2) return FBBEV_E_BADARG;
-    if (head_dim % 2 != 0 || out_features % head_dim != 0 || rows % tokens_per_image != 0 || head_dim > 0xffff || out_features > 0xffff)
-        return FBBEV_E_UNSUPPORTED;
+    rows_gemm c = {{x, x_row_stride}, fragments, bias, static_cast<float*>(out), 0, rows, in_features, out_features, 0, (fbbev_rt_stream)stream_};
+    c.planes = {tokens_per_image, head_dim, elem_type};
+    if (const int e = rows_planes_check(c)) return e;
     if (out && ((uintptr_t)out & (elem_type ? 3 : 7)) != 0) return FBBEV_E_UNSUPPORTED;
     if (out && !aligned16(out)) return FBBEV_E_UNSUPPORTED;
-    return rows_linear_x3_impl(x, x_row_stride, fragments, bias, rows, in_features, out_features, 0, static_cast<float*>(out), 0, nullptr, 0,
-                               1, stream_, tokens_per_image, head_dim | (elem_type << 16));
+    return rows_linear_x3_dispatch(c);
+}
+
+// The FFN entries' row operands, checked side by side -- x (rows of in_features), out and the optional residual (rows of
+// out_features) -- and their workgroups of 128 rows
+struct rows_ffn_io { rows_ref x; float* out; long long out_stride; rows_ref residual; long long rows, wgs; };
+static int rows_ffn_prepare(rows_ffn_io* io, int in_features, int out_features) {
+    int e = row_worse(row_operand(io->x.p, &io->x.stride, in_features), row_operand(io->out, &io->out_stride, out_features));
+    if (io->residual.p) e = row_worse(e, row_operand(io->residual.p, &io->residual.stride, out_features));
+    if (e) return e;
+    io->wgs = (io->rows + 127) / 128;
+    return io->wgs >= (1ll << 31) ? FBBEV_E_UNSUPPORTED : 0;
 }
 
 // The FFN pair of the encoder layer in one kernel: out = [LayerNorm](W2 relu(W1 x + b1) + b2 [+ residual]) -- mmcv FFN
@@ -3761,23 +3786,20 @@ extern "C" int fbbev_rows_ffn_x3(const float* x, long long x_row_stride, const v
     if (rows < 0 || in_features <= 0 || hidden <= 0 || out_features <= 0) return FBBEV_E_BADARG;
     if (rows == 0) return 0;
     if (!x || !w1_fragments || !b1 || !w2_fragments || !b2 || !out || (ln_weight && !ln_bias)) return FBBEV_E_BADARG;
-    int e = row_worse(row_operand(x, &x_row_stride, in_features), row_operand(out, &out_row_stride, out_features));
-    if (residual) e = row_worse(e, row_operand(residual, &residual_row_stride, out_features));
-    if (e) return e;
+    rows_ffn_io io = {{x, x_row_stride}, out, out_row_stride, {residual, residual_row_stride}, rows, 0};
+    if (const int e = rows_ffn_prepare(&io, in_features, out_features)) return e;
     if (in_features > 96 || in_features % 8 != 0 || hidden % FBBEV_FFN_HC != 0 || out_features > 80 || out_features % 4 != 0 ||
         !aligned16(w1_fragments) || !aligned16(w2_fragments) || !aligned16(b1) || !aligned16(b2) ||
         (ln_weight && (!aligned16(ln_weight) || !aligned16(ln_bias)))) return FBBEV_E_UNSUPPORTED;
-    const long long wgs = (rows + 127) / 128;
-    if (wgs >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     // hidden units per chunk: 32 (three workgroups per CU) measured 1.480 vs 1.508 ms for 64 in the S3 scope (profiles/r04_time_fb_ffn_hc.jsonl)
     FBBEV_KNOB_ONCE(int, hc, fbbev_env_int("FBBEV_FFN_HC", 32));   // tuning knob (the emulator tests switch the chunk)
     const int n_kc2 = (hidden + 127) / 128;
 #define FBBEV_FFN(LN_, HC_)                                                                                                              \
     do {                                                                                                                                 \
         const size_t lds = (size_t)fbbev_ffn_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                     \
-        FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, LN_, HC_>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,                  \
+        FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, LN_, HC_>), io.wgs, 256, lds, (fbbev_rt_stream)stream_, x, io.x.stride,                \
                              static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2, \
-                             out, out_row_stride, rows, in_features, hidden, out_features, n_kc2, residual, residual_row_stride,         \
+                             out, io.out_stride, rows, in_features, hidden, out_features, n_kc2, residual, io.residual.stride,           \
                              ln_weight, ln_bias, ln_eps, fbbev_ffn_pre{});                                                               \
     } while (0)
     if (hc == 64) { if (ln_weight) FBBEV_FFN(true, 64); else FBBEV_FFN(false, 64); }
@@ -3791,44 +3813,39 @@ extern "C" int fbbev_rows_ffn_x3(const float* x, long long x_row_stride, const v
 //   y1  = LayerNorm0(x W0^T + b0 + residual0)                 output_proj + residual + norm   (bevformer_encoder.py:250-377, ops 'cross_attn', 'norm')
 //   out = LayerNorm1(y1 + W2 relu(W1 y1 + b1) + b2)           mmcv FFN (add_identity) + norm  (ops 'ffn', 'norm')
 // x (rows, E) = the attention slots, residual0 (rows, E) = the block's input rows.  Supported: E in {16, 32, 48, 64, 80}, hidden % 64 == 0.
-static int rows_tail_ffn_x3_impl(const float* x, long long x_row_stride, const void* w0_fragments, const float* b0,
-                                 const float* residual0, long long residual0_row_stride, const float* ln0_weight,
-                                 const float* ln0_bias, float ln0_eps, const void* w1_fragments, const float* b1,
-                                 const void* w2_fragments, const float* b2, long long rows, int embed, int hidden,
-                                 const float* ln1_weight, const float* ln1_bias, float ln1_eps, float* out,
-                                 long long out_row_stride, long long tokens_per_image, fbbev_stream_t stream_) {
-    if (rows < 0 || embed <= 0 || hidden <= 0 || tokens_per_image < 0) return FBBEV_E_BADARG;
-    if (rows == 0) return 0;
-    if (tokens_per_image > 0) {                            // planes: out (rows / S, embed, S); the kernel takes S as a negative row stride
-        if (rows % tokens_per_image != 0) return FBBEV_E_BADARG;
-        if (rows >= (1ll << 31) || tokens_per_image >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;      // 32-bit row arithmetic in the store
-        out_row_stride = embed;                            // (passes the checks below)
+// `pre`: the tail's operands as the kernel takes them, filled by the entry.  tokens_per_image > 0: out as planes (rows / S, embed, S).
+struct rows_tail_ffn {
+    rows_ref x; fbbev_ffn_pre pre;
+    const void *w1_fragments, *w2_fragments; const float *b1, *b2;
+    long long rows; int embed, hidden;
+    const float *ln1_weight, *ln1_bias; float ln1_eps;
+    float* out; long long out_stride, tokens_per_image; fbbev_rt_stream stream;
+};
+static int rows_tail_ffn_x3_launch(rows_tail_ffn c) {
+    const int embed = c.embed, hidden = c.hidden;
+    if (c.rows < 0 || embed <= 0 || hidden <= 0 || c.tokens_per_image < 0) return FBBEV_E_BADARG;
+    if (c.rows == 0) return 0;
+    rows_ffn_io io = {c.x, c.out, c.out_stride, {c.pre.res0, c.pre.ld_res0}, c.rows, 0};
+    if (c.tokens_per_image > 0) {
+        if (c.rows % c.tokens_per_image != 0) return FBBEV_E_BADARG;
+        if (c.rows >= (1ll << 31) || c.tokens_per_image >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;   // 32-bit row arithmetic in the store
+        io.out_stride = embed;                                 // (the planes have no row stride: dense rows pass the checks below)
     }
-    if (!x || !w0_fragments || !b0 || !ln0_weight || !ln0_bias || !w1_fragments || !b1 || !w2_fragments || !b2 || !ln1_weight ||
-        !ln1_bias || !out) return FBBEV_E_BADARG;
-    int e = row_worse(row_operand(x, &x_row_stride, embed), row_operand(out, &out_row_stride, embed));
-    if (residual0) e = row_worse(e, row_operand(residual0, &residual0_row_stride, embed));
-    if (e) return e;
-    if (embed > 80 || embed % 16 != 0 || hidden % FBBEV_FFN_HC != 0 || !aligned16(w0_fragments) || !aligned16(w1_fragments) ||
-        !aligned16(w2_fragments) || !aligned16(b0) || !aligned16(b1) || !aligned16(b2) || !aligned16(ln0_weight) || !aligned16(ln0_bias) ||
-        !aligned16(ln1_weight) || !aligned16(ln1_bias)) return FBBEV_E_UNSUPPORTED;
-    const long long wgs = (rows + 127) / 128;
-    if (wgs >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    if (!c.x.p || !c.pre.w0f || !c.pre.b0 || !c.pre.ln0_w || !c.pre.ln0_b || !c.w1_fragments || !c.b1 || !c.w2_fragments || !c.b2 ||
+        !c.ln1_weight || !c.ln1_bias || !c.out) return FBBEV_E_BADARG;
+    if (const int e = rows_ffn_prepare(&io, embed, embed)) return e;
+    if (embed > 80 || embed % 16 != 0 || hidden % FBBEV_FFN_HC != 0 || !aligned16(c.pre.w0f) || !aligned16(c.w1_fragments) ||
+        !aligned16(c.w2_fragments) || !aligned16(c.pre.b0) || !aligned16(c.b1) || !aligned16(c.b2) || !aligned16(c.pre.ln0_w) ||
+        !aligned16(c.pre.ln0_b) || !aligned16(c.ln1_weight) || !aligned16(c.ln1_bias)) return FBBEV_E_UNSUPPORTED;
     const int n_kc2 = (hidden + 127) / 128;
-    fbbev_ffn_pre pre;
-    pre.w0f = static_cast<const unsigned short*>(w0_fragments); pre.b0 = b0; pre.res0 = residual0; pre.ld_res0 = residual0_row_stride;
-    pre.ln0_w = ln0_weight; pre.ln0_b = ln0_bias; pre.eps0 = ln0_eps;
-#define FBBEV_TFFN(HC_)                                                                                                                  \
-    do {                                                                                                                                 \
-        const size_t lds = (size_t)fbbev_ffn_pre_lds_bytes<3, 5, HC_>() + (size_t)hidden * 4; /* + b1 */                                 \
-        FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, true, HC_, true>), wgs, 256, lds, (fbbev_rt_stream)stream_, x, x_row_stride,           \
-                             static_cast<const unsigned short*>(w1_fragments), b1, static_cast<const unsigned short*>(w2_fragments), b2, \
-                             out, ldo, rows, embed, hidden, embed, n_kc2, (const float*)nullptr, (long long)0, ln1_weight,               \
-                             ln1_bias, ln1_eps, pre);                                                                                    \
-    } while (0)
-    const long long ldo = tokens_per_image > 0 ? -tokens_per_image : out_row_stride;
-    FBBEV_TFFN(32);      // (hidden chunks of 64 -- FBBEV_TAIL_FFN_HC=64 until round 5 -- measured no gain: 1.392 vs 1.392 ms S3; gone)
-#undef FBBEV_TFFN
+    c.pre.ld_res0 = io.residual.stride;
+    const long long ldo = c.tokens_per_image > 0 ? -c.tokens_per_image : io.out_stride;   // the kernel takes planes as a NEGATIVE row stride: -S
+    // (hidden chunks of 64 -- FBBEV_TAIL_FFN_HC=64 until round 5 -- measured no gain: 1.392 vs 1.392 ms S3; gone)
+    const size_t lds = (size_t)fbbev_ffn_pre_lds_bytes<3, 5, 32>() + (size_t)hidden * 4; /* + b1 */
+    FBBEV_LAUNCH_DYN_LDS((k_rows_ffn_x3<3, 5, true, 32, true>), io.wgs, 256, lds, c.stream, c.x.p, io.x.stride,
+                         static_cast<const unsigned short*>(c.w1_fragments), c.b1, static_cast<const unsigned short*>(c.w2_fragments), c.b2,
+                         c.out, ldo, c.rows, embed, hidden, embed, n_kc2, (const float*)nullptr, (long long)0, c.ln1_weight, c.ln1_bias,
+                         c.ln1_eps, c.pre);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -3839,9 +3856,9 @@ extern "C" int fbbev_rows_tail_ffn_x3(const float* x, long long x_row_stride, co
                                       const void* w2_fragments, const float* b2, long long rows, int embed, int hidden,
                                       const float* ln1_weight, const float* ln1_bias, float ln1_eps, float* out,
                                       long long out_row_stride, fbbev_stream_t stream_) {
-    return rows_tail_ffn_x3_impl(x, x_row_stride, w0_fragments, b0, residual0, residual0_row_stride, ln0_weight, ln0_bias, ln0_eps,
-                                 w1_fragments, b1, w2_fragments, b2, rows, embed, hidden, ln1_weight, ln1_bias, ln1_eps, out,
-                                 out_row_stride, 0, stream_);
+    const fbbev_ffn_pre pre = {static_cast<const unsigned short*>(w0_fragments), b0, residual0, residual0_row_stride, ln0_weight, ln0_bias, ln0_eps};
+    return rows_tail_ffn_x3_launch({{x, x_row_stride}, pre, w1_fragments, w2_fragments, b1, b2, rows, embed, hidden, ln1_weight, ln1_bias,
+                                    ln1_eps, out, out_row_stride, 0, (fbbev_rt_stream)stream_});
 }
 
 // The same with the result written as planes: out (rows / tokens_per_image, embed, tokens_per_image) -- the (B, C, Y, X) refined BEV
@@ -3853,128 +3870,137 @@ extern "C" int fbbev_rows_tail_ffn_x3_planes(const float* x, long long x_row_str
                                              const float* ln1_weight, const float* ln1_bias, float ln1_eps,
                                              long long tokens_per_image, float* out, fbbev_stream_t stream_) {
     if (tokens_per_image <= 0) return FBBEV_E_BADARG;
-    return rows_tail_ffn_x3_impl(x, x_row_stride, w0_fragments, b0, residual0, residual0_row_stride, ln0_weight, ln0_bias, ln0_eps,
-                                 w1_fragments, b1, w2_fragments, b2, rows, embed, hidden, ln1_weight, ln1_bias, ln1_eps, out, 0,
-                                 tokens_per_image, stream_);
+    const fbbev_ffn_pre pre = {static_cast<const unsigned short*>(w0_fragments), b0, residual0, residual0_row_stride, ln0_weight, ln0_bias, ln0_eps};
+    return rows_tail_ffn_x3_launch({{x, x_row_stride}, pre, w1_fragments, w2_fragments, b1, b2, rows, embed, hidden, ln1_weight, ln1_bias,
+                                    ln1_eps, out, 0, tokens_per_image, (fbbev_rt_stream)stream_});
 }
 
-static int conv3d_launch(const float* x, const float* weight_fragments, const float* bias, const float* residual, int B,
-                         int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int ksize, int stride, int pad,
-                         int relu, int mode, float* out, fbbev_stream_t stream_, bool planar = false) {
-    if (B == 0) return 0;
-    if (!x || !weight_fragments || !bias || !out) return FBBEV_E_BADARG;
-    if (Cin % 16 != 0 || !aligned16(x) || !aligned16(weight_fragments) || !aligned16(bias) || !aligned16(out) ||
-        (residual && !aligned16(residual))) return FBBEV_E_UNSUPPORTED;
-    const long long nvox = (long long)B * Do * Ho * Wo;
-    const long long gx = (nvox + 255) / 256;
-    const int mt_total = (Cout + 15) / 16;
-    const int MT = mt_total % 4 == 0 ? 4 : (mt_total % 2 == 0 ? 2 : 1);
-    const long long pstride = (long long)(Cin / 16) * mt_total * 256;
-    const int gy = mt_total / MT;
-    const long long grid = gx * gy * (mode == 1 ? 8 : 1);
-    if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-#define FBBEV_CONV3D(KD_, KS_, MT_)                                                                                      \
-    FBBEV_LAUNCH((k_conv3d_ndhwc<KD_, KS_, MT_>), grid, 256, 0, (fbbev_rt_stream)stream_, x, weight_fragments, bias,  \
-                 residual, out, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, mt_total, stride, pad, relu ? 1 : 0, mode, pstride, \
-                 (int)gx, gy)
-#define FBBEV_CONV3D_K(KD_, KS_) do { if (MT == 4) FBBEV_CONV3D(KD_, KS_, 4); else if (MT == 2) FBBEV_CONV3D(KD_, KS_, 2); else FBBEV_CONV3D(KD_, KS_, 1); } while (0)
-    if (ksize == 3 && planar) FBBEV_CONV3D_K(1, 3); else if (ksize == 3) FBBEV_CONV3D_K(3, 3); else if (ksize == 2) FBBEV_CONV3D_K(2, 2);
-    else FBBEV_CONV3D_K(1, 1);
-#undef FBBEV_CONV3D_K
+// ------------------------------------------------------------------------------ convolutions, channels-last (NDHWC)
+// The shape of a convolution call: B samples, the input and the output volume.  An image is a volume of one plane.
+struct conv_volume { int D, H, W, C; };
+struct conv_window {
+    int ksize, stride, pad;
+    // stride 1 / 2, padding 0 / 1, kernel size 1 / 3 -- and 2 where `with_k2`: the fp32 3-D kernels have it, the bf16 and 2-D routes do not
+    bool supported(bool with_k2) const { return (ksize == 1 || ksize == 3 || (with_k2 && ksize == 2)) && (stride == 1 || stride == 2) && pad >= 0 && pad <= 1; }
+};
+struct conv_dims {
+    int B; conv_volume in, out;
+    bool positive() const { return B >= 0 && in.D > 0 && in.H > 0 && in.W > 0 && in.C > 0 && out.D > 0 && out.H > 0 && out.W > 0 && out.C > 0; }
+    static bool axis_ok(int in, int out, conv_window w) { return out == (in + 2 * w.pad - w.ksize) / w.stride + 1; }
+    bool geometry_ok_planar(conv_window w) const { return axis_ok(in.H, out.H, w) && axis_ok(in.W, out.W, w); }   // the depth axis is the caller's
+    bool geometry_ok(conv_window w) const { return axis_ok(in.D, out.D, w) && geometry_ok_planar(w); }
+    bool same_volume() const { return out.D == in.D && out.H == in.H && out.W == in.W; }   // (the transposed route: 2x2x2 outputs per voxel)
+    long long out_voxels() const { return (long long)B * out.D * out.H * out.W; }
+    conv_dims swapped() const { return conv_dims{B, out, in}; }
+};
+// How the MFMA kernels tile a launch: mt_total 16-channel output tiles, MT of them per workgroup (4, 2 or 1: what divides mt_total),
+// gy = mt_total / MT workgroups per block of output; `gx` blocks (256 voxels, or one LDS tile), `per_block` workgroup groups for each
+// (8: the parities of the transposed route); pstride: weight fragment elements per tap (`cin_granule` input channels per fragment)
+struct conv_tile_plan { int mt_total, MT, gy; long long gx, grid, pstride; };
+static conv_tile_plan conv_tile_plan_of(const conv_dims& d, int cin_granule, long long gx, int per_block) {
+    const int mt_total = (d.out.C + 15) / 16, MT = mt_total % 4 == 0 ? 4 : (mt_total % 2 == 0 ? 2 : 1), gy = mt_total / MT;
+    return conv_tile_plan{mt_total, MT, gy, gx, gx * gy * per_block, (long long)(d.in.C / cin_granule) * mt_total * (16 * cin_granule)};
+}
+#define FBBEV_CONV_MT(mt, ...) FBBEV_POOL_WITH3(MT, mt, 4, 2, 1, __VA_ARGS__)
+
+// One forward-kernel call (the dgrad is one too: the gather form over dy).  mode: 0 convolution, 1 transposed 2x2x2, 2 dgrad
+struct conv_call {
+    const float* x; const void* weights; const float *bias, *residual; float* out;
+    conv_dims d; conv_window w;
+    int relu, mode; bool planar, bf16;
+    fbbev_rt_stream stream;
+};
+// what every forward entry asks of its operands once the shape is accepted and B > 0
+static int conv_operands_check(const conv_call& c, int cin_granule) {
+    if (!c.x || !c.weights || !c.bias || !c.out) return FBBEV_E_BADARG;
+    if (c.d.in.C % cin_granule != 0 || !aligned16(c.x) || !aligned16(c.weights) || !aligned16(c.bias) || !aligned16(c.out) ||
+        (c.residual && !aligned16(c.residual))) return FBBEV_E_UNSUPPORTED;
+    return 0;
+}
+#define FBBEV_CONV_DIMS(d) (d).B, (d).in.D, (d).in.H, (d).in.W, (d).in.C, (d).out.D, (d).out.H, (d).out.W, (d).out.C   /* as the kernels take them */
+
+// What the entries ask of a shape before anything else: positive dimensions (BADARG); the transposed route (mode 1) wants the same
+// volume in and out, has no planar form and sets its own window; otherwise the window must be one the kernels have (UNSUPPORTED)
+// and the geometry hold (BADARG) -- planar: one plane in, one plane out stands in for the depth axis's
+static int conv_shape_check(const conv_dims& d, conv_window* w, int mode, bool planar, bool with_k2) {
+    if (!d.positive()) return FBBEV_E_BADARG;
+    if (mode == 1) {
+        if (!d.same_volume() || planar) return FBBEV_E_BADARG;
+        *w = {1, 1, 0};
+        return 0;
+    }
+    if (!w->supported(with_k2)) return FBBEV_E_UNSUPPORTED;
+    return (planar ? d.in.D == 1 && d.out.D == 1 && d.geometry_ok_planar(*w) : d.geometry_ok(*w)) ? 0 : FBBEV_E_BADARG;
+}
+
+// the per-voxel kernels, fp32 (16 input channels per weight fragment) and bf16 (32), over blocks of 256 output voxels
+static int conv3d_launch(const conv_call& c) {
+    if (c.d.B == 0) return 0;
+    const int cin_granule = c.bf16 ? 32 : 16;
+    if (const int e = conv_operands_check(c, cin_granule)) return e;
+    const conv_tile_plan p = conv_tile_plan_of(c.d, cin_granule, (c.d.out_voxels() + 255) / 256, c.mode == 1 ? 8 : 1);
+    if (p.grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+#define FBBEV_CONV3D(KERNEL, WT, KD_, KS_)                                                                                        \
+    FBBEV_CONV_MT(p.MT, FBBEV_LAUNCH((KERNEL<KD_, KS_, MT>), p.grid, 256, 0, c.stream, c.x, static_cast<const WT*>(c.weights), c.bias, \
+                                     c.residual, c.out, FBBEV_CONV_DIMS(c.d), p.mt_total, c.w.stride, c.w.pad, c.relu ? 1 : 0, c.mode,   \
+                                     p.pstride, (int)p.gx, p.gy))
+    const int k = c.w.ksize;
+    if (!c.bf16) {
+        if (k == 3 && c.planar) FBBEV_CONV3D(k_conv3d_ndhwc, float, 1, 3); else if (k == 3) FBBEV_CONV3D(k_conv3d_ndhwc, float, 3, 3);
+        else if (k == 2) FBBEV_CONV3D(k_conv3d_ndhwc, float, 2, 2); else FBBEV_CONV3D(k_conv3d_ndhwc, float, 1, 1);
+    } else {
+        if (k == 3 && c.planar) FBBEV_CONV3D(k_conv3d_ndhwc_bf16, unsigned short, 1, 3); else if (k == 3) FBBEV_CONV3D(k_conv3d_ndhwc_bf16, unsigned short, 3, 3);
+        else FBBEV_CONV3D(k_conv3d_ndhwc_bf16, unsigned short, 1, 1);
+    }
 #undef FBBEV_CONV3D
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
 
-static bool conv3d_geometry_ok(int in, int out, int ksize, int stride, int pad) { return out == (in + 2 * pad - ksize) / stride + 1; }
-
 extern "C" int fbbev_conv3d_ndhwc(const float* x, const float* weight_fragments, const float* bias, const float* residual,
                                   int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout, int ksize,
                                   int stride, int pad, int relu, int transposed, float* out, fbbev_stream_t stream_) {
-    if (B < 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
-    if (transposed) {
-        if (Do != Di || Ho != Hi || Wo != Wi) return FBBEV_E_BADARG;
-        ksize = 1; stride = 1; pad = 0;
-    } else {
-        if (ksize < 1 || ksize > 3 || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
-        if (!conv3d_geometry_ok(Di, Do, ksize, stride, pad) || !conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) ||
-            !conv3d_geometry_ok(Wi, Wo, ksize, stride, pad)) return FBBEV_E_BADARG;
-    }
-    return conv3d_launch(x, weight_fragments, bias, residual, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, relu,
-                         transposed ? 1 : 0, out, stream_);
+    conv_call c = {x, weight_fragments, bias, residual, out, {B, {Di, Hi, Wi, Cin}, {Do, Ho, Wo, Cout}}, {ksize, stride, pad}, relu,
+                   transposed ? 1 : 0, false, false, (fbbev_rt_stream)stream_};
+    if (const int e = conv_shape_check(c.d, &c.w, c.mode, c.planar, true)) return e;
+    return conv3d_launch(c);
 }
 
 extern "C" int fbbev_conv2d_nhwc(const float* x, const float* weight_fragments, const float* bias, const float* residual,
                                  int B, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int ksize, int stride, int pad,
                                  int relu, float* out, fbbev_stream_t stream_) {
-    if (B < 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
-    if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
-    if (!conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) || !conv3d_geometry_ok(Wi, Wo, ksize, stride, pad)) return FBBEV_E_BADARG;
     // an NHWC image is an NDHWC volume with one plane; the planar instantiation has a single tap along that axis
-    return conv3d_launch(x, weight_fragments, bias, residual, B, 1, Hi, Wi, Cin, 1, Ho, Wo, Cout, ksize, stride, pad, relu, 0, out,
-                         stream_, true);
+    conv_call c = {x, weight_fragments, bias, residual, out, {B, {1, Hi, Wi, Cin}, {1, Ho, Wo, Cout}}, {ksize, stride, pad}, relu, 0, true,
+                   false, (fbbev_rt_stream)stream_};
+    if (const int e = conv_shape_check(c.d, &c.w, c.mode, c.planar, false)) return e;
+    return conv3d_launch(c);
 }
 
 extern "C" int fbbev_conv3d_ndhwc_bf16(const float* x, const void* weight_fragments_bf16, const float* bias,
                                        const float* residual, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo,
                                        int Cout, int ksize, int stride, int pad, int relu, int transposed, int planar,
                                        float* out, fbbev_stream_t stream_) {
-    if (B < 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
-    if (transposed) {
-        if (Do != Di || Ho != Hi || Wo != Wi || planar) return FBBEV_E_BADARG;
-        ksize = 1; stride = 1; pad = 0;
-    } else {
-        if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
-        if (planar ? (Di != 1 || Do != 1) : !conv3d_geometry_ok(Di, Do, ksize, stride, pad)) return FBBEV_E_BADARG;
-        if (!conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) || !conv3d_geometry_ok(Wi, Wo, ksize, stride, pad)) return FBBEV_E_BADARG;
-    }
-    if (B == 0) return 0;
-    if (!x || !weight_fragments_bf16 || !bias || !out) return FBBEV_E_BADARG;
-    if (Cin % 32 != 0 || !aligned16(x) || !aligned16(weight_fragments_bf16) || !aligned16(bias) || !aligned16(out) ||
-        (residual && !aligned16(residual))) return FBBEV_E_UNSUPPORTED;
-    const long long nvox = (long long)B * Do * Ho * Wo;
-    const long long gx = (nvox + 255) / 256;
-    const int mt_total = (Cout + 15) / 16;
-    const int MT = mt_total % 4 == 0 ? 4 : (mt_total % 2 == 0 ? 2 : 1);
-    const long long pstride = (long long)(Cin / 32) * mt_total * 512;
-    const int gy = mt_total / MT;
-    const long long grid = gx * gy * (transposed ? 8 : 1);
-    if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    const unsigned short* wfb = static_cast<const unsigned short*>(weight_fragments_bf16);
-#define FBBEV_CONV3DB(KD_, KS_, MT_)                                                                                 \
-    FBBEV_LAUNCH((k_conv3d_ndhwc_bf16<KD_, KS_, MT_>), grid, 256, 0, (fbbev_rt_stream)stream_, x, wfb, bias, residual, out, \
-                 B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, mt_total, stride, pad, relu ? 1 : 0, transposed ? 1 : 0, pstride,  \
-                 (int)gx, gy)
-#define FBBEV_CONV3DB_K(KD_, KS_) do { if (MT == 4) FBBEV_CONV3DB(KD_, KS_, 4); else if (MT == 2) FBBEV_CONV3DB(KD_, KS_, 2); else FBBEV_CONV3DB(KD_, KS_, 1); } while (0)
-    if (ksize == 3 && planar) FBBEV_CONV3DB_K(1, 3); else if (ksize == 3) FBBEV_CONV3DB_K(3, 3); else FBBEV_CONV3DB_K(1, 1);
-#undef FBBEV_CONV3DB_K
-#undef FBBEV_CONV3DB
-    FBBEV_CHECK_LAUNCH();
-    return 0;
+    conv_call c = {x, weight_fragments_bf16, bias, residual, out, {B, {Di, Hi, Wi, Cin}, {Do, Ho, Wo, Cout}}, {ksize, stride, pad}, relu,
+                   transposed ? 1 : 0, planar != 0, true, (fbbev_rt_stream)stream_};
+    if (const int e = conv_shape_check(c.d, &c.w, c.mode, c.planar, false)) return e;
+    return conv3d_launch(c);
 }
 
 extern "C" int fbbev_conv3d_k3s1_tiled_bf16(const float* x, const void* weight_fragments_bf16, const float* bias,
                                             const float* residual, int B, int D, int H, int W, int Cin, int Cout, int relu,
                                             float* out, fbbev_stream_t stream_) {
-    if (B < 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return FBBEV_E_BADARG;
+    const conv_call c = {x, weight_fragments_bf16, bias, residual, out, {B, {D, H, W, Cin}, {D, H, W, Cout}}};
+    if (!c.d.positive()) return FBBEV_E_BADARG;
     if (B == 0) return 0;
-    if (!x || !weight_fragments_bf16 || !bias || !out) return FBBEV_E_BADARG;
-    if (Cin % 32 != 0 || !aligned16(x) || !aligned16(weight_fragments_bf16) || !aligned16(bias) || !aligned16(out) ||
-        (residual && !aligned16(residual))) return FBBEV_E_UNSUPPORTED;
+    if (const int e = conv_operands_check(c, 32)) return e;
     const int tiles_d = (D + 3) / 4, tiles_h = (H + 7) / 8, tiles_w = (W + 7) / 8;
-    const int mt_total = (Cout + 15) / 16;
-    const int MT = mt_total % 4 == 0 ? 4 : (mt_total % 2 == 0 ? 2 : 1);
-    const int gy = mt_total / MT;
     const long long n_tiles = (long long)B * tiles_d * tiles_h * tiles_w;
-    const long long grid = (n_tiles + 7) / 8 * 8 * gy;          // whole groups of 8 tiles (one per XCD), see the kernel
-    if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    const conv_tile_plan p = conv_tile_plan_of(c.d, 32, (n_tiles + 7) / 8 * 8, 1);   // whole groups of 8 tiles (one per XCD), see the kernel
+    if (p.grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
     const size_t lds = (size_t)2 * 600 * 32 * sizeof(unsigned short);
-    const unsigned short* wfb = static_cast<const unsigned short*>(weight_fragments_bf16);
-#define FBBEV_CONV3DT(MT_)                                                                                                       \
-    FBBEV_LAUNCH_DYN_LDS((k_conv3d_k3_tile_bf16<MT_>), grid, 512, lds, (fbbev_rt_stream)stream_, x, wfb, bias, residual, out, B, \
-                         D, H, W, Cin, Cout, mt_total, relu ? 1 : 0, tiles_d, tiles_h, tiles_w, gy)
-    if (MT == 4) FBBEV_CONV3DT(4); else if (MT == 2) FBBEV_CONV3DT(2); else FBBEV_CONV3DT(1);
-#undef FBBEV_CONV3DT
+    FBBEV_CONV_MT(p.MT, FBBEV_LAUNCH_DYN_LDS((k_conv3d_k3_tile_bf16<MT>), p.grid, 512, lds, (fbbev_rt_stream)stream_, x,
+                                             static_cast<const unsigned short*>(weight_fragments_bf16), bias, residual, out, B, D, H, W,
+                                             Cin, Cout, p.mt_total, relu ? 1 : 0, tiles_d, tiles_h, tiles_w, p.gy));
     FBBEV_CHECK_LAUNCH();
     return 0;
 }
@@ -3982,13 +4008,12 @@ extern "C" int fbbev_conv3d_k3s1_tiled_bf16(const float* x, const void* weight_f
 extern "C" int fbbev_conv3d_dgrad_ndhwc(const float* dy, const float* weight_fragments_t, const float* zero_bias, int B,
                                         int Do, int Ho, int Wo, int Cout, int Di, int Hi, int Wi, int Cin, int ksize,
                                         int stride, int pad, float* dx, fbbev_stream_t stream_) {
-    if (B < 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
-    if (ksize < 1 || ksize > 3 || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
-    if (!conv3d_geometry_ok(Di, Do, ksize, stride, pad) || !conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) ||
-        !conv3d_geometry_ok(Wi, Wo, ksize, stride, pad)) return FBBEV_E_BADARG;
+    conv_call c = {dy, weight_fragments_t, zero_bias, nullptr, dx, {B, {Di, Hi, Wi, Cin}, {Do, Ho, Wo, Cout}}, {ksize, stride, pad}, 0, 2,
+                   false, false, (fbbev_rt_stream)stream_};           // (the forward's shape, for the checks)
+    if (const int e = conv_shape_check(c.d, &c.w, c.mode, c.planar, true)) return e;
     // gather form: the kernel's "input" is dy (Cout channels), its "output" voxels are those of dx (Cin channels)
-    return conv3d_launch(dy, weight_fragments_t, zero_bias, nullptr, B, Do, Ho, Wo, Cout, Di, Hi, Wi, Cin, ksize, stride, pad, 0,
-                         2, dx, stream_);
+    c.d = c.d.swapped();
+    return conv3d_launch(c);
 }
 
 // voxel chunk per wave: enough chunks to fill the chip a few times over, at least 256 voxels (16 loop iterations)
@@ -3998,35 +4023,33 @@ static long long conv3d_wgrad_chunk(long long nvox) {
     if (chunk > 4096) chunk = 4096;
     return (chunk + 15) / 16 * 16;
 }
-static int conv3d_wgrad_impl(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho, int Wo, int Cout,
-                             int ksize, int stride, int pad, float* dw, float* part, fbbev_stream_t stream_) {
-    if (B < 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return FBBEV_E_BADARG;
-    if (ksize < 1 || ksize > 3 || (stride != 1 && stride != 2) || pad < 0 || pad > 1) return FBBEV_E_UNSUPPORTED;
-    if (!conv3d_geometry_ok(Di, Do, ksize, stride, pad) || !conv3d_geometry_ok(Hi, Ho, ksize, stride, pad) ||
-        !conv3d_geometry_ok(Wi, Wo, ksize, stride, pad)) return FBBEV_E_BADARG;
-    if (B == 0) return 0;
-    if (!x || !dy || !dw) return FBBEV_E_BADARG;
-    if (Cin % 4 != 0 || Cout % 4 != 0 || !aligned16(x) || !aligned16(dy)) return FBBEV_E_UNSUPPORTED;
-    const long long nvox = (long long)B * Do * Ho * Wo;
-    const int cout_blocks = (Cout + 63) / 64, cin_blocks = (Cin + 63) / 64, T = ksize * ksize * ksize;
+// dw += the weight gradient; `part`: the deterministic route's per-chunk partial sums (then added to dw in chunk order), null: atomics
+struct conv_wgrad_call { const float *x, *dy; float *dw, *part; conv_dims d; conv_window w; fbbev_rt_stream stream; };
+static int conv3d_wgrad_impl(conv_wgrad_call c) {
+    const conv_dims& d = c.d;
+    if (const int e = conv_shape_check(d, &c.w, 0, false, true)) return e;
+    if (d.B == 0) return 0;
+    if (!c.x || !c.dy || !c.dw) return FBBEV_E_BADARG;
+    if (d.in.C % 4 != 0 || d.out.C % 4 != 0 || !aligned16(c.x) || !aligned16(c.dy)) return FBBEV_E_UNSUPPORTED;
+    const long long nvox = d.out_voxels();
+    const int cout_blocks = (d.out.C + 63) / 64, cin_blocks = (d.in.C + 63) / 64, T = c.w.ksize * c.w.ksize * c.w.ksize;
     const long long chunk = conv3d_wgrad_chunk(nvox);
     const long long n_chunks = (nvox + chunk - 1) / chunk;
     const long long tasks = n_chunks * cout_blocks * cin_blocks * T;
     const long long blocks = (tasks + 3) / 4;
     if (blocks >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
-    fbbev_rt_stream stream = (fbbev_rt_stream)stream_;
-#define FBBEV_WGRAD(KS_, DET_, OUT_)                                                                                   \
-    FBBEV_LAUNCH((k_conv3d_wgrad_ndhwc<KS_, DET_>), blocks, 256, 0, stream, x, dy, OUT_, B, Di, Hi, Wi, Cin, Do, Ho, Wo, \
-                 Cout, stride, pad, (int)chunk, (int)n_chunks, cout_blocks, cin_blocks)
-    if (part) {
-        if (ksize == 3) FBBEV_WGRAD(3, true, part); else if (ksize == 2) FBBEV_WGRAD(2, true, part); else FBBEV_WGRAD(1, true, part);
+#define FBBEV_WGRAD(KS_, DET_, OUT_)                                                                                      \
+    FBBEV_LAUNCH((k_conv3d_wgrad_ndhwc<KS_, DET_>), blocks, 256, 0, c.stream, c.x, c.dy, OUT_, FBBEV_CONV_DIMS(d), c.w.stride, \
+                 c.w.pad, (int)chunk, (int)n_chunks, cout_blocks, cin_blocks)
+    if (c.part) {
+        if (c.w.ksize == 3) FBBEV_WGRAD(3, true, c.part); else if (c.w.ksize == 2) FBBEV_WGRAD(2, true, c.part); else FBBEV_WGRAD(1, true, c.part);
         FBBEV_CHECK_LAUNCH();
-        const long long n = (long long)T * Cout * Cin;
+        const long long n = (long long)T * d.out.C * d.in.C;
         long long g = (n + 255) / 256;
         g = g > 4096 ? 4096 : g;
-        FBBEV_LAUNCH(k_sum_chunks_add, g, 256, 0, stream, (const float*)part, (int)n_chunks, n, dw);
+        FBBEV_LAUNCH(k_sum_chunks_add, g, 256, 0, c.stream, (const float*)c.part, (int)n_chunks, n, c.dw);
     } else {
-        if (ksize == 3) FBBEV_WGRAD(3, false, dw); else if (ksize == 2) FBBEV_WGRAD(2, false, dw); else FBBEV_WGRAD(1, false, dw);
+        if (c.w.ksize == 3) FBBEV_WGRAD(3, false, c.dw); else if (c.w.ksize == 2) FBBEV_WGRAD(2, false, c.dw); else FBBEV_WGRAD(1, false, c.dw);
     }
 #undef FBBEV_WGRAD
     FBBEV_CHECK_LAUNCH();
@@ -4036,7 +4059,7 @@ static int conv3d_wgrad_impl(const float* x, const float* dy, int B, int Di, int
 extern "C" int fbbev_conv3d_wgrad_ndhwc(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do,
                                         int Ho, int Wo, int Cout, int ksize, int stride, int pad, float* dw,
                                         fbbev_stream_t stream_) {
-    return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, nullptr, stream_);
+    return conv3d_wgrad_impl({x, dy, dw, nullptr, {B, {Di, Hi, Wi, Cin}, {Do, Ho, Wo, Cout}}, {ksize, stride, pad}, (fbbev_rt_stream)stream_});
 }
 extern "C" size_t fbbev_conv3d_wgrad_ws_bytes(int B, int Do, int Ho, int Wo, int Cin, int Cout, int ksize, int flags) {
     if (!(flags & FBBEV_FLAG_DETERMINISTIC) || B <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || ksize <= 0) return 0;
@@ -4046,12 +4069,13 @@ extern "C" size_t fbbev_conv3d_wgrad_ws_bytes(int B, int Do, int Ho, int Wo, int
 extern "C" int fbbev_conv3d_wgrad_ndhwc_ex(const float* x, const float* dy, int B, int Di, int Hi, int Wi, int Cin, int Do, int Ho,
                                            int Wo, int Cout, int ksize, int stride, int pad, float* dw, int flags, void* ws,
                                            size_t ws_bytes, fbbev_stream_t stream_) {
-    if (!(flags & FBBEV_FLAG_DETERMINISTIC))
-        return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, nullptr, stream_);
+    conv_wgrad_call c = {x, dy, dw, nullptr, {B, {Di, Hi, Wi, Cin}, {Do, Ho, Wo, Cout}}, {ksize, stride, pad}, (fbbev_rt_stream)stream_};
+    if (!(flags & FBBEV_FLAG_DETERMINISTIC)) return conv3d_wgrad_impl(c);
     if (B == 0) return 0;
     if (!ws) return FBBEV_E_BADARG;
     if (ws_bytes < fbbev_conv3d_wgrad_ws_bytes(B, Do, Ho, Wo, Cin, Cout, ksize, flags)) return FBBEV_E_WORKSPACE;
-    return conv3d_wgrad_impl(x, dy, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, ksize, stride, pad, dw, static_cast<float*>(ws), stream_);
+    c.part = static_cast<float*>(ws);
+    return conv3d_wgrad_impl(c);
 }
 
 extern "C" int fbbev_blend_levels_ndhwc(const float* level0, const float* const* coarse, const int* coarse_dims,

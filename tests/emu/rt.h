@@ -9,6 +9,8 @@
 // round-robin on ONE OS thread, so __syncthreads() and the wave64 shuffles are exact rendezvous
 // points and execution is deterministic.  Wave intrinsics must be called wave-uniformly.
 #pragma once
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -18,6 +20,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <string>
 #include <vector>
 
 #define FBBEV_TEST_OVERRIDES 1   /* emulator build: per-call test overrides of launcher plans (capi.hip) */
@@ -171,7 +174,6 @@ inline std::vector<LaunchRecord>& launch_log() { static thread_local std::vector
 // g++ spells the whole instantiation: "... [with auto K = k_pool_fwd_dense2<128, 8, 4, 256, 1, true, 1>]"
 template <auto K> const char* kname() { return __PRETTY_FUNCTION__; }
 }  // namespace emu
-extern "C" __attribute__((used, visibility("default"))) inline void fbbev_emu_launch_log_clear(void) { emu::launch_log().clear(); }
 // the number of launches logged; record i (when there is one) as its kernel's text and {grid, block, lds bytes}
 extern "C" __attribute__((used, visibility("default"))) inline int fbbev_emu_launch_log_read(int i, const char** kernel, long long* grid_block_lds) {
     const std::vector<emu::LaunchRecord>& log = emu::launch_log();
@@ -182,10 +184,46 @@ extern "C" __attribute__((used, visibility("default"))) inline int fbbev_emu_lau
     return (int)log.size();
 }
 
+// The opt-ins to dynamic LDS (fbbev_rt_allow_dyn_lds), a runtime call of their own: the kernel as the dynamic linker names it
+// ("void k_rows_linear_x3<2, true, 0>(float const*, ...)" cut at the parameter list), the bytes asked for, and how many launches this
+// thread had logged before it (tests/test_emu_rows_conv_launch_record.py).  fbbev_emu_launch_log_clear empties both logs.
+namespace emu {
+struct LdsOptIn { std::string kernel; long long bytes, launches_before; };
+inline std::vector<LdsOptIn>& lds_optin_log() { static thread_local std::vector<LdsOptIn> log; return log; }
+inline std::string symbol_of(const void* fn) {
+    Dl_info info;
+    if (!dladdr(fn, &info) || !info.dli_sname) return "?";
+    int status = 0;
+    char* text = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+    std::string name = status == 0 && text ? text : info.dli_sname;
+    free(text);
+    if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
+    const size_t open = name.find('(');
+    return open == std::string::npos ? name : name.substr(0, open);
+}
+}  // namespace emu
+extern "C" __attribute__((used, visibility("default"))) inline void fbbev_emu_launch_log_clear(void) {
+    emu::launch_log().clear();
+    emu::lds_optin_log().clear();
+}
+// on: this thread's launches are logged and NOT run (a launch table asks which kernel on which grid, not what it computes: the
+// kernels' results are other tests' business, and a 3 x 3 x 3 convolution takes seconds here)
+namespace emu { inline bool& log_only() { static thread_local bool on = false; return on; } }
+extern "C" __attribute__((used, visibility("default"))) inline void fbbev_emu_launch_log_only(int on) { emu::log_only() = on != 0; }
+// the number of opt-ins logged; record i (when there is one) as its kernel's text and {bytes, launches logged before it}
+extern "C" __attribute__((used, visibility("default"))) inline int fbbev_emu_lds_optin_log_read(int i, const char** kernel, long long* bytes_before) {
+    const std::vector<emu::LdsOptIn>& log = emu::lds_optin_log();
+    if (i >= 0 && i < (int)log.size()) {
+        *kernel = log[i].kernel.c_str();
+        bytes_before[0] = log[i].bytes; bytes_before[1] = log[i].launches_before;
+    }
+    return (int)log.size();
+}
+
 typedef void* fbbev_rt_stream;
 #define FBBEV_LAUNCH(kern, grid, block, lds_bytes, stream, ...)                                                                    \
     (emu::launch_log().push_back({emu::kname<kern>(), (long long)(unsigned)(grid), (long long)(unsigned)(block), (long long)(lds_bytes)}), \
-     emu::launch((unsigned)(grid), (unsigned)(block), (size_t)(lds_bytes), [=]() { kern(__VA_ARGS__); }))
+     emu::log_only() ? (void)0 : emu::launch((unsigned)(grid), (unsigned)(block), (size_t)(lds_bytes), [=]() { kern(__VA_ARGS__); }))
 static inline int fbbev_rt_last_error() { return 0; }
 typedef int fbbev_rt_event;                                  // launches are synchronous here: streams and events are no-ops
 static inline int fbbev_rt_device() { return 0; }
@@ -193,7 +231,10 @@ static inline int fbbev_rt_stream_create(fbbev_rt_stream* s, int) { *s = nullptr
 static inline int fbbev_rt_event_create(fbbev_rt_event* e) { *e = 0; return 0; }
 static inline int fbbev_rt_event_record(fbbev_rt_event, fbbev_rt_stream) { return 0; }
 static inline int fbbev_rt_stream_wait(fbbev_rt_stream, fbbev_rt_event) { return 0; }
-static inline int fbbev_rt_allow_dyn_lds(const void*, size_t) { return 0; }
+static inline int fbbev_rt_allow_dyn_lds(const void* kern, size_t bytes) {
+    emu::lds_optin_log().push_back({emu::symbol_of(kern), (long long)bytes, (long long)emu::launch_log().size()});
+    return 0;
+}
 static inline int fbbev_rt_memset_async(void* p, int byte, size_t n, fbbev_rt_stream) { memset(p, byte, n); return 0; }
 inline float* fbbev_dyn_lds_f32() {
     uintptr_t p = reinterpret_cast<uintptr_t>(emu::S().lds.data());

@@ -309,7 +309,7 @@ def check_wgrad_real(api, name, case):
 
 # ------------------------------------------------------------------------------------------------------------------ fbbev_rows_linear_x3*
 # (rows, I, O, real, period of the addend (rows % period == 0)).  k_rows_linear_x3p (one K chunk, no addend) gives a workgroup every
-# n_slots-th tile of 128 rows, n_slots = min(512 / n_oc, tiles) (rows_linear_x3_impl in fb_bev_amd/csrc/capi.hip): 65573 rows at two
+# n_slots-th tile of 128 rows, n_slots = min(512 / n_oc, tiles) (rows_linear_x3_dispatch in fb_bev_amd/csrc/capi.hip): 65573 rows at two
 # output chunks are 513 tiles on 256 slots -- slot 0 walks tiles 0, 256 and 512, and tile 512 has 37 rows.
 def _lin(rows, I, O, real, period, env=None):
     return dict(rows=rows, I=I, O=O, real=real, period=period, env=env or {})

@@ -1427,3 +1427,378 @@ PL_LIFT_OFFSETS = [[0, 0, 996864, 1993728, 2990592, 3987456, 4984320, 5981184, 5
                    [0, 0, 256, 512, 768, 1024, 1280, 1536, 1792], [0, 0, 256, 512, 768, 1024, 1280, 1536, 1792], [-1, 0, 0, 0, 0, 0, 0, 0, 0],
                    [0, 0, 8581545984, 17163091968, 25744637952, 34326183936, 42907729920, 51489275904, 51489276160],
                    [-1, 0, 0, 0, 0, 0, 0, 0, 0], [-1, 0, 0, 0, 0, 0, 0, 0, 0]]
+
+
+# ---- the row-wise linear layers (split-bf16 x3, exact f32, head planes, FFN, tail + FFN) and the convolutions (fp32, 2-D, bf16,
+# tiled bf16, dgrad, wgrad): one table, recorded on the launchers before they shared their operand records
+RC_IO = ['x', 'x_row_stride', 'weights', 'bias', 'rows', 'in_features', 'out_features']
+RC_ADD = ['x', 'x_row_stride', 'addend', 'addend_row_stride', 'addend_period', 'weights', 'bias', 'rows', 'in_features', 'out_features', 'relu']
+RC_LN = RC_IO + ['residual', 'residual_row_stride', 'ln_weight', 'ln_bias', 'ln_eps', 'out', 'out_row_stride', 'stream']
+RC_TAIL = ['x', 'x_row_stride', 'w0_fragments', 'b0', 'residual0', 'residual0_row_stride', 'ln0_weight', 'ln0_bias', 'ln0_eps',
+           'w1_fragments', 'b1', 'w2_fragments', 'b2', 'rows', 'embed', 'hidden', 'ln1_weight', 'ln1_bias', 'ln1_eps']
+RC_VOL = ['B', 'Di', 'Hi', 'Wi', 'Cin', 'Do', 'Ho', 'Wo', 'Cout', 'ksize', 'stride', 'pad']
+RC_PARAMS = {
+    'rows_linear_x3': RC_IO + ['relu', 'out', 'out_row_stride', 'stream'],
+    'rows_linear_x3_add': RC_ADD + ['out', 'out_row_stride', 'stream'],
+    'rows_linear_x3_train': RC_ADD + ['residual', 'residual_row_stride', 'mask', 'mask_row_stride', 'out', 'out_row_stride', 'stream'],
+    'rows_linear_x3_ln': RC_LN,
+    'rows_linear_x3_planes': RC_IO + ['tokens_per_image', 'head_dim', 'out', 'stream'],
+    'rows_linear_x3_planes_e': RC_IO + ['tokens_per_image', 'head_dim', 'elem_type', 'out', 'stream'],
+    'rows_linear_f32': RC_IO + ['relu', 'out', 'out_row_stride', 'stream'],
+    'rows_linear_f32_add': RC_ADD + ['out', 'out_row_stride', 'stream'],
+    'rows_linear_f32_ln': RC_LN,
+    'rows_ffn_x3': ['x', 'x_row_stride', 'w1_fragments', 'b1', 'w2_fragments', 'b2', 'rows', 'in_features', 'hidden', 'out_features',
+                    'residual', 'residual_row_stride', 'ln_weight', 'ln_bias', 'ln_eps', 'out', 'out_row_stride', 'stream'],
+    'rows_tail_ffn_x3': RC_TAIL + ['out', 'out_row_stride', 'stream'],
+    'rows_tail_ffn_x3_planes': RC_TAIL + ['tokens_per_image', 'out', 'stream'],
+    'rows_linear_x3_fragments': ['weight', 'in_features', 'out_features', 'fragments', 'fragment_bytes', 'stream'],
+    'conv3d_ndhwc': ['x', 'weights', 'bias', 'residual'] + RC_VOL + ['relu', 'transposed', 'out', 'stream'],
+    'conv2d_nhwc': ['x', 'weights', 'bias', 'residual', 'B', 'Hi', 'Wi', 'Cin', 'Ho', 'Wo', 'Cout', 'ksize', 'stride', 'pad', 'relu', 'out', 'stream'],
+    'conv3d_ndhwc_bf16': ['x', 'weights', 'bias', 'residual'] + RC_VOL + ['relu', 'transposed', 'planar', 'out', 'stream'],
+    'conv3d_k3s1_tiled_bf16': ['x', 'weights', 'bias', 'residual', 'B', 'D', 'H', 'W', 'Cin', 'Cout', 'relu', 'out', 'stream'],
+    'conv3d_dgrad_ndhwc': ['dy', 'weights', 'bias', 'B', 'Do', 'Ho', 'Wo', 'Cout', 'Di', 'Hi', 'Wi', 'Cin', 'ksize', 'stride', 'pad', 'dx', 'stream'],
+    'conv3d_wgrad_ndhwc': ['x', 'dy'] + RC_VOL + ['dw', 'stream'],
+    'conv3d_wgrad_ndhwc_ex': ['x', 'dy'] + RC_VOL + ['dw', 'flags', 'ws', 'ws_bytes', 'stream'],
+}
+# a call that would LAUNCH (so no row below is this alone): 256 rows, 80 -> 80 features (embed 80), hidden 320, every optional operand
+# given, an addend for every row, 128 tokens per image in heads of 10 bf16 channels; 3 x 3 x 3, stride 1, padding 1 on one 8 x 8 x 8
+# volume (image, tile volume) of 32 -> 32 channels, the deterministic weight gradient; every pointer non-null and 16-byte aligned
+RC_BASE = dict(x_row_stride=0, out_row_stride=0, addend_row_stride=0, addend_period=1, residual_row_stride=0, residual0_row_stride=0,
+               mask_row_stride=0, rows=256, in_features=80, out_features=80, embed=80, hidden=320, relu=1, ln_eps=1e-5, ln0_eps=1e-5,
+               ln1_eps=1e-5, tokens_per_image=128, head_dim=10, elem_type=1, fragment_bytes=1 << 40, B=1, D=8, H=8, W=8, Di=8, Hi=8, Wi=8,
+               Cin=32, Do=8, Ho=8, Wo=8, Cout=32, ksize=3, stride=1, pad=1, transposed=0, planar=0, flags=1, ws_bytes=1 << 40,
+               stream=DA_NULL)
+RC_2G_ROW_TILES = 128 << 31                                          # rows of 2^31 128-row workgroups
+RC_2G_BLOCKS_X8 = dict(B=1 << 16, Di=1 << 10, Hi=1 << 10, Wi=1, Do=1 << 10, Ho=1 << 10, Wo=1)   # 2^28 blocks of 256 voxels: x 8 parities
+# 2^33 voxels in 2^21 chunks, 64 x 64 blocks of 64 x 64 channels, one tap: 2^33 tasks, four to a workgroup
+RC_2G_WGRAD = dict(ksize=1, pad=0, B=1 << 13, Di=1 << 10, Hi=1 << 10, Wi=1, Do=1 << 10, Ho=1 << 10, Wo=1, Cin=4096, Cout=4096)
+
+
+def rc_call(lib, entry, case):
+    """`entry` with RC_BASE's operands, `case` on top of them; 'null': every pointer the entry takes is null unless `case` names it"""
+    case = dict(case)
+    null = case.pop('null', False)
+    args = []
+    for name in RC_PARAMS[entry]:
+        if name in case:
+            args.append(case.pop(name))
+        elif name in RC_BASE:
+            args.append(RC_BASE[name])
+        else:
+            args.append(DA_NULL if null else DA_P16)
+    assert not case, (entry, 'operands the entry does not take', case)
+    return getattr(lib, 'fbbev_' + entry)(*args)
+
+
+def test_rows_and_conv_entries_keep_their_error_codes():
+    """Every entry of the row-wise linear layers and of the convolutions: the code of each argument check and which code wins where
+    two defects coincide (the order of an entry's checks is part of the ABI; the rows of
+    test_invalid_arguments_return_error_codes_without_touching_the_gpu hold the row-operand rule).  Every row returns BEFORE the
+    entry's first runtime call, so this runs without a GPU; below a 2^31-workgroup limit the next thing is a launch, so the limits
+    are pinned from the refusing side.  The two host functions are pinned as values."""
+    lib = _capi.declare(ctypes.CDLL(_capi.LIB_PATH))
+    NULL, P16, P8, P4 = DA_NULL, DA_P16, DA_P8, DA_P4
+    table = []
+    row = lambda entry, case, code: table.append((entry, case, code))   # noqa: E731
+    # ---- fbbev_rows_linear_x3 / _f32 and what their _add and _ln forms check in front
+    for fam in ('x3', 'f32'):
+        lin, add, ln = f'rows_linear_{fam}', f'rows_linear_{fam}_add', f'rows_linear_{fam}_ln'
+        for e in (lin, add, ln):
+            row(e, dict(rows=-1), -1)
+            row(e, dict(in_features=0), -1)
+            row(e, dict(out_features=0), -1)
+            row(e, dict(rows=0), 0)
+            row(e, dict(rows=0, x=NULL, weights=NULL, out=NULL, bias=NULL), 0)       # the empty call comes before the pointers
+            row(e, dict(rows=0, in_features=0, x=NULL), -1)                          # ... and behind the dimensions
+            for k in ('x', 'weights', 'out'):
+                row(e, {k: NULL}, -1)
+            row(e, dict(out=NULL, x=P8), -1)                                         # pointers before the row operands
+            row(e, dict(out=NULL, in_features=84), -1)
+            row(e, dict(in_features=84), -2)                                         # % 8
+            row(e, dict(weights=P8), -2)
+            row(e, dict(bias=P8), -2)
+            row(e, dict(in_features=84, x_row_stride=80), -1)                        # the row operands before the feature counts
+            row(e, dict(rows=RC_2G_ROW_TILES), -2)
+            row(e, dict(rows=RC_2G_ROW_TILES, x_row_stride=40), -1)                  # the row operands before the grid
+            row(e, dict(rows=RC_2G_ROW_TILES, weights=NULL), -1)
+        row(lin, dict(out_features=84, out_row_stride=80), -1)
+        row(lin, dict(out_features=82), -2)
+        row(lin, dict(rows=RC_2G_ROW_TILES >> 1, out_features=256), -2)              # two output chunks: 2^30 tiles x 2
+        row(add, dict(rows=RC_2G_ROW_TILES >> 1, out_features=256), -2)
+        row(add, dict(addend=NULL), -1)
+        row(add, dict(addend_period=0), -1)
+        row(add, dict(addend_period=-1), -1)
+        row(add, dict(addend=NULL, rows=-1), -1)
+        row(add, dict(addend_period=0, addend=P8), -1)
+        row(add, dict(addend=P8, in_features=0), -2)                                 # the addend before in_features <= 0
+        row(add, dict(addend_row_stride=82, rows=0), -2)                             # ... and before the empty call
+        row(add, dict(addend_row_stride=40, x=NULL), -1)
+        row(add, dict(addend=P8, x=NULL), -2)
+        row(ln, dict(ln_weight=NULL), -1)
+        row(ln, dict(ln_bias=NULL), -1)
+        row(ln, dict(ln_bias=NULL, out_features=132), -1)
+        row(ln, dict(out_features=132), -2)                                          # a workgroup holds whole rows: <= 128
+        row(ln, dict(out_features=256), -2)
+        row(ln, dict(out_features=132, residual_row_stride=40), -2)                  # ... before the residual
+        row(ln, dict(ln_weight=P8), -2)
+        row(ln, dict(ln_bias=P8), -2)
+        row(ln, dict(ln_weight=P8, rows=-1), -2)                                     # the LayerNorm operands before rows < 0
+        row(ln, dict(ln_weight=P8, rows=0), -2)
+        row(ln, dict(ln_weight=NULL, rows=0), -1)
+        row(ln, dict(residual=P8, ln_weight=NULL), -1)
+        row(ln, dict(residual=NULL, residual_row_stride=40, x=NULL), -1)
+    # ---- fbbev_rows_linear_x3_train: the feature counts first, an addend only when there is one (its period then 1), residual, mask
+    train = 'rows_linear_x3_train'
+    row(train, dict(out_features=0), -1)
+    row(train, dict(in_features=0), -1)
+    row(train, dict(in_features=0, addend=P8), -1)                                   # the feature counts before the addend
+    row(train, dict(out_features=0, residual=P8), -1)
+    row(train, dict(addend_period=0), -1)
+    row(train, dict(addend_period=0, x=P8), -1)
+    row(train, dict(addend=NULL, addend_period=0, x=P8), -2)                         # no addend: its period is not looked at
+    row(train, dict(addend=NULL, addend_period=-5, addend_row_stride=3, rows=-1), -1)
+    row(train, dict(addend=P8), -2)
+    row(train, dict(addend=P8, residual_row_stride=40), -2)
+    row(train, dict(residual=P8, mask_row_stride=40), -2)
+    row(train, dict(mask=P8, rows=-1), -2)                                           # mask before rows < 0
+    row(train, dict(mask=NULL, mask_row_stride=40, residual=NULL, residual_row_stride=40, rows=-1), -1)
+    row(train, dict(rows=-1), -1)
+    row(train, dict(rows=0), 0)
+    row(train, dict(rows=0, mask=P8), -2)
+    for k in ('x', 'weights', 'out'):
+        row(train, {k: NULL}, -1)
+    row(train, dict(in_features=84), -2)
+    row(train, dict(rows=RC_2G_ROW_TILES), -2)
+    # ---- the head planes: their own dimensions (-1) and divisibility / 16-bit limits (-2), out's alignment, then the shared checks
+    for e in ('rows_linear_x3_planes', 'rows_linear_x3_planes_e'):
+        row(e, dict(tokens_per_image=0), -1)
+        row(e, dict(head_dim=0), -1)
+        row(e, dict(out_features=0), -1)
+        row(e, dict(tokens_per_image=0, head_dim=11), -1)
+        row(e, dict(head_dim=11), -2)                                                # odd
+        row(e, dict(head_dim=32), -2)                                                # 80 % 32
+        row(e, dict(rows=250), -2)                                                   # rows % tokens_per_image
+        row(e, dict(rows=-1), -2)                                                    # ... which a negative count fails first
+        row(e, dict(rows=-128), -1)
+        row(e, dict(out_features=0x10000, head_dim=16), -2)                          # the 16-bit limits of the packed head width
+        row(e, dict(out_features=0x20000, head_dim=0x20000), -2)
+        row(e, dict(out_features=0x10000, head_dim=16, x=NULL), -2)
+        row(e, dict(head_dim=11, out=P4), -2)
+        row(e, dict(out=P4), -2)
+        row(e, dict(out=P4, rows=-128), -2)                                          # out's alignment before the shared checks
+        row(e, dict(out=P4, x=NULL), -2)
+        row(e, dict(rows=0), 0)
+        row(e, dict(rows=0, out=NULL, x=NULL), 0)
+        for k in ('x', 'weights', 'out'):
+            row(e, {k: NULL}, -1)
+        row(e, dict(in_features=84), -2)
+        row(e, dict(rows=RC_2G_ROW_TILES), -2)
+    row('rows_linear_x3_planes', dict(out=P8, x_row_stride=40), -1)                  # 8 bytes do for the entry's own test: x's rows win
+    row('rows_linear_x3_planes', dict(out=P8), -2)                                   # ... and the shared checks want 16
+    row('rows_linear_x3_planes_e', dict(out=P8, x_row_stride=40), -2)                # the 16-bit planes test 16 bytes themselves
+    row('rows_linear_x3_planes_e', dict(out=P8, x_row_stride=40, elem_type=0), -2)
+    row('rows_linear_x3_planes_e', dict(out=P4, elem_type=0), -2)
+    row('rows_linear_x3_planes_e', dict(elem_type=3), -1)
+    row('rows_linear_x3_planes_e', dict(elem_type=-1), -1)
+    row('rows_linear_x3_planes_e', dict(elem_type=3, head_dim=11), -1)
+    # ---- fbbev_rows_ffn_x3
+    ffn = 'rows_ffn_x3'
+    for k in ('in_features', 'hidden', 'out_features'):
+        row(ffn, {k: 0}, -1)
+    row(ffn, dict(rows=-1), -1)
+    row(ffn, dict(rows=0), 0)
+    row(ffn, dict(rows=0, null=True), 0)
+    row(ffn, dict(rows=0, hidden=0), -1)
+    for k in ('x', 'w1_fragments', 'b1', 'w2_fragments', 'b2', 'out'):
+        row(ffn, {k: NULL}, -1)
+    row(ffn, dict(ln_bias=NULL), -1)                                                 # a LayerNorm weight wants its bias
+    row(ffn, dict(ln_bias=NULL, x_row_stride=82), -1)
+    row(ffn, dict(ln_weight=NULL, ln_bias=NULL, residual=NULL, x=P8), -2)            # no LayerNorm, no residual: fine as far as they go
+    row(ffn, dict(residual=NULL, x=P8), -2)                                          # a LayerNorm without a residual is accepted
+    row(ffn, dict(b1=NULL, x_row_stride=40), -1)
+    row(ffn, dict(in_features=104), -2)                                              # > 96
+    row(ffn, dict(in_features=104, x_row_stride=100), -1)                            # the row operands before the shape limits
+    row(ffn, dict(in_features=84), -2)
+    row(ffn, dict(hidden=96), -2)
+    row(ffn, dict(hidden=352), -2)                                                   # % 32 is not enough
+    row(ffn, dict(out_features=84), -2)
+    row(ffn, dict(out_features=82), -2)
+    for k in ('w1_fragments', 'w2_fragments', 'b1', 'b2', 'ln_weight', 'ln_bias'):
+        row(ffn, {k: P8}, -2)
+    row(ffn, dict(rows=RC_2G_ROW_TILES), -2)
+    row(ffn, dict(rows=RC_2G_ROW_TILES, out_row_stride=40), -1)
+    row(ffn, dict(rows=RC_2G_ROW_TILES, out=NULL), -1)
+    # ---- fbbev_rows_tail_ffn_x3[_planes]
+    tail, tail_planes = 'rows_tail_ffn_x3', 'rows_tail_ffn_x3_planes'
+    TAIL_PTRS = ('x', 'w0_fragments', 'b0', 'ln0_weight', 'ln0_bias', 'w1_fragments', 'b1', 'w2_fragments', 'b2', 'ln1_weight', 'ln1_bias', 'out')
+    for e in (tail, tail_planes):
+        row(e, dict(rows=-1), -1)
+        row(e, dict(embed=0), -1)
+        row(e, dict(hidden=0), -1)
+        row(e, dict(rows=0), 0)
+        row(e, dict(rows=0, null=True), 0)
+        row(e, dict(rows=0, embed=0), -1)
+        for k in TAIL_PTRS:
+            row(e, {k: NULL}, -1)
+        row(e, dict(b0=NULL, x=P8), -1)
+        row(e, dict(embed=96), -2)
+        row(e, dict(embed=40), -2)                                                   # % 16
+        row(e, dict(hidden=96), -2)
+        row(e, dict(embed=96, x_row_stride=80), -1)
+        for k in TAIL_PTRS[1:-1]:
+            row(e, {k: P8}, -2)
+        row(e, dict(rows=RC_2G_ROW_TILES), -2)
+    row(tail, dict(rows=RC_2G_ROW_TILES, out_row_stride=40), -1)
+    row(tail, dict(rows=RC_2G_ROW_TILES, x=NULL), -1)
+    row(tail_planes, dict(tokens_per_image=0), -1)
+    row(tail_planes, dict(tokens_per_image=-1), -1)
+    row(tail_planes, dict(tokens_per_image=0, rows=0), -1)                           # the entry's own test before the empty call
+    row(tail_planes, dict(rows=250), -1)                                             # rows % tokens_per_image is BADARG here
+    row(tail_planes, dict(rows=250, embed=96), -1)
+    row(tail_planes, dict(rows=1 << 31), -2)                                         # 32-bit row arithmetic in the planes' store
+    row(tail_planes, dict(rows=1 << 31, x=NULL), -2)                                 # ... both tested before the pointers
+    row(tail_planes, dict(rows=250, x=NULL), -1)
+    row(tail_planes, dict(rows=(1 << 31) + 1), -1)
+    row(tail_planes, dict(rows=1 << 31, tokens_per_image=1 << 31), -2)
+    row(tail_planes, dict(rows=1 << 32, tokens_per_image=1 << 31, x=NULL), -2)
+    row(tail_planes, dict(rows=RC_2G_ROW_TILES, x_row_stride=40), -2)
+    # ---- fbbev_rows_linear_x3_fragments
+    frag = 'rows_linear_x3_fragments'
+    row(frag, dict(in_features=0), -1)
+    row(frag, dict(out_features=0), -1)
+    row(frag, dict(weight=NULL), -1)
+    row(frag, dict(fragments=NULL), -1)
+    row(frag, dict(fragments=NULL, fragment_bytes=0), -1)
+    row(frag, dict(fragments=P8), -3)
+    row(frag, dict(fragment_bytes=65535), -3)
+    row(frag, dict(fragment_bytes=393215, in_features=129, out_features=257), -3)
+    row(frag, dict(fragments=P8, in_features=0), -1)
+    # ---- the forward convolutions: dimensions (-1), the window (-2: kernel size 2 only in fp32 3-D), geometry (-1), the empty batch,
+    # pointers (-1), channels and alignment (-2), 2^31 workgroups (-2)
+    c3, c2, cb, ct = 'conv3d_ndhwc', 'conv2d_nhwc', 'conv3d_ndhwc_bf16', 'conv3d_k3s1_tiled_bf16'
+    for e in (c3, cb):
+        row(e, dict(B=-1), -1)
+        for k in RC_VOL[1:9]:
+            row(e, {k: 0}, -1)
+        row(e, dict(Di=0, ksize=4), -1)
+        for bad in (dict(ksize=0), dict(ksize=4), dict(stride=0), dict(stride=3), dict(pad=-1), dict(pad=2)):
+            row(e, bad, -2)
+            row(e, dict(bad, Do=7), -2)                                              # the window before the geometry
+            row(e, dict(bad, transposed=1, x=NULL), -1)                              # the transposed route sets its own window
+        for k in ('Do', 'Ho', 'Wo'):
+            row(e, {k: 7}, -1)
+            row(e, {k: 7, 'B': 0}, -1)                                               # the geometry before the empty batch
+            row(e, {k: 16, 'transposed': 1}, -1)
+        row(e, dict(B=0, ksize=4), -2)
+        row(e, dict(B=0), 0)
+        row(e, dict(B=0, null=True), 0)
+        row(e, dict(B=0, transposed=1, null=True), 0)
+        for k in ('x', 'weights', 'bias', 'out'):
+            row(e, {k: NULL}, -1)
+            row(e, {k: P8}, -2)
+        row(e, dict(residual=P8), -2)
+        row(e, dict(Cin=24), -2)
+        row(e, dict(Cin=24, out=NULL), -1)
+        row(e, dict(RC_2G_BLOCKS_X8, transposed=1), -2)
+        row(e, dict(RC_2G_BLOCKS_X8, transposed=1, Cout=48), -2)
+        row(e, dict(RC_2G_BLOCKS_X8, transposed=1, bias=NULL), -1)
+    row(c3, dict(ksize=2), -1)                                                       # fp32 has the 2 x 2 x 2 kernel: 8 -> 9 voxels is its geometry's refusal
+    row(c3, dict(ksize=2, stride=2, pad=0, Do=4, Ho=4, Wo=4, x=NULL), -1)
+    row(cb, dict(ksize=2), -2)
+    row(cb, dict(ksize=2, stride=2, pad=0, Do=4, Ho=4, Wo=4, x=NULL), -2)
+    row(cb, dict(Cin=16), -2)
+    row(cb, dict(planar=1), -1)                                                      # planar: one plane in, one plane out instead of the depth geometry
+    row(cb, dict(planar=1, Di=1, Do=1, x=NULL), -1)
+    row(cb, dict(planar=1, Di=1, Do=1, Cin=16), -2)                                  # ... accepted as far as the channels
+    row(cb, dict(planar=1, Di=1, Do=2), -1)
+    row(cb, dict(planar=1, Di=3, Do=1, pad=0, Ho=6, Wo=6, Cin=16), -1)               # (where the depth geometry itself would hold)
+    row(cb, dict(planar=1, Di=1, Do=1, Ho=7, Cin=16), -1)
+    row(cb, dict(planar=1, transposed=1), -1)
+    row(cb, dict(planar=1, transposed=1, Di=1, Do=1, ksize=9), -1)
+    row(cb, dict(planar=1, Di=1, Do=1, ksize=2), -2)
+    row(c2, dict(B=-1), -1)
+    for k in ('Hi', 'Wi', 'Cin', 'Ho', 'Wo', 'Cout'):
+        row(c2, {k: 0}, -1)
+    for bad in (dict(ksize=0), dict(ksize=2), dict(ksize=4), dict(stride=0), dict(stride=3), dict(pad=-1), dict(pad=2)):
+        row(c2, bad, -2)
+        row(c2, dict(bad, Ho=7), -2)
+        row(c2, dict(bad, Hi=0), -1)
+    for k in ('Ho', 'Wo'):
+        row(c2, {k: 7}, -1)
+        row(c2, {k: 7, 'B': 0}, -1)
+    row(c2, dict(B=0), 0)
+    row(c2, dict(B=0, null=True), 0)
+    for k in ('x', 'weights', 'bias', 'out'):
+        row(c2, {k: NULL}, -1)
+        row(c2, {k: P8}, -2)
+    row(c2, dict(residual=P8), -2)
+    row(c2, dict(Cin=24), -2)
+    row(c2, dict(Cin=24, x=NULL), -1)
+    row(ct, dict(B=-1), -1)
+    for k in ('D', 'H', 'W', 'Cin', 'Cout'):
+        row(ct, {k: 0}, -1)
+    row(ct, dict(B=0), 0)
+    row(ct, dict(B=0, null=True), 0)
+    row(ct, dict(B=0, D=0), -1)
+    for k in ('x', 'weights', 'bias', 'out'):
+        row(ct, {k: NULL}, -1)
+        row(ct, {k: P8}, -2)
+    row(ct, dict(residual=P8), -2)
+    row(ct, dict(Cin=16), -2)
+    row(ct, dict(Cin=16, bias=NULL), -1)
+    row(ct, dict(B=1 << 20, D=1 << 12, H=16, W=8), -2)                               # 2^31 tiles of 4 x 8 x 8
+    row(ct, dict(B=1 << 20, D=1 << 12, H=16, W=8, out=NULL), -1)
+    # ---- dgrad (the forward's checks; its kernel reads dy, so the 16-channel rule is Cout's) and wgrad
+    dg, wg, wgx = 'conv3d_dgrad_ndhwc', 'conv3d_wgrad_ndhwc', 'conv3d_wgrad_ndhwc_ex'
+    for e in (dg, wg, wgx):
+        ex = dict(flags=0) if e == wgx else {}
+        row(e, dict(ex, B=-1), -1)
+        for k in RC_VOL[1:9]:
+            row(e, dict(ex, **{k: 0}), -1)
+        for bad in (dict(ksize=0), dict(ksize=4), dict(stride=0), dict(stride=3), dict(pad=-1), dict(pad=2)):
+            row(e, dict(ex, **bad), -2)
+            row(e, dict(ex, Do=7, **bad), -2)
+            row(e, dict(ex, Di=0, **bad), -1)
+        row(e, dict(ex, ksize=2), -1)                                                # the 2 x 2 x 2 kernel is known: its geometry refuses
+        for k in ('Do', 'Ho', 'Wo'):
+            row(e, dict(ex, **{k: 7}), -1)
+            row(e, dict(ex, B=0, **{k: 7}), -1)
+        row(e, dict(ex, B=0), 0)
+        row(e, dict(ex, B=0, null=True), 0)
+    for k in ('dy', 'weights', 'bias', 'dx'):
+        row(dg, {k: NULL}, -1)
+        row(dg, {k: P8}, -2)
+    row(dg, dict(Cout=24), -2)
+    row(dg, dict(Cout=24, dx=NULL), -1)
+    for e in (wg, wgx):
+        for k in ('x', 'dy', 'dw'):
+            row(e, {k: NULL}, -1)
+        for k in ('x', 'dy'):
+            row(e, {k: P8}, -2)
+        row(e, dict(Cin=30), -2)
+        row(e, dict(Cout=30), -2)
+        row(e, dict(Cin=30, dw=NULL), -1)
+        row(e, dict(RC_2G_WGRAD, flags=0) if e == wgx else RC_2G_WGRAD, -2)
+    row(wgx, dict(RC_2G_WGRAD, ws_bytes=1 << 62), -2)
+    row(wgx, RC_2G_WGRAD, -3)                                                        # (2^57 bytes of partial sums: the workspace comes first)
+    row(wgx, dict(B=0, Di=0), 0)                                                     # deterministic: the empty batch before everything
+    row(wgx, dict(B=0, ws=NULL, ksize=4), 0)
+    row(wgx, dict(ws=NULL), -1)
+    row(wgx, dict(ws=NULL, ws_bytes=0), -1)
+    row(wgx, dict(ws_bytes=221183), -3)
+    row(wgx, dict(ws_bytes=221183, Di=0), -3)                                        # the workspace before the shape
+    row(wgx, dict(ws=NULL, Di=0), -1)
+    row(wgx, dict(Di=0), -1)
+    row(wgx, dict(ksize=4), -2)
+    row(wgx, dict(flags=0, ws=NULL, ws_bytes=0, x=P8), -2)                           # the atomic route takes no workspace
+    shown = lambda case: {k: (v.value if isinstance(v, ctypes.c_void_p) else v) for k, v in case.items()}   # noqa: E731
+    got = [(entry, shown(case), rc_call(lib, entry, case)) for entry, case, _ in table]
+    want = [(entry, shown(case), code) for entry, case, code in table]
+    assert got == want, [(g, w[2]) for g, w in zip(got, want) if g != w]
+    assert {entry for entry, _, _ in table} == set(RC_PARAMS)
+    frag_bytes, ws_bytes = lib.fbbev_rows_linear_x3_fragment_bytes, lib.fbbev_conv3d_wgrad_ws_bytes
+    assert [frag_bytes(i, o) for i, o in ((80, 80), (128, 128), (129, 128), (80, 129), (129, 257), (0, 80), (80, 0), (-1, -1))] == \
+        [65536, 65536, 131072, 131072, 393216, 0, 0, 0]
+    assert [ws_bytes(*a) for a in ((1, 8, 8, 8, 32, 32, 3, 1), (2, 9, 9, 9, 16, 32, 3, 1), (1, 8, 8, 8, 32, 32, 3, 0), (0, 8, 8, 8, 32, 32, 3, 1),
+                                  (1, 8, 8, 8, 32, 32, 0, 1), (1, 8, 8, 0, 32, 32, 3, 1), (1, 128, 128, 128, 80, 80, 1, 1))] == \
+        [221184, 331776, 0, 0, 0, 0, 13107200]
