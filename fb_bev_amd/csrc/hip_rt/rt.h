@@ -43,7 +43,12 @@ __device__ __forceinline__ float* fbbev_dyn_lds_f32() { return reinterpret_cast<
 // 16-byte store with a selectable cache policy for the write-once streaming output.
 //   0 plain | 1 nt (clang nontemporal builtin) | 2 sc1 | 3 sc0 sc1 | 4 sc1 nt | 5 sc0 nt | 6 sc0 sc1 nt | 7 sc0
 // (gfx950 cache-control bits; MI355X_MICROARCH.md "stores of each flavour").  Stores have no
-// return value, so the hand-written forms need no extra s_waitcnt bookkeeping.
+// return value, so the hand-written forms need no extra s_waitcnt bookkeeping.  They do need the wait states of the hardware's
+// store-data hazard: a VMEM store of more than 64 bits reads its data VGPRs after it has issued, and a VALU write to one of them
+// within the next two wait states (gfx940 and later) reaches memory instead of the value.  The compiler pads its own stores, but
+// it cannot see one inside an asm statement: k_pool_fwd_dense_cl<TV, 8, 4, 256> computed its second store's address into the
+// first store's data registers in the very next instruction, and channels 0-1 of voxel rows held that address
+// (tests/test_gpu_pool_kernels.py, cl-c80-tv64-cpl8).  Hence the `s_nop 1` behind every hand-written store.
 typedef float fbbev_v4f __attribute__((ext_vector_type(4)));
 typedef float fbbev_v2f __attribute__((ext_vector_type(2)));
 typedef unsigned int fbbev_v4u __attribute__((ext_vector_type(4)));
@@ -53,17 +58,17 @@ __device__ __forceinline__ void fbbev_store4(float* p, fbbev_v4f v) {
     if constexpr (ST == 1) {
         __builtin_nontemporal_store(v, reinterpret_cast<fbbev_v4f*>(p));
     } else if constexpr (ST == 2) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else if constexpr (ST == 3) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else if constexpr (ST == 4) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else if constexpr (ST == 5) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 nt" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 nt\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else if constexpr (ST == 6) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else if constexpr (ST == 7) {
-        asm volatile("global_store_dwordx4 %0, %1, off sc0" : : "v"(p), "v"(v) : "memory");
+        asm volatile("global_store_dwordx4 %0, %1, off sc0\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
     } else {
         *reinterpret_cast<fbbev_v4f*>(p) = v;
     }
