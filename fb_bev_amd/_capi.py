@@ -190,6 +190,8 @@ SIGNATURES = {
     'fbbev_depth_loss_grad': (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p]),
     'fbbev_points_to_depth': (c_int, [c_void_p, c_int, c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int] * 3 + [c_float, c_float] +
                               [c_void_p, c_void_p]),
+    'fbbev_image_prep': (c_int, [c_void_p, c_int64] + [c_int] * 5 + [c_void_p] * 4 + [c_int] + [c_void_p] * 3),
+    'fbbev_image_prep_limits': (c_int, [c_void_p] * 7),
 }
 
 _lib = None
@@ -2200,3 +2202,45 @@ def points_to_depth(points, offsets, max_points, lidar2img, post_rots, post_tran
                                            _dev(post_trans, F32, 'post_trans'), H, W, ds, float(depth_lo), float(depth_hi),
                                            _dev(out, F32, 'out'), _stream()), 'fbbev_points_to_depth')
     return out
+
+
+FLAG_IP_SWAP, FLAG_IP_CHANNELS_LAST = 1, 2          # include/fbbev.h FBBEV_IP_SWAP, FBBEV_IP_CHANNELS_LAST
+
+
+def image_prep_limits():
+    """fbbev_image_prep_limits -> dict(tile_w, tile_h, max_taps, max_box_w, max_box_h, max_src_rows, max_src_cols)"""
+    names = ('tile_w', 'tile_h', 'max_taps', 'max_box_w', 'max_box_h', 'max_src_rows', 'max_src_cols')
+    vals = [c_int(0) for _ in names]
+    _check(lib().fbbev_image_prep_limits(*[ctypes.cast(ctypes.pointer(v), c_void_p) for v in vals]), 'fbbev_image_prep_limits')
+    return {n: int(v.value) for n, v in zip(names, vals)}
+
+
+def image_prep(frames, plan, need, fH, fW, mean, inv_std, swap=True, channels_last=False, canvas=False, out=None):
+    """fbbev_image_prep: frames (n, Hs, Ws, 3) uint8 (any image stride, the rows of an image dense), plan int32 on the device and
+    `need` (five host ints) from fb_bev_amd.image_prep.build_plan, mean / inv_std three floats each -> imgs (n, 3, fH, fW) f32, in
+    channels-last strides when asked [, canvas (n, fH, fW, 3) uint8]; see include/fbbev.h.  Bit-identical from run to run."""
+    require_gpu(frames, 'frames')
+    if frames.dtype != U8 or frames.dim() != 4 or frames.shape[3] != 3:
+        raise FbbevError(f'frames must be (n, Hs, Ws, 3) uint8, got {frames.dtype} {tuple(frames.shape)}')
+    n, Hs, Ws = (int(v) for v in frames.shape[:3])
+    if n == 0 or tuple(frames.stride()[1:]) != (Ws * 3, 3, 1):
+        raise FbbevError(f'frames must hold at least one image with dense rows, got shape {tuple(frames.shape)} strides {frames.stride()}')
+    stride = frames.stride(0) if n > 1 else Hs * Ws * 3
+    fH, fW = int(fH), int(fW)
+    if out is None:
+        out = torch.empty((n, 3, fH, fW), dtype=F32, device=frames.device,
+                          memory_format=torch.channels_last if channels_last else torch.contiguous_format)
+    elif tuple(out.shape) != (n, 3, fH, fW) or not out.is_contiguous(
+            memory_format=torch.channels_last if channels_last else torch.contiguous_format):
+        raise FbbevError(f'out must be {(n, 3, fH, fW)} in the asked memory format, got {tuple(out.shape)} strides {out.stride()}')
+    cv = torch.empty((n, fH, fW, 3), dtype=U8, device=frames.device) if canvas else None
+    host_need = (c_int * 5)(*[int(v) for v in need])
+    m3 = (c_float * 3)(*[float(v) for v in mean])
+    s3 = (c_float * 3)(*[float(v) for v in inv_std])
+    flags = (FLAG_IP_SWAP if swap else 0) | (FLAG_IP_CHANNELS_LAST if channels_last else 0)
+    with _on(frames):
+        _check(lib().fbbev_image_prep(_dev(frames, U8, 'frames', contiguous=False), int(stride), n, Hs, Ws, fH, fW, _dev(plan, I32, 'plan'),
+                                      ctypes.cast(host_need, c_void_p), ctypes.cast(m3, c_void_p), ctypes.cast(s3, c_void_p), flags,
+                                      _dev(out, F32, 'out', contiguous=False), None if cv is None else _dev(cv, U8, 'canvas'), _stream()),
+               'fbbev_image_prep')
+    return (out, cv) if canvas else out

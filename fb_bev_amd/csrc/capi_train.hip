@@ -9,6 +9,7 @@
 #include "occ_lovasz_kernels.h"
 #include "depth_loss_kernels.h"
 #include "points_depth_kernels.h"
+#include "image_prep_kernels.h"
 #include "../../include/fbbev.h"
 
 // ------------------------------------------------------------------------------ weight / bias gradient of a row-wise linear layer
@@ -533,6 +534,45 @@ extern "C" int fbbev_points_to_depth(const float* points, int point_stride, cons
     if (blocks < 1) blocks = 1;
     if (blocks > FBBEV_PD_RESOLVE_BLOCKS) blocks = FBBEV_PD_RESOLVE_BLOCKS;
     FBBEV_LAUNCH(k_points_depth_resolve, blocks, FBBEV_PD_THREADS, 0, stream, plane, n, (int)head, nv);
+    FBBEV_CHECK_LAUNCH();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------ camera frames -> network input
+extern "C" int fbbev_image_prep_limits(int* tile_w, int* tile_h, int* max_taps, int* max_box_w, int* max_box_h, int* max_src_rows,
+                                       int* max_src_cols) {
+    if (!tile_w || !tile_h || !max_taps || !max_box_w || !max_box_h || !max_src_rows || !max_src_cols) return FBBEV_E_BADARG;
+    *tile_w = FBBEV_IP_TILE_W;
+    *tile_h = FBBEV_IP_TILE_H;
+    *max_taps = FBBEV_IP_MAX_TAPS;
+    *max_box_w = FBBEV_IP_BOX_W;
+    *max_box_h = FBBEV_IP_BOX_H;
+    *max_src_rows = FBBEV_IP_SRC_ROWS;
+    *max_src_cols = FBBEV_IP_SRC_COLS;
+    return 0;
+}
+
+extern "C" int fbbev_image_prep(const uint8_t* frames, long long image_stride, int n_img, int Hs, int Ws, int fH, int fW,
+                                const int32_t* plan, const int32_t* host_need, const float* mean3, const float* inv_std3, int flags,
+                                float* out, uint8_t* canvas, fbbev_stream_t stream_) {
+    if (!frames || !plan || !host_need || !mean3 || !inv_std3 || !out) return FBBEV_E_BADARG;
+    if (n_img < 0 || Hs <= 0 || Ws <= 0 || fH <= 0 || fW <= 0 || (flags & ~(FBBEV_IP_SWAP | FBBEV_IP_CHANNELS_LAST))) return FBBEV_E_BADARG;
+    if (image_stride < (long long)Hs * Ws * 3) return FBBEV_E_BADARG;
+    for (int i = 0; i < 5; ++i)
+        if (host_need[i] < 0) return FBBEV_E_BADARG;
+    if (n_img == 0) return 0;
+    if (host_need[0] > FBBEV_IP_MAX_TAPS || host_need[1] > FBBEV_IP_BOX_W || host_need[2] > FBBEV_IP_BOX_H ||
+        host_need[3] > FBBEV_IP_SRC_ROWS || host_need[4] > FBBEV_IP_SRC_COLS)
+        return FBBEV_E_UNSUPPORTED;
+    if (!aligned16(out) || (reinterpret_cast<uintptr_t>(frames) & 3u) || (reinterpret_cast<uintptr_t>(plan) & 3u)) return FBBEV_E_UNSUPPORTED;
+    if (fH >= 16384 || fW >= 16384 || Hs >= (1 << 24) || Ws >= (1 << 24)) return FBBEV_E_UNSUPPORTED;   // the 16.16 walk; row * Ws in 48 bits
+    const long long tiles_x = (fW + FBBEV_IP_TILE_W - 1) / FBBEV_IP_TILE_W, tiles_y = (fH + FBBEV_IP_TILE_H - 1) / FBBEV_IP_TILE_H;
+    const long long grid = tiles_x * tiles_y * n_img;
+    if (grid >= (1ll << 31)) return FBBEV_E_UNSUPPORTED;
+    const long long frames_end = (long long)(n_img - 1) * image_stride + (long long)Hs * Ws * 3;
+    FBBEV_LAUNCH(k_image_prep, grid, FBBEV_IP_THREADS, 0, (fbbev_rt_stream)stream_, (const unsigned char*)frames, image_stride, frames_end,
+                 Hs, Ws, fH, fW, (int)tiles_x, (int)tiles_y, (const int*)plan, mean3[0], mean3[1], mean3[2], inv_std3[0], inv_std3[1],
+                 inv_std3[2], (flags & FBBEV_IP_SWAP) ? 1 : 0, (flags & FBBEV_IP_CHANNELS_LAST) ? 1 : 0, out, (unsigned char*)canvas);
     FBBEV_CHECK_LAUNCH();
     return 0;
 }

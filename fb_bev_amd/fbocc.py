@@ -87,6 +87,10 @@ class FBOCC(nn.Module):
         the LiDAR sweeps (points_depth.points_to_depth: a list of (P_i, >= 3) tensors, img_inputs' post_rots / post_trans, the image
         size, the depth net's grid_config['depth'], downsample 1) instead of taking it from the loader; a gt_depth that is given
         is used as it is; default off;
+        images_from_frames=True: forward_train / forward_test / predict_occupancy / predict_occupancy_classes accept img_inputs[0] as
+        raw camera frames, uint8 (B, N, Hs, Ws, 3) on the GPU, together with the keyword img_augs (B * N entries, or B lists of N, of
+        PrepareImageInputs' (resize, resize_dims, crop, flip, rotate)), and prepare them on the device (image_prep.prepare_images;
+        channels-last when the image backbone runs channels-last); a float img_inputs[0] passes through untouched; default off;
         mfma_conv3d / mfma_conv3d_train=True route the voxel encoder + head through fbbev_conv3d_* (mfma_conv3d.py)."""
         super().__init__()
         if frpn is not None or pts_bbox_head is not None:
@@ -103,6 +107,7 @@ class FBOCC(nn.Module):
         if self.depth_net is not None and ex.get('fused_depth_loss') is not None:
             self.depth_net.fused_depth_loss = bool(ex['fused_depth_loss'])
         self.depth_from_points = bool(ex.get('depth_from_points', False))
+        self.images_from_frames = bool(ex.get('images_from_frames', False))
         fvt = FBViewTransform(forward_projection, backward_projection, readd=readd)
         self.forward_projection = fvt.forward_projection
         self.backward_projection = fvt.backward_projection
@@ -284,6 +289,28 @@ class FBOCC(nn.Module):
         ret['img_bev_feat'] = self.bev_encoder(bev_feat)
         return ret
 
+    def _frames_to_images(self, img_inputs, kwargs):
+        """execution=dict(images_from_frames=True): img_inputs with raw uint8 frames in [0] -> img_inputs with the prepared floats;
+        with the flag on, img_augs leaves kwargs (extract_feat never sees it)"""
+        if not self.images_from_frames:
+            return img_inputs
+        augs = kwargs.pop('img_augs', None)
+        if img_inputs is None or img_inputs[0].dtype != torch.uint8:
+            return img_inputs
+        frames = img_inputs[0]
+        if frames.dim() != 5 or frames.shape[-1] != 3:
+            raise ValueError(f'raw frames must be uint8 (B, N, Hs, Ws, 3), got {tuple(frames.shape)}')
+        if augs is None:
+            raise ValueError('raw frames need img_augs: one (resize, resize_dims, crop, flip, rotate) per frame')
+        from .image_prep import prepare_images
+        B, N = frames.shape[:2]
+        augs = list(augs)
+        if augs and isinstance(augs[0][0], (list, tuple)):                               # B lists of N
+            augs = [a for sample in augs for a in sample]
+        cl = bool(getattr(self.img_backbone, 'channels_last', False))
+        imgs = prepare_images(frames.reshape(B * N, *frames.shape[2:]), augs, channels_last=cl)
+        return [imgs.view(B, N, *imgs.shape[1:])] + list(img_inputs[1:])
+
     def extract_feat(self, points, img, img_metas, **kwargs):
         return self.extract_img_bev_feat(img, img_metas, **kwargs) if img is not None else {}
 
@@ -291,6 +318,7 @@ class FBOCC(nn.Module):
     def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
                       gt_bboxes=None, img_inputs=None, proposals=None, gt_bboxes_ignore=None, gt_occupancy_flow=None,
                       **kwargs):
+        img_inputs = self._frames_to_images(img_inputs, kwargs)
         if self.depth_from_points:
             lidar2img = kwargs.pop('lidar2img', None)                                                     # extract_feat never sees it
             if (kwargs.get('gt_depth') is None and points is not None and lidar2img is not None and self.use_depth_supervision
@@ -328,6 +356,7 @@ class FBOCC(nn.Module):
     def predict_occupancy(self, img_inputs, img_metas, return_raw_occ=False, **kwargs):
         """simple_test's device-side part for a whole batch: -> (B, X', Y', Z) class ids (or (B, X', Y', Z, classes)
         probabilities) in the CVPR-2023 axis convention of :547-552, still on the GPU."""
+        img_inputs = self._frames_to_images(img_inputs, kwargs)
         results = self.extract_feat(None, img=img_inputs, img_metas=img_metas, **kwargs)
         if 'img_bev_feat_ndhwc' in results:
             occ = self._mfma_stacks()[2](results['img_bev_feat_ndhwc'])                           # (B,cls,H,W,D) view
@@ -350,6 +379,7 @@ class FBOCC(nn.Module):
         scores the batch against gt_occupancy / mask_camera (B, X', Y', Z) into it.  With `fscore` (occ_metrics.Metric_FScore) the
         class map is scored into it on the device (fbbev_occ_fscore_counts), with or without `metric`."""
         from . import _capi
+        img_inputs = self._frames_to_images(img_inputs, kwargs)
         results = self.extract_feat(None, img=img_inputs, img_metas=img_metas, **kwargs)
         if 'img_bev_feat_ndhwc' in results:
             occ = self._mfma_stacks()[2](results['img_bev_feat_ndhwc'])                           # (B,cls,H,W,D) channels-last view
